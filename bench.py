@@ -3,8 +3,14 @@
 
 A "step" is one pass of the hot path (lock-step transition kernel + 256-deep re-run of
 overflowing systems + counter reduction) over this rank's batch of synthetic systems, whose
-packed traces are already resident in HBM (generated on the device before warmup; the
-generator pass is timed separately as the trace-streaming phase).
+packed traces are already resident in HBM (generated on the device before warmup; with --full
+the generator pass is timed separately as the trace-streaming phase).
+
+A plain run sets up, warms up, times the steps, writes its outputs if --dump-outputs is given
+and prints the result line.  --full adds everything else after the timed steps: the
+trace-generator, text-parser and dump-formatter phases, the per-type message pass, the parity
+checks against the reference's aggregates and the golden fixtures (a mismatch exits 3) and the
+CPU baselines; the line's fields for these are null without it.
 
 Default workload (N=1): BASELINE.json configs[2] / SURVEY 8d C3 -- 1M synthetic 8-node
 systems, uniform RD/WR over 0x00-0x7F, 4096 instructions per node, seed 1.  With N GPUs each
@@ -12,6 +18,7 @@ rank simulates its own 1M systems (ids rank*1M ..), i.e. weak scaling; the only 
 the final RCCL all-reduce of the counters.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config random|hot|evict]
+                    [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
 With --gpus N > 1 and no torch.distributed launcher around it (WORLD_SIZE unset), the process
@@ -328,25 +335,44 @@ def issue_from_profiles(config):
     return _load_json(os.path.join(REPO, "profiles", "pmc_issue.json")).get(config) or None
 
 
-def run_c_driver(args):
-    """bench.py --driver c: the C multi-GPU driver (hp-assignment-2_amd/dsm_ensemble: one
-    process, one host thread per GPU, RCCL all-reduce through dsm_group_*) over N GPUs; its
-    per-rank aggregates, job total, counters and per-type counts are checked here against the
-    reference's, and the bench line is printed from its JSON.  Returns the exit code (3 on a
-    parity mismatch)."""
+DUMP_BUDGET = 48 * 10 ** 6      # bytes of per-system rows in a --dump-outputs directory
+
+
+def dump_outputs(path, rank, first, res, counters):
+    """--dump-outputs: what the last timed step handed back, as float64 .npy files (every value
+    is a 32-bit word or a sum of a few, so float64 holds it exactly):
+      results.npy   [k, 8]  per system: status, rounds, msgs, instrs, then the low and high
+                            32-bit halves of dump_hash and of final_hash;
+      systems.npy   [k]     the system ids of those rows: all of this rank's systems, or, when
+                            they would not fit DUMP_BUDGET, a fixed seeded sample in id order;
+      counters.npy  [n, 2]  the step's dsm_counters vector (this rank's, before any
+                            all-reduce) up to max_rounds, low and high 32-bit halves of each
+                            slot.  The slots after it (overflow_reruns .. ser_iterations) say
+                            how the schedule spent its waves, which varies from run to run on
+                            the same inputs, so they are left out.
+    Ranks above 0 write <name>.rank<r>.npy."""
     import pydsm
-    dname, n_sys, n_instr, seed, workload = CONFIGS[args.config]
-    if args.systems:
-        n_sys = args.systems
-    cmd = [os.path.join(PKG, "dsm_ensemble"), "--gpus", str(args.gpus), "--config", args.config,
-           "--steps", str(args.steps), "--warmup", str(args.warmup), "--systems", str(n_sys)]
-    if not args.no_types:
-        cmd.append("--type-counts")
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    sys.stderr.write(r.stderr)
-    if r.returncode != 0:
-        return r.returncode
-    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    os.makedirs(path, exist_ok=True)
+    n = len(res)
+    k = min(n, DUMP_BUDGET // (8 * 8))
+    idx = np.arange(n) if k == n else np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+    r = res[idx]
+    lo = np.uint64(0xFFFFFFFF)
+    rows = np.stack([r["status"], r["rounds"], r["msgs"], r["instrs"],
+                     r["dump_hash"] & lo, r["dump_hash"] >> np.uint64(32),
+                     r["final_hash"] & lo, r["final_hash"] >> np.uint64(32)],
+                    axis=1).astype(np.float64)
+    c = np.asarray(counters, dtype=np.uint64).reshape(-1)[:pydsm.MAX_SLOT + 1]
+    suffix = f".rank{rank}" if rank else ""
+    for name, a in (("results", rows), ("systems", (idx + first).astype(np.float64)),
+                    ("counters", np.stack([c & lo, c >> np.uint64(32)], axis=1).astype(np.float64))):
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), a)
+
+
+def c_driver_parity(d, dname, seed, n_instr, n_sys):
+    """The C driver's per-rank aggregates, job total, counters and per-type counts against
+    the reference's: (parity string, source of the job's reference aggregate, shard tally)."""
+    import pydsm
     tally = dict(ok=0, bad=0, unpinned=0)
     for rk in d["ranks"]:
         gold, src = golden_for(dname, seed, n_instr, rk["first_sys"], rk["systems"])
@@ -378,6 +404,31 @@ def run_c_driver(args):
         elif gold is not None and gold.get("msgs_by_type"):
             parity += ("; msgs_by_type == reference (13 types)" if by_type == gold["msgs_by_type"]
                        else "; MSGS_BY_TYPE MISMATCH vs reference")
+    return parity, src, tally
+
+
+def run_c_driver(args):
+    """bench.py --driver c: the C multi-GPU driver (hp-assignment-2_amd/dsm_ensemble: one
+    process, one host thread per GPU, RCCL all-reduce through dsm_group_*) over N GPUs; its
+    per-rank aggregates, job total, counters and per-type counts are checked here against the
+    reference's (--full only), and the bench line is printed from its JSON.  Returns the exit
+    code (3 on a parity mismatch)."""
+    import pydsm
+    dname, n_sys, n_instr, seed, workload = CONFIGS[args.config]
+    if args.systems:
+        n_sys = args.systems
+    cmd = [os.path.join(PKG, "dsm_ensemble"), "--gpus", str(args.gpus), "--config", args.config,
+           "--steps", str(args.steps), "--warmup", str(args.warmup), "--systems", str(n_sys)]
+    if args.full and not args.no_types:
+        cmd.append("--type-counts")
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    sys.stderr.write(r.stderr)
+    if r.returncode != 0:
+        return r.returncode
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    world = d["n_gpus"]
+    parity, src, tally = c_driver_parity(d, dname, seed, n_instr, n_sys) if args.full else (None,) * 3
+    by_type = d.get("msgs_by_type")
     kavg = float(np.mean(d["kernel_ms"])) if d["kernel_ms"] else float("nan")
     r0 = d["ranks"][0]["aggregate"]
     alg_bytes = 2 * r0["instrs"] + (32 + 4 * NP) * r0["systems"]
@@ -407,10 +458,10 @@ def run_c_driver(args):
         "msgs_by_type": dict(zip(pydsm.TYPE_NAMES, by_type)) if by_type is not None else None,
         "kernel_ms": d["kernel_ms"],
         "parity": parity,
-        "parity_detail": dict(job_source=src, shards=tally),
+        "parity_detail": dict(job_source=src, shards=tally) if args.full else None,
     }
     print(json.dumps(rec), flush=True)
-    return 3 if "MISMATCH" in parity else 0
+    return 3 if args.full and "MISMATCH" in parity else 0
 
 
 def main():
@@ -436,7 +487,19 @@ def main():
     ap.add_argument("--driver", default="py", choices=("py", "c"),
                     help="c: the C multi-GPU driver (hp-assignment-2_amd/dsm_ensemble: one host "
                          "thread per GPU, RCCL), checked here against the reference aggregates")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything that is not the headline "
+                         "figure: the trace-generator / text-parser / dump-formatter phases, the "
+                         "per-type message pass, the parity checks against the reference's "
+                         "aggregates and golden fixtures, and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (per-system results, "
+                         "counters) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.driver == "c":
+        ap.error("--dump-outputs needs the Python driver (--driver py)")
 
     if args.driver == "c":
         if "WORLD_SIZE" in os.environ and os.environ["WORLD_SIZE"] != "1":
@@ -493,20 +556,21 @@ def main():
     if not args.fused:
         traces = torch.empty((n_sys, NP, n_instr), dtype=torch.int16, device=dev)
         counts = torch.empty((n_sys, NP), dtype=torch.int32, device=dev)
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         eng.generate_device(dname, seed, n_instr, first, n_sys, traces.data_ptr(),
                             counts.data_ptr(), sp)              # cold (first-touch) pass
-        ev0.record(stream)
-        eng.generate_device(dname, seed, n_instr, first, n_sys, traces.data_ptr(),
-                            counts.data_ptr(), sp)
-        ev1.record(stream)
-        torch.cuda.synchronize(dev)
-        gms = ev0.elapsed_time(ev1)
-        gbytes = traces.numel() * 2 + counts.numel() * 4
-        trace_stream = dict(kernel="gen_kernel (trace generator, writes packed traces)",
-                            bytes=gbytes, ms=round(gms, 3),
-                            achieved_gbs=round(gbytes / gms / 1e6, 1), peak_gbs=HBM_PEAK_GBS,
-                            frac=round(gbytes / gms / 1e6 / HBM_PEAK_GBS, 4))
+        if args.full:       # the trace-streaming phase: a second, timed generator pass
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev0.record(stream)
+            eng.generate_device(dname, seed, n_instr, first, n_sys, traces.data_ptr(),
+                                counts.data_ptr(), sp)
+            ev1.record(stream)
+            torch.cuda.synchronize(dev)
+            gms = ev0.elapsed_time(ev1)
+            gbytes = traces.numel() * 2 + counts.numel() * 4
+            trace_stream = dict(kernel="gen_kernel (trace generator, writes packed traces)",
+                                bytes=gbytes, ms=round(gms, 3),
+                                achieved_gbs=round(gbytes / gms / 1e6, 1), peak_gbs=HBM_PEAK_GBS,
+                                frac=round(gbytes / gms / 1e6 / HBM_PEAK_GBS, 4))
 
     def step():
         cnt.zero_()
@@ -537,12 +601,16 @@ def main():
     # the transition kernel's device time per step (HIP events around its launches, on the
     # stream they run on), read after the timed region
     kms = eng.kernel_ms_history(min(args.steps, 64))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, first,
+                     out.cpu().numpy().view(pydsm.RESULT_DTYPE).reshape(-1),
+                     cnt.cpu().numpy().view(np.uint64))
 
     # initializeProcessor's reader on the GPU (parse_kernel): the same workload's core files as
     # text (shipped-test format) for the first --parse-systems systems, scanned back into packed
     # traces; timed separately, not part of `value`; checked bit-exact against gen_kernel
     trace_parse = None
-    if args.parse_systems and not args.fused:
+    if args.full and args.parse_systems and not args.fused:
         ps = min(args.parse_systems, n_sys)
         off = torch.zeros(ps * NP + 1, dtype=torch.int64, device=dev)
         eng.generate_text_device(dname, seed, n_instr, first, ps, 0, off.data_ptr(), sp)
@@ -578,7 +646,7 @@ def main():
     # printProcessorState of every node's final record, formatted on the GPU (fmt_kernel):
     # the dump/checksum writer phase, HBM-write-bound; timed separately, not part of `value`
     dump_stream = None
-    if not args.no_dump:
+    if args.full and not args.no_dump:
         n_rec = n_sys * NP
         d_txt = torch.empty(n_rec * pydsm.DUMP_SLOT, dtype=torch.uint8, device=dev)
         d_len = torch.empty(n_rec, dtype=torch.int32, device=dev)
@@ -631,7 +699,7 @@ def main():
     # with DSM_F_TYPE_COUNTS (the one-pass lock-step kernel with per-type counters); its
     # totals must equal the timed run's messages and the reference's per-type totals
     type_pass = None
-    if not args.fused and not args.no_types:
+    if args.full and not args.fused and not args.no_types:
         teng = pydsm.Engine(NP, n_instr, ring_cap=args.ring, device=local, type_counts=True)
         tcnt = torch.zeros(pydsm.NCOUNTERS, dtype=torch.int64, device=dev)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -650,27 +718,29 @@ def main():
     # rank's shard against the reference's own handler text (its full-size aggregate:
     # counters, status counts, hash sums, position-sensitive result digest), then the job's
     # all-reduced aggregate against the reference's total over ids [0, world * n)
-    res_host = out.cpu().numpy().view(pydsm.RESULT_DTYPE).reshape(-1)
-    mine, verdict, shard_msg = shard_parity(dname, seed, n_instr, first, res_host, local_c)
-    # the library's device fold of the same results (dsm_aggregate_device, what the C driver
-    # all-reduces) must equal the host fold
-    agg_dev = torch.zeros(pydsm.NAGG, dtype=torch.int64, device=dev)
-    eng.aggregate_device(out, n_sys, first, agg_dev, sp)
-    torch.cuda.synchronize(dev)
-    dev_diff = pydsm.aggregate_diff(pydsm.agg_vec_to_dict(agg_dev.cpu().numpy().view(np.uint64)), mine)
-    if dev_diff:
-        verdict = "bad"
-        shard_msg += "; DEVICE AGGREGATE MISMATCH: " + ",".join(dev_diff)
-    print(f"bench.py rank {rank}: {shard_msg}", file=sys.stderr, flush=True)
-    avec = torch.from_numpy(agg_to_vec(mine, verdict).view(np.int64).copy())
-    if group is not None:       # dsm_aggregate layout: the shard tallies ride in its reserved slots
-        avec = avec.to(dev)
-        group.allreduce_aggregate(avec, sp)
+    parity = parity_detail = verdict = res_host = None
+    if args.full:
+        res_host = out.cpu().numpy().view(pydsm.RESULT_DTYPE).reshape(-1)
+        mine, verdict, shard_msg = shard_parity(dname, seed, n_instr, first, res_host, local_c)
+        # the library's device fold of the same results (dsm_aggregate_device, what the C driver
+        # all-reduces) must equal the host fold
+        agg_dev = torch.zeros(pydsm.NAGG, dtype=torch.int64, device=dev)
+        eng.aggregate_device(out, n_sys, first, agg_dev, sp)
         torch.cuda.synchronize(dev)
-    else:
-        avec = reduce_vector(avec.to(cdev), dist if use_dist else None, (AGG_MAX,))
-    parity, parity_detail = job_parity(dname, seed, n_instr, world, n_sys,
-                                       avec.cpu().numpy().view(np.uint64), c)
+        dev_diff = pydsm.aggregate_diff(pydsm.agg_vec_to_dict(agg_dev.cpu().numpy().view(np.uint64)), mine)
+        if dev_diff:
+            verdict = "bad"
+            shard_msg += "; DEVICE AGGREGATE MISMATCH: " + ",".join(dev_diff)
+        print(f"bench.py rank {rank}: {shard_msg}", file=sys.stderr, flush=True)
+        avec = torch.from_numpy(agg_to_vec(mine, verdict).view(np.int64).copy())
+        if group is not None:   # dsm_aggregate layout: the shard tallies ride in its reserved slots
+            avec = avec.to(dev)
+            group.allreduce_aggregate(avec, sp)
+            torch.cuda.synchronize(dev)
+        else:
+            avec = reduce_vector(avec.to(cdev), dist if use_dist else None, (AGG_MAX,))
+        parity, parity_detail = job_parity(dname, seed, n_instr, world, n_sys,
+                                           avec.cpu().numpy().view(np.uint64), c)
     if type_pass is not None:
         gold, _ = golden_for(dname, seed, n_instr, 0, world * n_sys)
         ok_sum = sum(type_pass["msgs_by_type"]) == c["msgs"] == type_pass["msgs"]
@@ -742,7 +812,7 @@ def main():
                 phase["traffic"] = tr[kname].get("bytes_per_launch")
         # and system by system: the golden per-system prefix (tests/golden/ensemble/np8_<dist>.npy)
         gp = os.path.join(GOLDEN, "ensemble", f"np8_{dname}.npy")
-        if first == 0 and os.path.exists(gp):
+        if args.full and first == 0 and os.path.exists(gp):
             g = np.load(gp)
             r = res_host[:len(g)]
             mine6 = np.stack([r["status"].astype(np.uint64), r["rounds"].astype(np.uint64),
@@ -751,7 +821,7 @@ def main():
             parity += (f"; golden[0:{len(r)}] bit-exact" if np.array_equal(mine6, g[:len(r)])
                        else "; GOLDEN MISMATCH")
         cpu = cpu_port = None
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             hc = host_cpu()
             threads = hc["threads"]
             cpu = cpu_baseline_reference(dname, n_instr, seed,
@@ -821,7 +891,7 @@ def main():
     if use_dist:
         dist.destroy_process_group()
     # a failed parity check fails the run: this rank's shard, and on rank 0 the job's line
-    if verdict == "bad" or (rank == 0 and "MISMATCH" in parity):
+    if args.full and (verdict == "bad" or (rank == 0 and "MISMATCH" in parity)):
         sys.exit(3)
 
 

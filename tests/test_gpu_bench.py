@@ -14,7 +14,7 @@ from conftest import REPO
 
 pytestmark = pytest.mark.gpu
 
-SMALL = ["--systems", "32768", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-dump",
+SMALL = ["--systems", "32768", "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--no-dump",
          "--parse-systems", "0"]
 
 
@@ -64,7 +64,7 @@ def test_c_driver_one_gpu_pinned_prefix():
     fixture pins: its device aggregate (dsm_aggregate_device) and the reduced counters equal the
     reference's, and its per-type counts sum to the messages."""
     line = _bench(["--driver", "c", "--gpus", "1", "--systems", "4096", "--steps", "2",
-                   "--warmup", "1"])
+                   "--warmup", "1", "--full"])
     assert line["n_gpus"] == 1 and line["driver"].startswith("dsm_ensemble (C")
     assert line["parity"].startswith("full-size aggregate == reference (job total over 1 shard(s), "
                                      "aggregates.json:np8_uniform)"), line["parity"]
@@ -72,6 +72,38 @@ def test_c_driver_one_gpu_pinned_prefix():
     assert "msgs_by_type == reference (13 types)" in line["parity"], line["parity"]
     assert sum(line["msgs_by_type"].values()) == line["counters"]["msgs"]
     assert line["value"] > 0 and line["collective"].startswith("rccl ncclAllReduce over 1 GPU")
+
+
+def test_plain_run_times_the_steps_and_dumps_the_last_steps_results(tmp_path):
+    """A plain run (no --full): --steps timed steps, the headline fields, nothing of the side
+    phases, parity checks or baselines; --dump-outputs writes the last timed step's per-system
+    results and counters, which equal the golden per-system fixture of the reference's handler
+    text (tests/golden/ensemble/np8_uniform.npy: the 4096 systems run here) word for word."""
+    import numpy as np
+    import pydsm
+    from conftest import golden_ensemble
+    line = _bench(["--gpus", "1", "--systems", "4096", "--steps", "3", "--warmup", "1",
+                   "--dump-outputs", str(tmp_path)])
+    assert line["steps"] == 3 and line["warmup"] == 1 and len(line["kernel_ms"]) == 3
+    assert line["ms_per_step"] > 0 and line["value"] > 0 and line["dtype"] == "u8"
+    assert line["unit"] == "transactions/s" and line["higher_is_better"] is True
+    assert abs(line["value"] * line["ms_per_step"] * 1e-3 / line["counters"]["msgs"] - 1) < 1e-2
+    for k in ("parity", "parity_detail", "cpu_baseline", "cpu_port", "trace_stream", "trace_parse",
+              "dump_stream", "msgs_by_type", "type_pass"):
+        assert line[k] is None, k
+    rows = np.load(tmp_path / "results.npy")
+    assert rows.dtype == np.float64 and rows.shape == (4096, 8)
+    assert np.array_equal(np.load(tmp_path / "systems.npy"), np.arange(4096))
+    w = rows.astype(np.uint64)
+    mine6 = np.stack([w[:, 0], w[:, 1], w[:, 2], w[:, 3], w[:, 4] | (w[:, 5] << np.uint64(32)),
+                      w[:, 6] | (w[:, 7] << np.uint64(32))], axis=1)
+    assert np.array_equal(mine6, golden_ensemble("np8_uniform"))
+    c = np.load(tmp_path / "counters.npy").astype(np.uint64)
+    assert len(c) == pydsm.MAX_SLOT + 1
+    c = dict(zip(pydsm.COUNTER_FIELDS, (int(x) for x in c[:, 0] | (c[:, 1] << np.uint64(32)))))
+    assert c["max_rounds"] == line["counters"]["max_rounds"] == int(w[:, 1].max())
+    assert c["msgs"] == line["counters"]["msgs"] == int(w[:, 2].sum())
+    assert hex(c["sum_final_hash"]) == line["sum_final_hash"]
 
 
 @pytest.mark.parametrize("gpus,config,n", [(2, "random", 2048), (4, "evict", 1024)])

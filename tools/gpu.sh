@@ -5,7 +5,7 @@
 #
 #   smoke                       __graft_entry__.smoke()
 #   tests[:K]                   pytest -m gpu (-k K)
-#   bench:CONFIG[:cpu]          bench.py --config CONFIG (--no-cpu unless ":cpu")
+#   bench:CONFIG[:cpu]          bench.py --full --config CONFIG (--no-cpu unless ":cpu")
 #   profile:TAG:CONFIG          tools/profile.sh: kernel trace + SQ / wait / FETCH / WRITE passes
 #   kt:TAG:CONFIG               kernel trace only (rocprofv3 --kernel-trace --stats)
 #   ab:VAR:V1,V2:N:REPS:DIST    tools/ab_open.py (a knob read at dsm_open, in-process A/B)
@@ -30,13 +30,13 @@ for s in "$@"; do
     smoke)   step smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()" ;;
     tests)   step "gpu_tests${a:+_$a}" 900 python -u -m pytest tests -m gpu -x -q --timeout 240 \
                  --timeout-method thread ${a:+-k "$a"} ;;
-    bench)   if [ "$b" = cpu ]; then step "bench_${a}_cpu" 600 python -u bench.py --config "$a"
-             else step "bench_$a" 400 python -u bench.py --config "$a" --no-cpu; fi ;;
+    bench)   if [ "$b" = cpu ]; then step "bench_${a}_cpu" 600 python -u bench.py --full --config "$a"
+             else step "bench_$a" 400 python -u bench.py --full --config "$a" --no-cpu; fi ;;
     profile) bash tools/profile.sh "$a" --config "$b" --steps 3 --warmup 1 --no-types || exit $? ;;
     kt)      mkdir -p "gpurun_out/prof_$a"
              step "kt_$a" 600 rocprofv3 --kernel-trace --stats --output-format csv \
                  -d "gpurun_out/prof_$a/kt" -o kt -- python3 bench.py --no-cpu --no-types --config "$b" \
-                 --steps 3 --warmup 1 ;;
+                 --steps 3 --warmup 1 --full ;;
     ab)      step "ab_${a}_${e:-uniform}" 600 python -u tools/ab_open.py "$a" "$b" "${c:-1048576}" "${d:-2}" "${e:-uniform}" ;;
     abl)     step "abl_${a}" 600 bash tools/ab_libs.sh "$a" "$b" ${c//,/ } ;;
     util)    step "util_$b" 300 env DSM_LIB="$a" python -u tools/lane_util.py "$b" ;;
