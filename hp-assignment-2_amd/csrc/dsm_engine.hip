@@ -84,9 +84,14 @@ struct SimArgs {
     uint32_t *susp;                 /* [sys][word][node] suspended state (susp_words)        */
     uint32_t *susp_list;            /* budget pass: suspended system ids                     */
     unsigned int *susp_count;
-    unsigned int *susp_long;        /* serial-form budget pass: systems of the long class, listed
-                                     * from the list's top down (SER_LONG); the serial pass
-                                     * claims them first                                     */
+    uint32_t *susp_order;           /* order_kernel: the suspended ids by class (2 susp_cap
+                                     * words): the lone systems of the long class from word
+                                     * susp_cap - 1 down, the other lone ones from word 0 up,
+                                     * the multi-node ones from word susp_cap up; nullptr
+                                     * where the kernel is not launched                      */
+    unsigned int *susp_multi;       /* order_kernel: multi-node systems: claimed first       */
+    unsigned int *susp_long;        /* ... lone systems of the long class: claimed next      */
+    unsigned int *susp_short;       /* ... and the other lone systems                        */
     uint32_t susp_cap;              /* the list's capacity (systems in the run)              */
     uint32_t lim_rsh;               /* round limit = 1 << lim_rsh (DSM_MAX_ROUNDS, or
                                      * dsm_set_round_limit): ROUND_LIMIT at that many rounds */
@@ -145,11 +150,6 @@ DEVI uint64_t uni64(uint64_t x) { return ((uint64_t)uni32((uint32_t)(x >> 32)) <
 #ifndef REC_PROBE
 #define REC_PROBE 0         /* probe build (hashes invalid): no node records and no digest pass, to
                                time what the records cost the step */
-#endif
-#ifndef SER_LONG
-#define SER_LONG 0          /* the serial pass claims lone systems with this many instructions left
-                               (and multi-node ones) first, the rest last-suspended first (0: all
-                               last-suspended first) */
 #endif
 #ifndef SIM_TAILPROBE
 #define SIM_TAILPROBE 0     /* budget-pass wave end-time histogram (probe build, results exact;
@@ -1200,22 +1200,11 @@ sim_kernel(const SimArgs *Ap) {
                         for (int k = 0; k < 4; ++k) { q[(7 + k) * NP] = cur[k]; q[(11 + k) * NP] = nxt[k]; }
                     }
                     const uint32_t ins = gsum32<NP>(nd.ip), msgs = gsum32<NP>(nd.nmsg - (FB ? 0u : nd.rh >> 8));
-                    /* the serial pass's claim order, longest first by class: a lone system whose
-                     * lone node has SER_LONG or more instructions left (the one lane with
-                     * any: a group sum), or one still running several nodes, is long */
-                    uint32_t lrem = 0;
-                    if (SER_LONG && LONE)
-                        lrem = gsum32<NP>((lone && (nd.ctl & (C_WAIT | C_DUMPED)) == 0u) ? nd.nins - nd.ip : 0u);
                     uint32_t nlo = 0xFFFFFFFFu, nhi = 0xFFFFFFFFu;
                     if (node == 0) {
                         if (susp) {
-                            if (SER_LONG && LONE && ser_fmt && (!lone || lrem >= (uint32_t)SER_LONG)) {
-                                const uint32_t lp = atomicAdd(Ap->susp_long, 1u);
-                                Ap->susp_list[Ap->susp_cap - 1u - lp] = (uint32_t)sys;
-                            } else {
-                                const uint32_t pos = atomicAdd(Ap->susp_count, 1u);
-                                Ap->susp_list[pos] = (uint32_t)sys;
-                            }
+                            const uint32_t pos = atomicAdd(Ap->susp_count, 1u);
+                            Ap->susp_list[pos] = (uint32_t)sys;
                             atomicAdd(&s_cnt[wv][K_RESUMED], 1ull);
                         } else if (handoff) {
                             const uint32_t pos = atomicAdd(Ap->ovf_count, 1u);
@@ -1474,17 +1463,20 @@ ser_kernel(const SimArgs *Ap) {
     const LdsCol<SER_WAVES> m{s_ser, &s_dum[lane], wv, lane,
                               (GU32 *)(Ap->spill + ((uint64_t)blockIdx.x * (64 * SER_WAVES) + threadIdx.x) * S_SPILL)};
     const LdsTab T{s_tab};
-    /* claim k -> system: the long class first (SER_LONG: listed from the top down by the
-     * budget pass, taken in suspension order), then the rest last-suspended first, as the
-     * lock-step resume (their records the likeliest still in the MALL) */
-    const uint32_t nlong = (SER_LONG && Ap->serfmt && Ap->susp_long) ? *Ap->susp_long : 0u;
-    const uint32_t n = SIM_RFL ? uni32(*Ap->d_n + nlong) : *Ap->d_n + nlong;   /* (sim_kernel's n) */
+    /* claim k -> system: where order_kernel ran, the long class first -- the multi-node
+     * systems, then the lone ones in the order listed (earliest suspended, so longest, first)
+     * -- then the rest last-suspended first, as the lock-step resume (their records the
+     * likeliest still in the MALL); else the budget pass's list, last-suspended first */
+    const bool ordered = Ap->serfmt != 0u && Ap->susp_order != nullptr;
+    const uint32_t nmulti = ordered ? *Ap->susp_multi : 0u;
+    const uint32_t nlong = nmulti + (ordered ? *Ap->susp_long : 0u);
+    const uint32_t n = SIM_RFL ? uni32(*Ap->d_n) : *Ap->d_n;   /* (sim_kernel's n) */
     const uint32_t lcap = Ap->susp_cap;
-    const uint32_t *const list = Ap->list;
+    const uint32_t *const list = ordered ? Ap->susp_order : Ap->list;
     /* global (not flat) accesses: a pending flat operation makes every later wait a full
      * vmcnt(0) lgkmcnt(0), the LDS waits of the macro-step included */
     auto sel = [&](uint32_t k) -> uint32_t {
-        return ((const GU32 *)list)[k < nlong ? lcap - 1u - k : n - 1u - k];
+        return ((const GU32 *)list)[k < nmulti ? lcap + k : k < nlong ? lcap - 1u - (k - nmulti) : n - 1u - k];
     };
 
     const uint32_t stride = Ap->stride, lim_rsh = Ap->lim_rsh, SR = Ap->susp_ring;
@@ -1963,6 +1955,78 @@ ser_kernel(const SimArgs *Ap) {
     }
 }
 
+/* ---- the serial pass's claim order (between the budget pass and ser_kernel) ---------------
+ * Splits the budget pass's list of suspended systems in two classes (dsm_serial.h
+ * ser_long_class).  Of the long one, the lone systems that hold no stale directory entry --
+ * nearly all of them whole-trace systems -- go to the top of a second buffer's first
+ * susp_cap words, downwards, and the multi-node systems to its second susp_cap words; the
+ * rest goes to its bottom, upwards.  ser_kernel claims the multi-node systems first (few,
+ * the slowest in that pass -- one node-action per iteration -- and up to 4.5k iterations
+ * long: claimed in the second generation they were the pass's last 1.5 ms, DESIGN), then
+ * the lone long class, so every whole-trace system starts in the first half of the pass,
+ * then the rest last-suspended first as before.  NP lanes to a system, lane h takes home h: its eight S_MB
+ * words and its S_DS word, and the owners' line and control words, straight from the record;
+ * the group's verdict by ballot.  A workgroup reserves its places with one atomic per class:
+ * the short class's reservations land in dispatch order, so last-suspended-first holds at
+ * workgroup granularity (within a workgroup the list's order is kept).  The grid is sized
+ * from the ensemble; workgroups past the device-resident count exit.  No wave waits for
+ * another.  The original list stays as it is (the lock-step resume and the re-run read it). */
+struct RecCol {                      /* a serial-form record in HBM as a column */
+    const GU32 *sp;
+    DEVI uint32_t ld(uint32_t w) const { return sp[w]; }
+};
+constexpr int ORD_THREADS = 512;      /* 64 systems of 8 nodes to a workgroup */
+template <int NP>
+__global__ void __launch_bounds__(ORD_THREADS) order_kernel(const SimArgs *Ap) {
+    constexpr uint32_t SPB = ORD_THREADS / NP, NW = ORD_THREADS / 64;
+    constexpr uint64_t NPM = (1ull << NP) - 1ull;
+    if (Ap->ffsel && ff_verdict(Ap->scan)) return;
+    const uint32_t n = *Ap->d_n, first = blockIdx.x * SPB;
+    if (first >= n) return;                      /* the whole workgroup */
+    __shared__ uint32_t s_nm[NW], s_nl[NW], s_ns[NW], s_base[3];
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const uint32_t h = lane & (uint32_t)(NP - 1), gbase = lane & ~(uint32_t)(NP - 1);
+    const uint32_t k = first + threadIdx.x / NP;
+    const bool have = k < n;
+    uint32_t sys = 0;
+    bool lone = false, stale = false;
+    if (have) {
+        sys = ((const GU32 *)Ap->list)[k];
+        const RecCol m{(const GU32 *)(Ap->susp + sys * (uint64_t)ssusp_words((int)Ap->susp_ring))};
+        const uint32_t hd = m.sp[121];
+        lone = (hd & 0x100u) != 0u;
+        stale = dsms::ser_stale_home(m, h, hd & 7u);
+    }
+    const bool gstale = ((__ballot(stale) >> gbase) & NPM) != 0ull;
+    const bool lead = have && h == 0u;
+    const uint32_t cls = !lone ? 0u : (gstale ? 2u : 1u);      /* multi-node, lone long, lone short */
+    const uint64_t mb = __ballot(lead && cls == 0u), lb = __ballot(lead && cls == 1u), sb = __ballot(lead && cls == 2u);
+    if (lane == 0) {
+        s_nm[wv] = (uint32_t)__builtin_popcountll(mb);
+        s_nl[wv] = (uint32_t)__builtin_popcountll(lb);
+        s_ns[wv] = (uint32_t)__builtin_popcountll(sb);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t nm = 0, nl = 0, ns = 0;
+        for (uint32_t w = 0; w < NW; ++w) { nm += s_nm[w]; nl += s_nl[w]; ns += s_ns[w]; }
+        s_base[0] = nm ? atomicAdd(Ap->susp_multi, nm) : 0u;
+        s_base[1] = nl ? atomicAdd(Ap->susp_long, nl) : 0u;
+        s_base[2] = ns ? atomicAdd(Ap->susp_short, ns) : 0u;
+    }
+    __syncthreads();
+    if (lead) {
+        const uint64_t below = (1ull << lane) - 1ull;
+        const uint32_t *const cw = cls == 0u ? s_nm : (cls == 1u ? s_nl : s_ns);
+        uint32_t r = s_base[cls] + (uint32_t)__builtin_popcountll((cls == 0u ? mb : (cls == 1u ? lb : sb)) & below);
+        for (uint32_t w = 0; w < wv; ++w) r += cw[w];
+        /* the three counts add up to n <= susp_cap: the lone classes' two ends never meet, and
+         * the multi-node ones stay inside the buffer's second susp_cap words */
+        const uint32_t cap = Ap->susp_cap;
+        Ap->susp_order[cls == 0u ? cap + r : (cls == 1u ? cap - 1u - r : r)] = sys;
+    }
+}
+
 /* ---- aggregate: the golden-aggregate view of per-system results (dsm_aggregate) --------
  * One lane per system (32-B result: two 16-B loads); per-lane sums, then wave sums by
  * shuffles and one device atomic per slot and workgroup.  The result digest is the sum of
@@ -2201,8 +2265,10 @@ static_assert(sizeof(SimArgsPack) % 4 == 0, "SimArgsPack words");
 #define CTRL_FB 256
 #define CTRL_OVF 512
 #define CTRL_RES 1024       /* claim shards of the resume pass */
-#define CTRL_SUSP 1536      /* systems the budget pass suspended (the short class with SER_LONG) */
-#define CTRL_SUSPL 1568     /* ... of the long class (SER_LONG), listed from the top down */
+#define CTRL_SUSP 1536      /* systems the budget pass suspended */
+#define CTRL_SUSPL 1568     /* order_kernel: ... lone, of the long class, listed from the top down */
+#define CTRL_SUSPS 1600     /* order_kernel: ... lone, of the other, listed from the bottom up */
+#define CTRL_SUSPM 1632     /* order_kernel: ... multi-node, listed in the buffer's second half */
 #define CTRL_SCAN 1792      /* ffscan_kernel's sample counts */
 
 /* Two-pass schedule (bench mode: MODE 0, packed traces).  A system's length is unknown until
@@ -2311,7 +2377,7 @@ extern "C" void dsm_close(dsm_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    void *ptrs[] = {c->d_ctrl, c->d_args, c->d_ovf_list, c->d_susp, c->d_susp_list, c->d_spill,
+    void *ptrs[] = {c->d_ctrl, c->d_args, c->d_ovf_list, c->d_susp, c->d_susp_list, c->d_susp_order, c->d_spill,
                     c->d_traces, c->d_counts,
                     c->d_res, c->d_cnt, c->d_recs, c->d_table, c->d_issue, c->d_issue_n};
     for (void *p : ptrs) if (p) (void)hipFree(p);
@@ -2366,7 +2432,6 @@ static const char *build_variant() {
         if (v != def && n < (int)sizeof tag) n += snprintf(tag + n, sizeof tag - n, " %s=%ld", name, v);
     };
     add("SIM_BF", SIM_BF, 0);
-    add("SER_LONG", SER_LONG, 0);
     add("REC_PROBE", REC_PROBE, 0);
     add("SIM_UNI", SIM_UNI, 1);
     add("SIM_RFL", SIM_RFL, 1);
@@ -2436,13 +2501,53 @@ extern "C" int dsm_set_inbox_limit(dsm_ctx *c, uint32_t cap) {
     return DSM_OK;
 }
 
+/* test-only (dsm_internal.h) */
+namespace {
+struct HostRec {
+    const uint32_t *p;
+    uint32_t ld(uint32_t w) const { return p[w]; }
+};
+}
+extern "C" int dsm_debug_order_state(dsm_ctx *c, uint32_t *counts, uint32_t *list, uint32_t *order,
+                                     uint64_t cap, uint64_t sys, uint32_t *rec, uint32_t rec_cap,
+                                     uint32_t *rec_words, int *host_long) {
+    if (!c || !counts) return DSM_E_INVAL;
+    HIPCK(hipSetDevice(c->device));
+    HIPCK(hipStreamSynchronize(c->last_st ? c->last_st : c->stream));
+    const uint64_t n = c->last_n_sys;
+    counts[0] = counts[1] = counts[2] = counts[3] = 0;
+    if (!n || !c->last_blog) return 0;
+    HIPCK(hipMemcpy(&counts[0], c->d_ctrl + CTRL_SUSP, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCK(hipMemcpy(&counts[1], c->d_ctrl + CTRL_SUSPL, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCK(hipMemcpy(&counts[2], c->d_ctrl + CTRL_SUSPS, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCK(hipMemcpy(&counts[3], c->d_ctrl + CTRL_SUSPM, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    counts[1] += counts[3];
+    if ((list && cap < n) || (order && cap < 2 * n)) return DSM_E_INVAL;
+    if (list) HIPCK(hipMemcpy(list, c->d_susp_list, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (order && c->last_order)
+        HIPCK(hipMemcpy(order, c->d_susp_order, 2 * n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (rec_words) *rec_words = c->last_rec_words;
+    if (rec && c->last_rec_words) {
+        if (sys >= n || rec_cap < c->last_rec_words) return DSM_E_INVAL;
+        HIPCK(hipMemcpy(rec, c->d_susp + sys * (uint64_t)c->last_rec_words,
+                        c->last_rec_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (host_long) {
+            const HostRec m{rec};
+            *host_long = (c->cfg.np == 4 ? dsms::ser_long_class<4>(m, rec[121])
+                                         : dsms::ser_long_class<8>(m, rec[121])) ? 1 : 0;
+        }
+    }
+    return c->last_order;
+}
+
 /* Run the transition kernel (+ resume pass, 256-deep re-run of overflowing systems, digest).
  * Everything is enqueued on `st`; the host never waits. */
 static int run_engine(dsm_ctx *c, bool gen, const dsm_gen *g, uint64_t first_sys,
                       const uint16_t *d_traces, const uint32_t *d_counts, uint64_t n_sys,
                       dsm_sys_result *d_results, dsm_counters *d_counters, hipStream_t st) {
     if (n_sys == 0) {    /* nothing launched: the launch info says so */
-        c->last_pair = 0;
+        c->last_pair = c->last_order = 0;
+        c->last_n_sys = 0;
         c->info.grid_blocks = c->info.block_threads = c->info.resume_blocks = 0;
         c->info.budget_log2 = c->info.late_log2 = c->info.budget_rounds = c->info.ff_picked = 0;
         c->info.budget_mode = c->info.resume_mode = -1;
@@ -2493,6 +2598,10 @@ static int run_engine(dsm_ctx *c, bool gen, const dsm_gen *g, uint64_t first_sys
         if ((rc = ensure(&c->d_susp, &c->susp_cap, (size_t)n_sys * sw))) return rc;
         if ((rc = ensure(&c->d_susp_list, &c->susp_list_cap, (size_t)n_sys))) return rc;
     }
+    /* the serial pass's claim order (order_kernel): where ser_kernel is launched and the
+     * budget pass writes the serial form */
+    const bool order = use_ser && (plain_only || pair) && !TRAFFIC_PROBE;
+    if (order && (rc = ensure(&c->d_susp_order, &c->susp_order_cap, (size_t)n_sys * 2))) return rc;
     if ((rc = ensure(&c->d_recs, &c->recs_cap, (size_t)n_sys * np * 8))) return rc;
     /* the serial pass's grid: one workgroup per CU, fewer when the ensemble cannot fill
      * them (at most n_sys systems are suspended); its spill FIFOs: S_SPILL words per lane
@@ -2559,7 +2668,10 @@ static int run_engine(dsm_ctx *c, bool gen, const dsm_gen *g, uint64_t first_sys
     A.susp = c->d_susp;
     A.susp_list = c->d_susp_list;
     A.susp_count = c->d_ctrl + CTRL_SUSP;
+    A.susp_order = order ? c->d_susp_order : nullptr;
+    A.susp_multi = c->d_ctrl + CTRL_SUSPM;
     A.susp_long = c->d_ctrl + CTRL_SUSPL;
+    A.susp_short = c->d_ctrl + CTRL_SUSPS;
     A.susp_cap = (uint32_t)n_sys;
     A.susp_ring = (uint32_t)ring_eff;
     A.spill = c->d_spill;
@@ -2621,6 +2733,11 @@ static int run_engine(dsm_ctx *c, bool gen, const dsm_gen *g, uint64_t first_sys
         if (ser) {
             /* the CAP build keeps per-node inbox counts for an inbox limit below 256 */
             const bool capb = c->inbox_limit < (uint32_t)FB_RING;
+            if (order) {
+                const unsigned ob = (unsigned)((n_sys * (uint64_t)np + ORD_THREADS - 1) / ORD_THREADS);
+                hipLaunchKernelGGL(np == 4 ? order_kernel<4> : order_kernel<8>, dim3(ob), dim3(ORD_THREADS), 0, st, a);
+                HIPCK(hipGetLastError());
+            }
             if (!TRAFFIC_PROBE)
                 hipLaunchKernelGGL(np == 4 ? (capb ? ser_kernel<4, true> : ser_kernel<4, false>)
                                            : (capb ? ser_kernel<8, true> : ser_kernel<8, false>),
@@ -2686,6 +2803,9 @@ static int run_engine(dsm_ctx *c, bool gen, const dsm_gen *g, uint64_t first_sys
     c->last_ser_blocks = ser_blocks;
     c->last_blog = blog;
     c->last_thr_ff = A.thr_ff;
+    c->last_order = order ? 1 : 0;
+    c->last_n_sys = n_sys;
+    c->last_rec_words = A.serfmt ? (uint32_t)ssusp_words(ring_eff) : 0u;
     c->info.lds_bytes_per_block = lds_bytes(ring_eff, FW);
     c->info.late_log2 = (int)A.late_rsh;
     c->info.round_limit_log2 = (int)c->round_limit_log2;

@@ -28,6 +28,8 @@ struct dsm_ctx {
     size_t susp_cap;
     uint32_t *d_susp_list;           /*   and the suspended system ids                       */
     size_t susp_list_cap;
+    uint32_t *d_susp_order;          /*   and the same ids by class (order_kernel)           */
+    size_t susp_order_cap;
     uint32_t *d_spill;               /* serial resume: per-lane inbox spill FIFOs            */
     size_t spill_cap;
     uint16_t *d_traces;
@@ -51,6 +53,11 @@ struct dsm_ctx {
     hipStream_t last_st;
     int last_pair, last_use_ser, last_grid_fast, last_ser_blocks;
     uint32_t last_blog, last_thr_ff;
+    /* the last run, for dsm_debug_order_state: order_kernel launched, the systems, the words of
+     * a serial-form record (0: the budget pass wrote the lock-step form) */
+    int last_order;
+    uint64_t last_n_sys;
+    uint32_t last_rec_words;
     /* two-pass schedule and round limit (dsm_set_budget / dsm_set_round_limit; defaults from
      * DSM_BUDGET_LOG2 / DSM_LATE_LOG2, read once at dsm_open) */
     uint32_t budget_log2, late_log2, round_limit_log2, inbox_limit;
@@ -83,6 +90,23 @@ struct dsm_ctx {
 };
 
 #define HIPCK(x) do { if ((x) != hipSuccess) return DSM_E_DEVICE; } while (0)
+
+/* Test-only view of the serial pass's claim order after a run (not part of the ABI; the
+ * library exports it for pydsm.Engine.order_state).  Waits for the run.  counts[0..3]: systems
+ * the budget pass suspended; systems order_kernel put in the long class, in the other, and the
+ * multi-node ones among the long class (all 0 where it was not launched or exited under the
+ * fast-forward verdict).  list (cap words, may be NULL): the budget pass's list, the run's
+ * system count n of words.  order (cap words, may be NULL): order_kernel's buffer, 2 n words --
+ * the short class in words [0, short), the lone systems of the long class in [n - (long -
+ * multi), n), the multi-node ones in [n, n + multi); left untouched where the kernel was not
+ * launched.  DSM_E_INVAL when cap is too small.  rec (rec_cap words, may be NULL): system
+ * `sys`'s suspended record as the budget pass left it, *rec_words its length (0: not in serial
+ * form), and *host_long the host's verdict on it (dsm_serial.h ser_long_class), meaningful only
+ * for a system on the list.  Returns 1 when order_kernel was launched, 0 when not, < 0 on
+ * error. */
+extern "C" int dsm_debug_order_state(dsm_ctx *c, uint32_t *counts, uint32_t *list, uint32_t *order,
+                                     uint64_t cap, uint64_t sys, uint32_t *rec, uint32_t rec_cap,
+                                     uint32_t *rec_words, int *host_long);
 
 /* dsm_text.hip: called by dsm_close */
 void dsm_text_release(dsm_ctx *c);

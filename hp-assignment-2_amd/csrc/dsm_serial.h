@@ -619,6 +619,51 @@ DSM_HD bool ser_macro(M &m, SReg &r, SCache &cc, F &&fetch, R &&on_dump, P &&sta
     return true;
 }
 
+/* ---- claim order of the resume pass (round 7) ----------------------------------------------
+ * A lone node ends at a dead-end forward (ser_macro's `dead`): a miss on a block whose
+ * directory entry is EM at another node that no longer holds the block in M or E.  Such stale
+ * entries can be read from the suspended state: a lone system with one or more of them runs
+ * ~86 more instructions on average and never 3,000; one with none runs its whole trace in
+ * 88% of cases (DESIGN, ser_kernel).  The resume pass claims the systems without one first.
+ *
+ * ser_stale_home: home h holds a stale entry as seen by the lone node n -- some block b in EM
+ * whose owner o (findOwner :98-105: the lowest bit) is not n and whose line b & 3 at o does
+ * not hold address h << 4 | b in M or E.  Reads home h's eight S_MB words and its S_DS word,
+ * and the owners' S_LA / S_CT words; no branches, every load independent of the others'
+ * values but for the owner's index. */
+template <class M>
+DSM_HD bool ser_stale_home(const M &m, uint32_t h, uint32_t n) {
+    const uint32_t ds = m.ld(S_DS + h);
+    bool stale = false;
+    for (uint32_t p = 0; p < 8u; ++p) {
+        const uint32_t mb = m.ld(S_MB + 8u * h + p);
+        for (uint32_t k = 0; k < 2u; ++k) {
+            const uint32_t b = 2u * p + k, idx = b & 3u;
+            const uint32_t bv = (mb >> (16u * k + 8u)) & 0xFFu;
+            const uint32_t o = s_ctz(bv | 0x100u) & 7u;            /* (bv == 0: no owner) */
+            const uint32_t la = m.ld(S_LA + o), ct = m.ld(S_CT + o);
+            const bool holds = (((la >> (8u * idx)) & 0xFFu) == ((h << 4) | b)) &
+                               (((ct >> (SC_LS + 2u * idx)) & 3u) <= 1u);
+            stale |= (((ds >> (2u * b)) & 3u) == 0u) & (bv != 0u) & (o != n) & !holds;
+        }
+    }
+    return stale;
+}
+/* any home of the system (the host's form; the ordering kernel takes one home per lane) */
+template <int NP, class M>
+DSM_HD bool ser_stale_any(const M &m, uint32_t n) {
+    bool stale = false;
+    for (uint32_t h = 0; h < (uint32_t)NP; ++h) stale |= ser_stale_home(m, h, n);
+    return stale;
+}
+/* the long class: a system that was not lone at suspension (lone_hdr, the serial-form
+ * record's word 121: node | 0x100 when lone; multi-node systems are the slow ones in the
+ * serial pass), or a lone one without a stale entry */
+template <int NP, class M>
+DSM_HD bool ser_long_class(const M &m, uint32_t lone_hdr) {
+    return (lone_hdr & 0x100u) == 0u || !ser_stale_any<NP>(m, lone_hdr & 7u);
+}
+
 /* word i of node n's canonical 64-byte record (dsm_node_state); flags = wait | dumped << 1 */
 template <class M>
 DSM_HD uint32_t ser_rec_word(M &m, uint32_t n, uint32_t flags, int i) {

@@ -141,6 +141,9 @@ def lib():
             "dsm_group_allreduce_counters": (i32, [vp, vp, vp]),
             "dsm_group_allreduce_aggregate": (i32, [vp, vp, vp]),
             "dsm_group_barrier": (i32, [vp, vp]),
+            # test-only (csrc/dsm_internal.h, not in include/dsm.h)
+            "dsm_debug_order_state": (i32, [vp, vp, vp, vp, u64, u64, vp, u32, ctypes.POINTER(u32),
+                                            ctypes.POINTER(i32)]),
         }
         for name, (res, args) in sig.items():
             if os.environ.get("DSM_LIB") and not hasattr(L, name):
@@ -441,6 +444,36 @@ class Engine:
     def set_fast_forward(self, mode):
         """FF_OFF / FF_ON / FF_AUTO (dsm_set_fast_forward): only time depends on it."""
         _check(lib().dsm_set_fast_forward(self.ctx, mode), "dsm_set_fast_forward")
+
+    def order_state(self, n_sys, sys=None):
+        """Test-only: the serial pass's claim order after the last run (of n_sys systems).
+        Without `sys` a dict: `launched` (the ordering kernel was), `suspended`, `long`, `short`
+        and `multi` (counts: the two classes, and the multi-node systems among the long one),
+        `list` (the budget pass's suspended ids) and `order_long` / `order_short` (the two
+        classes as the ordering kernel listed them, in claim order; None where not launched).
+        With `sys`: that system's suspended record (None unless in serial form) and the host
+        classifier's verdict on it."""
+        counts = np.zeros(4, dtype=np.uint32)
+        rw, hl = ctypes.c_uint32(0), ctypes.c_int(-1)
+        if sys is not None:
+            rec = np.zeros(512, dtype=np.uint32)
+            rc = lib().dsm_debug_order_state(self.ctx, _ptr(counts), None, None, 0, sys, _ptr(rec),
+                                             rec.size, ctypes.byref(rw), ctypes.byref(hl))
+            _check(min(rc, 0), "dsm_debug_order_state")
+            return (rec[:rw.value].copy(), bool(hl.value)) if rw.value else (None, None)
+        n = n_sys
+        lst = np.zeros(max(n, 1), dtype=np.uint32)
+        order = np.zeros(max(2 * n, 1), dtype=np.uint32)
+        rc = lib().dsm_debug_order_state(self.ctx, _ptr(counts), _ptr(lst), _ptr(order), order.size,
+                                         0, None, 0, ctypes.byref(rw), ctypes.byref(hl))
+        _check(min(rc, 0), "dsm_debug_order_state")
+        nl, ns, nm = int(counts[1]), int(counts[2]), int(counts[3])
+        d = {"launched": rc == 1, "suspended": int(counts[0]), "long": nl, "short": ns, "multi": nm,
+             "list": lst[:int(counts[0])].copy(), "order_long": None, "order_short": None}
+        if rc == 1:     # claim order: multi-node, lone long (top down), short (last listed first)
+            d["order_long"] = np.concatenate([order[n:n + nm], order[n - (nl - nm):n][::-1]])
+            d["order_short"] = order[:ns][::-1].copy()
+        return d
 
     def launch_info(self):
         """dsm_launch_info of the last run, plus `kernels`: the kernels that did its work
