@@ -29,6 +29,7 @@
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
+#include <utility>
 
 #include <stdint.h>
 #include <stdio.h>
@@ -41,7 +42,7 @@
                                first destination index as a mask select (dsm_table.h) */
 #endif
 #include "dsm_table.h"
-#include "dsm_internal.h"
+#include "dsm_internal.h"   /* and dsm_plan.h: the schedule */
 #include "dsm_gen.h"
 #include "dsm_serial.h"
 
@@ -165,6 +166,7 @@ DEVI uint64_t uni64(uint64_t x) { return ((uint64_t)uni32((uint32_t)(x >> 32)) <
 namespace {
 
 using namespace dsmg;
+using namespace dsmp;    /* MODE bits, traits and predicates: dsm_plan.h */
 
 /* transactionType (assignment.c:20-34) plus the local actions of one round */
 enum : uint32_t {
@@ -184,27 +186,8 @@ enum { K_MSGS = 13, K_INSTRS = 14, K_ROUNDS = 15, K_SYSTEMS = 16, K_STATUS = 17,
        K_SERIT = 33  /* ser_kernel only: its wave iterations (dsm_counters.ser_iterations)  */,
        K_SERPROBE = 34 /* SIM_TAILPROBE builds: the serial pass's wave end-time histogram, 34-39 */ };
 static_assert(sizeof(dsm_counters) == DSM_NCOUNTERS * 8 && K_SERMAC < DSM_NCOUNTERS, "dsm_counters slots");
-constexpr uint32_t RSH_MAX = 22;    /* 1 << 22 == DSM_MAX_ROUNDS */
-static_assert((1u << RSH_MAX) == DSM_MAX_ROUNDS, "DSM_MAX_ROUNDS");
-/* suspended node state: memory/bitVector (8), lines (4), ring (RING), dst, ctl, ip, nins, rh,
- * nmsg, rounds (7), trace chunks cur, nxt (8) */
-constexpr int susp_words(int ring) { return 27 + ring; }
-/* the suspended state in serial form (a budget pass whose resume pass is ser_kernel): one
- * contiguous record per system, so the resume reads it with 16-byte row loads --
- *   [0, 96)    the serial pass's LDS column (dsm_serial.h S_MB .. S_CT), as it will be;
- *   [96, 104)  per node: ring head | count << 8;  [104, 112) instructions in the trace;
- *   [112, 120) messages received;  [120] rounds;
- *   [121]      a lone system: its node | 0x100 (else 0), and [124, 128) / [128, 132) that
- *              node's trace chunk ip >> 3 and the next (the lock-step shift register cur,
- *              instructions ip.. in its low half-words, and nxt), so the serial pass's first
- *              macro-step has its instruction at hand;
- *   [136, 136 + 8 RING)  per node: its queued ring entries, oldest first (count of them). */
-constexpr int SSUSP_HDR = 136;
-constexpr int ssusp_words(int ring) { return SSUSP_HDR + 8 * ring; }
-
 constexpr uint64_t NO_SYS = ~0ull;
 constexpr uint32_t DSM_LINE_INIT = 0xFFu | (3u << 16);   /* address 0xFF, value 0, INVALID */
-constexpr int FB_RING = 256;        /* MSG_BUFFER_SIZE, assignment.c:12 */
 
 /* ---- small bit-field helpers ------------------------------------------------------- */
 DEVI uint32_t get2(uint32_t w, uint32_t i) { return __builtin_amdgcn_ubfe(w, i * 2, 2); }
@@ -394,36 +377,8 @@ DEVI uint32_t gmin(uint32_t x) {
  * predicates, selects): a divergent 17-way switch costs every wave the sum of the taken
  * cases plus their exec-mask bookkeeping.  Only the once-per-node dump, the trace-chunk
  * refill and the per-system finish are real branches.                                   */
-/* MODE bits: the optional parts of a round, compiled in only where asked for */
-enum : int {
-    M_TC = 1,   /* per-type message counters (DSM_F_TYPE_COUNTS): 16-bit fields per node and
-                 * system, added to the wave counters when the system finishes             */
-    M_TR = 2,   /* issue-order trace (DSM_F_ISSUE_TRACE): DEBUG_INSTR order, :595-598      */
-    M_SX = 4,   /* seeded schedule exploration (dsm_set_schedule): a node with an action
-                 * may stall for the round (oracle/dsm_common.h dsm_sched_act)            */
-    M_LIM = 8,  /* run-time round limit / inbox limit (dsm_set_round_limit,
-                 * dsm_set_inbox_limit) for the bench mode, which otherwise has them as
-                 * constants (measured: the two limits as SGPRs cost 1.5-2% in the round)  */
-    M_NOFF = 16,/* the bench mode without the hit-run fast-forward (ffscan_kernel picks)     */
-    M_SERB = 32 /* with M_NOFF: the budget pass of a serial-resumed run (suspend-on-lone, the
-                 * serial-form record); the plain budget pass of a fast-forward-resumed run
-                 * is the kernel without them (measured on C4: 41.1 -> 40.0 ms per run)    */
-};
-
-/* ---- fast-forward verdict --------------------------------------------------------------
- * The hit-run fast-forward (sim_kernel step (0)) pays only where nodes issue long runs of
- * hits; elsewhere its second copy of the round costs the plain round ~3% (C3).  Before the
- * packed path's budget pass, ffscan_kernel replays the first instructions of a sample of
- * node traces through a private 4-line tag model (each line holds the last address that
- * mapped to it, assignment.c:177-184 indexing; no coherence) and counts the instructions
- * that end a run of 8 hits.  Both kernels of the pair are launched; the one this verdict
- * does not pick exits at once.  The choice only moves time: both produce the same results
- * (tests/test_gpu_fastforward.py). */
-constexpr uint32_t SCAN_SYS = 4096, SCAN_INSTR = 256;
-DEVI bool ff_verdict(const uint32_t *scan) {
-    const uint32_t tot = scan[0], run8 = scan[1];
-    return run8 != 0u && (uint64_t)run8 * 16u >= tot;    /* >= 1/16 of the sample */
-}
+/* MODE bits (M_*), the traits of an instantiation and the fast-forward verdict: dsm_plan.h */
+constexpr uint32_t SCAN_INSTR = 256;   /* instructions ffscan_kernel replays per sampled trace */
 template <int NP>
 __global__ void __launch_bounds__(256) ffscan_kernel(const uint16_t *traces, const uint32_t *counts,
                                                      uint32_t stride, uint64_t n_sys, uint32_t *scan,
@@ -465,21 +420,15 @@ __global__ void __launch_bounds__(256) ffscan_kernel(const uint16_t *traces, con
     }
 }
 
-template <int NP, int RING, int WAVES, bool GEN, int MODE, int OCC = 5>
+template <int NP, int RING, int WAVES, bool GEN, int MODE, int OCC = SIM_OCC>
 __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(OCC)))
 sim_kernel(const SimArgs *Ap) {
     constexpr int GPW = 64 / NP;
     constexpr uint32_t NPM = (1u << NP) - 1u;
     constexpr bool FB = (RING == FB_RING);   /* the 256-deep re-run kernel                */
     constexpr bool TC = (MODE & M_TC) != 0, TR = (MODE & M_TR) != 0, SX = (MODE & M_SX) != 0;
-    constexpr bool BUD = (MODE & ~(M_LIM | M_NOFF | M_SERB)) == 0 && !FB && !GEN;   /* two-pass schedule */
-    constexpr bool LIM = FB || (MODE & ~(M_NOFF | M_SERB)) != 0;   /* limits read at run time, else constants */
-    /* hit-run fast-forward: wherever the order of issues inside a round is not observed
-     * (not with the issue-order trace or the seeded stalls of schedule exploration) */
-    constexpr bool FF = (MODE & (M_TR | M_SX | M_NOFF)) == 0;
-    /* suspend-on-lone and the serial-form record: the plain budget kernel of a serial-resumed
-     * run only (M_SERB) */
-    constexpr bool LONE = BUD && !FF && (MODE & M_SERB) != 0;
+    constexpr SimTraits T = sim_traits(MODE, GEN, FB);
+    constexpr bool BUD = T.bud, LIM = T.lim, FF = T.ff, LONE = T.lone;
     constexpr bool UNI = SIM_UNI != 0 && LONE;     /* the per-round end test as one ballot */
     /* paired refills (SIM_R2): the plain kernels, whose ip only ever moves by one issue */
     constexpr bool R2 = SIM_R2 != 0 && BUD && !FF && !GEN;
@@ -489,15 +438,11 @@ sim_kernel(const SimArgs *Ap) {
      * runs stop paying for the probe) */
     constexpr uint32_t FF_PROBE = 4, FF_PROBE_MAX = 512;
 
-    /* one of a fast-forward / plain pair: the kernel the trace scan's verdict did not pick
-     * exits at once (wave-uniform scalar loads; the whole workgroup returns before any
-     * barrier).  A budget pass always runs on the plain one: its rounds are the cold start,
-     * misses rather than hit runs, where the fast-forward step's probes only cost (C4: 48.2
-     * -> 46.4 ms per step) */
-    if (!FB && Ap->ffsel && (ff_verdict(Ap->scan) && !Ap->budget) != FF) return;
-    /* ... and of the two plain budget kernels (SimArgs::split), the one for the resume pass
-     * the verdict picked: M_SERB for the serial one, the other for the fast-forward one */
-    if (!FB && !FF && Ap->split && Ap->budget && ff_verdict(Ap->scan) == LONE) return;
+    /* the kernel of a pair, and of the two plain budget kernels, that the trace scan's verdict
+     * did not pick exits at once (dsm_plan.h; wave-uniform scalar loads: the whole workgroup
+     * returns before any barrier) */
+    if (DSM_SIM_EXITS_PAIR(FB, FF, Ap)) return;
+    if (DSM_SIM_EXITS_SPLIT(FB, FF, LONE, Ap)) return;
 
     __shared__ uint32_t s_mb[WAVES][8][64];          /* 2 x (mem | bv << 8) per dword */
     __shared__ uint32_t s_line[WAVES][4][64];        /* cache lines: addr | value << 8 | state << 16 */
@@ -535,20 +480,14 @@ sim_kernel(const SimArgs *Ap) {
     /* an inbox beyond ocap ends the round's system: the fast kernel hands it to the 256-deep
      * re-run (its ring holds RING), which reports RING_OVERFLOW beyond the inbox limit */
     const uint32_t ocap = FB || (LIM && Ap->icap < (uint32_t)RING) ? Ap->icap : (uint32_t)RING;
-    const uint32_t rsh0 = BUD && Ap->rsh < lim_rsh ? Ap->rsh : lim_rsh;
     /* the round test's threshold: the round limit, or the budget pass's budget (wave-uniform) */
-    uint32_t thr = 1u << rsh0;
-    if (BUD && Ap->budget && Ap->thr_ff && (FF || (Ap->ffsel && ffv)) &&
-        Ap->thr_ff < (1u << lim_rsh))
-        thr = Ap->thr_ff;          /* a fast-forward workload's budget (thr_ff, run_engine) */
+    uint32_t thr = sim_threshold(T, Ap, lim_rsh, ffv);
     const uint32_t late_rsh = BUD ? Ap->late_rsh : 0u;
     const bool budget = BUD && Ap->budget != 0, resume = BUD && Ap->resume != 0;
-    /* suspend-on-lone: the budget pass of a run whose resume pass is the serial one (not the
-     * fast-forward pair's pick) */
-    const uint32_t lone_on = (LONE && budget && !(Ap->ffsel && ffv)) ? Ap->lone : 0u;
+    const uint32_t lone_on = sim_lone_on(T, Ap, ffv);   /* suspend-on-lone: rounds between checks */
     uint32_t lcd = lone_on;             /* rounds to the next check (uniform) */
     const uint32_t lone_min = Ap->lone_min;   /* not before this many rounds */
-    const bool ser_fmt = LONE && budget && Ap->serfmt && !(Ap->ffsel && ffv);
+    const bool ser_fmt = sim_ser_fmt(T, Ap, ffv);
     /* systems started statically (one per slot), the rest claimed from the shard counters.
      * The resume pass is launched at the full grid and sizes itself here from the device-
      * resident count of suspended systems (no host round trip): it uses the fewest slots
@@ -1389,7 +1328,7 @@ sim_kernel(const SimArgs *Ap) {
 #endif
 /* SER_RF: iterations between trace refills; SER_GE: the one-action step (ser_step) runs in
  * every SER_GE-th iteration (the macro-step in every one) */
-constexpr int SER_WAVES = 6, SER_RF = SER_RF_DEF, SER_GE = SER_GE_DEF;
+constexpr int SER_RF = SER_RF_DEF, SER_GE = SER_GE_DEF;
 constexpr int SER_MACRO = SER_MACRO_DEF;   /* lone-node macro-steps per iteration */
 /* SER_PROBE builds (diagnostics, never the default): per-wave event counts of the serial pass
  * in the counter slots the pass leaves unused (msgs_by_type 0-4): iterations, iterations with
@@ -1446,7 +1385,7 @@ ser_kernel(const SimArgs *Ap) {
     constexpr uint32_t NPM = (1u << NP) - 1u;
     /* one of a fast-forward / serial pair: the fast-forward lock-step resume takes the run
      * when the trace scan picked fast-forward */
-    if (Ap->ffsel && ff_verdict(Ap->scan)) return;
+    if (DSM_SER_EXITS(Ap)) return;
 
     __shared__ uint32_t s_ser[SER_WAVES][S_WORDS][64];
     __shared__ uint2 s_tab[DT_TABLE_WORDS / 2];
@@ -1975,12 +1914,11 @@ struct RecCol {                      /* a serial-form record in HBM as a column 
     const GU32 *sp;
     DEVI uint32_t ld(uint32_t w) const { return sp[w]; }
 };
-constexpr int ORD_THREADS = 512;      /* 64 systems of 8 nodes to a workgroup */
 template <int NP>
 __global__ void __launch_bounds__(ORD_THREADS) order_kernel(const SimArgs *Ap) {
     constexpr uint32_t SPB = ORD_THREADS / NP, NW = ORD_THREADS / 64;
     constexpr uint64_t NPM = (1ull << NP) - 1ull;
-    if (Ap->ffsel && ff_verdict(Ap->scan)) return;
+    if (DSM_SER_EXITS(Ap)) return;
     const uint32_t n = *Ap->d_n, first = blockIdx.x * SPB;
     if (first >= n) return;                      /* the whole workgroup */
     __shared__ uint32_t s_nm[NW], s_nl[NW], s_ns[NW], s_base[3];
@@ -2183,44 +2121,35 @@ typedef void (*sim_fn)(const SimArgs *);
  * workgroup in LDS; at ring 12 a wave needs ~6 KB of LDS and the kernel fits 5 waves per
  * SIMD (96 VGPRs), so 4-wave groups (5 per CU = 20 waves, 146 KB LDS) fill the CU where
  * 8-wave groups stop at 2 per CU (16 waves; measured 0.6% slower, profiles/README.md). */
-constexpr int FW = 4;
+constexpr int FW = SIM_WAVES;
 
+/* the fast kernel of (ring, mode), nullptr where the dispatch has none: the set is
+ * dsm_plan.h's (SIM_MODES, sim_instantiated), and `ring` the plan's (plan_ring) */
+template <int NP, bool GEN, int MODE, int RING>
+sim_fn fast_ring() {
+    if constexpr (sim_instantiated(GEN, RING, MODE)) return sim_kernel<NP, RING, FW, GEN, MODE>;
+    else return nullptr;
+}
 template <int NP, bool GEN, int MODE>
 sim_fn fast_mode(int ring) {
-    /* the inbox depth only moves time, never results: every depth for the bench mode, and
-     * the overflow-prone depth 4 (which exercises the 256-deep re-run) for the others */
     switch (ring) {
-    case 4: return sim_kernel<NP, 4, FW, GEN, MODE>;
-    case 8: if ((MODE & ~(M_NOFF | M_SERB)) == 0) return sim_kernel<NP, 8, FW, GEN, MODE & (M_NOFF | M_SERB)>; break;
-    case 16: if ((MODE & ~(M_NOFF | M_SERB)) == 0) return sim_kernel<NP, 16, FW, GEN, MODE & (M_NOFF | M_SERB)>; break;
-    default: break;
+    case 4: return fast_ring<NP, GEN, MODE, 4>();
+    case 8: return fast_ring<NP, GEN, MODE, 8>();
+    case 16: return fast_ring<NP, GEN, MODE, 16>();
+    case 12: return fast_ring<NP, GEN, MODE, 12>();
+    default: return nullptr;
     }
-    return sim_kernel<NP, 12, FW, GEN, MODE>;
 }
-template <int NP, bool GEN>
-sim_fn fast_np_gen(int ring, int mode) {
-    switch (mode) {
-    case 1: return fast_mode<NP, GEN, 1>(ring);
-    case 2: return fast_mode<NP, GEN, 2>(ring);
-    case 3: return fast_mode<NP, GEN, 3>(ring);
-    case 4: return fast_mode<NP, GEN, 4>(ring);
-    case 5: return fast_mode<NP, GEN, 5>(ring);
-    case 6: return fast_mode<NP, GEN, 6>(ring);
-    case 7: return fast_mode<NP, GEN, 7>(ring);
-    case M_LIM: return fast_mode<NP, GEN, M_LIM>(ring);
-    case M_NOFF:                        /* packed path only (ffscan_kernel reads traces); the
-                                         * fused generator has no plain kernel: mode 0 */
-        if constexpr (!GEN) return fast_mode<NP, GEN, M_NOFF>(ring);
-        else return fast_mode<NP, GEN, 0>(ring);
-    case M_NOFF | M_SERB:
-        if constexpr (!GEN) return fast_mode<NP, GEN, M_NOFF | M_SERB>(ring);
-        else return fast_mode<NP, GEN, 0>(ring);
-    default: return fast_mode<NP, GEN, 0>(ring);
-    }
+template <int NP, bool GEN, int... I>
+sim_fn fast_np_gen(int ring, int mode, std::integer_sequence<int, I...>) {
+    sim_fn f = nullptr;
+    ((mode == SIM_MODES[I] ? (void)(f = fast_mode<NP, GEN, SIM_MODES[I]>(ring)) : (void)0), ...);
+    return f;
 }
 sim_fn pick_fast(int np, int ring, bool gen, int mode) {
-    if (np == 4) return gen ? fast_np_gen<4, true>(ring, mode) : fast_np_gen<4, false>(ring, mode);
-    return gen ? fast_np_gen<8, true>(ring, mode) : fast_np_gen<8, false>(ring, mode);
+    constexpr std::make_integer_sequence<int, SIM_NMODES> modes{};
+    if (np == 4) return gen ? fast_np_gen<4, true>(ring, mode, modes) : fast_np_gen<4, false>(ring, mode, modes);
+    return gen ? fast_np_gen<8, true>(ring, mode, modes) : fast_np_gen<8, false>(ring, mode, modes);
 }
 template <int NP, bool GEN>
 sim_fn fb_np_gen(int mode) {
@@ -2325,9 +2254,9 @@ extern "C" int dsm_open(int device, const dsm_config *cfg, dsm_ctx **out) {
     if (c->budget_log2 >= RSH_MAX) c->budget_log2 = 0;
     /* the fast-forward kernel's budget in rounds (0: the plain budget); DSM_FF_BUDGET_LOG2,
      * if set, gives it as a power of two */
-    c->ff_budget_log2 = env_u32("DSM_FF_BUDGET_LOG2", 0);
-    if (c->ff_budget_log2 >= RSH_MAX) c->ff_budget_log2 = 0;
-    c->ff_budget_rounds = getenv("DSM_FF_BUDGET_LOG2") ? (c->ff_budget_log2 ? 1u << c->ff_budget_log2 : 0u)
+    uint32_t ffb_log2 = env_u32("DSM_FF_BUDGET_LOG2", 0);
+    if (ffb_log2 >= RSH_MAX) ffb_log2 = 0;
+    c->ff_budget_rounds = getenv("DSM_FF_BUDGET_LOG2") ? (ffb_log2 ? 1u << ffb_log2 : 0u)
                                                        : env_u32("DSM_FF_BUDGET_ROUNDS", 448);
     if (c->ff_budget_rounds >= (1u << RSH_MAX)) c->ff_budget_rounds = 0;
     /* the late budget (a shorter budget once a wave finds no new system) is off: with
@@ -2392,32 +2321,19 @@ extern "C" void dsm_close(dsm_ctx *c) {
 
 extern "C" int dsm_launch_info_get(dsm_ctx *c, dsm_launch_info *info) {
     if (!c || !info) return DSM_E_INVAL;
-    if (c->last_pair) {
-        /* the trace scan chose the pair's kernel on the device: wait for the run, read the
-         * verdict (ff_verdict) and report the passes that actually ran (one pass at budget
-         * 0: only the kernel it picked) */
+    if (c->plan.pair && c->last_verdict < 0) {
+        /* the trace scan chose the pair's kernels on the device: wait for the run and read
+         * what it found */
         uint32_t scan[2] = {0, 0};
         HIPCK(hipSetDevice(c->device));
         HIPCK(hipStreamSynchronize(c->last_st));
         HIPCK(hipMemcpy(scan, c->d_ctrl + CTRL_SCAN, sizeof scan, hipMemcpyDeviceToHost));
-        const bool ff = scan[1] != 0u && (uint64_t)scan[1] * 16u >= scan[0];
-        c->info.ff_picked = ff ? 1 : 0;
-        if (c->last_blog) {
-            c->info.resume_form = ff ? DSM_RESUME_FASTFORWARD
-                                     : (c->last_use_ser ? DSM_RESUME_SERIAL : DSM_RESUME_LOCKSTEP);
-            c->info.resume_blocks = (ff || !c->last_use_ser) ? c->last_grid_fast : c->last_ser_blocks;
-            c->info.budget_rounds = (int)((ff && c->last_thr_ff) ? c->last_thr_ff : 1u << c->last_blog);
-            /* the budget pass runs on a plain kernel: with the serial resume, the M_SERB one
-             * unless the verdict picked the fast-forward resume (SimArgs::split) */
-            c->info.budget_mode = (!ff && c->last_use_ser) ? (M_NOFF | M_SERB) : M_NOFF;
-            c->info.resume_mode = ff ? 0 : (c->last_use_ser ? -1 : M_NOFF);
-        } else {
-            c->info.budget_mode = ff ? 0 : M_NOFF;
-            c->info.resume_mode = -1;
-        }
-        c->last_pair = 0;
+        c->last_verdict = ff_verdict(scan) ? 1 : 0;
     }
-    *info = c->info;
+    *info = plan_info(c->plan, c->last_verdict > 0);
+    info->lds_bytes_per_block = c->plan.n_launch ? lds_bytes(c->plan.ring_eff, FW) : 0;
+    info->fmt_tile = c->fmt_tile;
+    info->parse_bpl = c->parse_bpl;
     return DSM_OK;
 }
 
@@ -2514,9 +2430,10 @@ extern "C" int dsm_debug_order_state(dsm_ctx *c, uint32_t *counts, uint32_t *lis
     if (!c || !counts) return DSM_E_INVAL;
     HIPCK(hipSetDevice(c->device));
     HIPCK(hipStreamSynchronize(c->last_st ? c->last_st : c->stream));
-    const uint64_t n = c->last_n_sys;
+    const Plan &pl = c->plan;
+    const uint64_t n = pl.in.n_sys;
     counts[0] = counts[1] = counts[2] = counts[3] = 0;
-    if (!n || !c->last_blog) return 0;
+    if (!n || !pl.blog) return 0;
     HIPCK(hipMemcpy(&counts[0], c->d_ctrl + CTRL_SUSP, sizeof(uint32_t), hipMemcpyDeviceToHost));
     HIPCK(hipMemcpy(&counts[1], c->d_ctrl + CTRL_SUSPL, sizeof(uint32_t), hipMemcpyDeviceToHost));
     HIPCK(hipMemcpy(&counts[2], c->d_ctrl + CTRL_SUSPS, sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -2524,91 +2441,78 @@ extern "C" int dsm_debug_order_state(dsm_ctx *c, uint32_t *counts, uint32_t *lis
     counts[1] += counts[3];
     if ((list && cap < n) || (order && cap < 2 * n)) return DSM_E_INVAL;
     if (list) HIPCK(hipMemcpy(list, c->d_susp_list, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (order && c->last_order)
-        HIPCK(hipMemcpy(order, c->d_susp_order, 2 * n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (rec_words) *rec_words = c->last_rec_words;
-    if (rec && c->last_rec_words) {
-        if (sys >= n || rec_cap < c->last_rec_words) return DSM_E_INVAL;
-        HIPCK(hipMemcpy(rec, c->d_susp + sys * (uint64_t)c->last_rec_words,
-                        c->last_rec_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (order && pl.order)
+        HIPCK(hipMemcpy(order, c->d_susp_order, pl.order_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (rec_words) *rec_words = pl.rec_words;
+    if (rec && pl.rec_words) {
+        if (sys >= n || rec_cap < pl.rec_words) return DSM_E_INVAL;
+        HIPCK(hipMemcpy(rec, c->d_susp + sys * (uint64_t)pl.rec_words,
+                        pl.rec_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
         if (host_long) {
             const HostRec m{rec};
             *host_long = (c->cfg.np == 4 ? dsms::ser_long_class<4>(m, rec[121])
                                          : dsms::ser_long_class<8>(m, rec[121])) ? 1 : 0;
         }
     }
-    return c->last_order;
+    return pl.order ? 1 : 0;
 }
 
-/* Run the transition kernel (+ resume pass, 256-deep re-run of overflowing systems, digest).
- * Everything is enqueued on `st`; the host never waits. */
+/* the schedule's scalar fields of an argument block, from the plan */
+static void put_sched(SimArgs &a, const PlanArgs &s) {
+    a.rsh = s.rsh; a.budget = s.budget; a.resume = s.resume; a.ffsel = s.ffsel;
+    a.late_rsh = s.late_rsh; a.thr_ff = s.thr_ff; a.lone = s.lone; a.lone_min = s.lone_min;
+    a.serfmt = s.serfmt; a.split = s.split; a.susp_ring = s.susp_ring; a.lim_rsh = s.lim_rsh;
+    a.icap = s.icap;
+}
+
+/* Run the transition kernel (+ resume pass, 256-deep re-run of overflowing systems, digest):
+ * dsm_plan.h decides the launches, this executes them.  Everything is enqueued on `st`; the
+ * host never waits. */
 static int run_engine(dsm_ctx *c, bool gen, const dsm_gen *g, uint64_t first_sys,
                       const uint16_t *d_traces, const uint32_t *d_counts, uint64_t n_sys,
                       dsm_sys_result *d_results, dsm_counters *d_counters, hipStream_t st) {
+    if (n_sys > 0xFFFFFFFFull) return DSM_E_INVAL;
+    const int np = c->cfg.np;
+    const bool tr = (c->cfg.flags & DSM_F_ISSUE_TRACE) != 0;
+    PlanIn in{};
+    in.np = np; in.ring = c->ring; in.gen = gen; in.n_sys = n_sys; in.cus = c->cus;
+    in.tc = (c->cfg.flags & DSM_F_TYPE_COUNTS) != 0; in.tr = tr; in.sx = c->sched_thresh < DSM_SCHED_LOCKSTEP;
+    in.round_limit_log2 = c->round_limit_log2; in.inbox_limit = c->inbox_limit;
+    in.ff_mode = c->ff_mode; in.serial = c->serial; in.ff_budget_rounds = c->ff_budget_rounds;
+    in.budget_log2 = c->budget_log2; in.late_log2 = c->late_log2;
+    in.lone_rounds = c->lone_rounds; in.lone_min = c->lone_min;
+    in.traffic_probe = TRAFFIC_PROBE;
+    Plan p = plan_build(in);
     if (n_sys == 0) {    /* nothing launched: the launch info says so */
-        c->last_pair = c->last_order = 0;
-        c->last_n_sys = 0;
-        c->info.grid_blocks = c->info.block_threads = c->info.resume_blocks = 0;
-        c->info.budget_log2 = c->info.late_log2 = c->info.budget_rounds = c->info.ff_picked = 0;
-        c->info.budget_mode = c->info.resume_mode = -1;
-        c->info.resume_form = DSM_RESUME_NONE;
+        c->plan = p;
         return DSM_OK;
     }
-    if (n_sys > 0xFFFFFFFFull) return DSM_E_INVAL;
     HIPCK(hipSetDevice(c->device));
-    const int np = c->cfg.np, gpw = 64 / np;
-    const bool tr = (c->cfg.flags & DSM_F_ISSUE_TRACE) != 0;
-    int mode = ((c->cfg.flags & DSM_F_TYPE_COUNTS) ? M_TC : 0) | (tr ? M_TR : 0) |
-               (c->sched_thresh < DSM_SCHED_LOCKSTEP ? M_SX : 0);
-    /* the bench mode with a round limit or an inbox limit below the fast ring */
-    if (mode == 0 && (c->round_limit_log2 != RSH_MAX || c->inbox_limit < (uint32_t)c->ring)) mode = M_LIM;
-    /* the bench mode on the packed path: the hit-run fast-forward per dsm_set_fast_forward;
-     * in auto, a pair of launches per pass, picked on the device by ffscan_kernel */
-    const bool plain_only = mode == 0 && !gen && c->ff_mode == DSM_FF_OFF;
-    const bool pair = mode == 0 && !gen && c->ff_mode == DSM_FF_AUTO;
-    /* two-pass schedule on the packed path in bench mode */
-    const uint32_t blog = ((mode & ~M_LIM) == 0 && !gen) ? c->budget_log2 : 0u;
-    /* the resume pass in serial form (ser_kernel) unless fast-forward is forced; with the
-     * fast-forward pair, the trace scan's verdict picks between it and the fast-forward
-     * lock-step resume */
-    const bool use_ser = blog && c->serial && c->ff_mode != DSM_FF_ON;
-    /* plain budget kernels: M_SERB (suspend-on-lone, serial-form record) where the serial
-     * pass resumes; the pair launches both and the verdict keeps one (SimArgs::split) */
-    const int plain_mode = use_ser ? (M_NOFF | M_SERB) : M_NOFF;
-    const sim_fn fast = pick_fast(np, c->ring, gen, plain_only ? plain_mode : mode), fb = pick_fallback(np, gen, mode);
-    const sim_fn fast_nf = pair ? pick_fast(np, c->ring, gen, M_NOFF) : nullptr;
-    const sim_fn fast_serb = pair && use_ser ? pick_fast(np, c->ring, gen, M_NOFF | M_SERB) : nullptr;
+    /* the sim_kernel of each launch that has one; the first sizes the grid */
+    sim_fn sim[PLAN_MAX_LAUNCHES] = {}, fast = nullptr;
+    for (int i = 0; i < p.n_launch; ++i) {
+        if (p.launch[i].kernel != PK_SIM) continue;
+        if (!(sim[i] = pick_fast(np, p.ring_eff, gen, p.launch[i].mode))) return DSM_E_INVAL;
+        if (!fast) fast = sim[i];
+    }
+    const sim_fn fb = pick_fallback(np, gen, p.mode);
     int nb_fast = 0, nb_fb = 0;
     HIPCK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb_fast, (const void *)fast, 64 * FW, 0));
     HIPCK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb_fb, (const void *)fb, 64, 0));
     if (nb_fast < 1 || nb_fb < 1) return DSM_E_DEVICE;
-    uint64_t want = (n_sys + (uint64_t)(FW * gpw) - 1) / (uint64_t)(FW * gpw);
-    const int grid_max = nb_fast * c->cus;
-    int grid_fast = (int)((uint64_t)grid_max < want ? (uint64_t)grid_max : want);
-    int grid_fb = nb_fb * c->cus;
-    if (grid_fb > 1024) grid_fb = 1024;
-    uint64_t dblocks = (n_sys * np + 255) / 256;
-    if (dblocks > (uint64_t)c->cus * 8) dblocks = (uint64_t)c->cus * 8;
+    plan_grids(p, nb_fast, nb_fb);
+
     int rc;
     if ((rc = ensure(&c->d_ovf_list, &c->ovf_cap, (size_t)n_sys))) return rc;
-    const int ring_eff = (mode && c->ring != 4) ? 12 : c->ring;   /* fast_mode's choice */
-    if (blog) {
-        const size_t sw = (size_t)np * susp_words(ring_eff) > (size_t)ssusp_words(ring_eff)
-                              ? (size_t)np * susp_words(ring_eff) : (size_t)ssusp_words(ring_eff);
-        if ((rc = ensure(&c->d_susp, &c->susp_cap, (size_t)n_sys * sw))) return rc;
+    if (p.blog) {
+        if ((rc = ensure(&c->d_susp, &c->susp_cap, (size_t)n_sys * p.susp_words))) return rc;
         if ((rc = ensure(&c->d_susp_list, &c->susp_list_cap, (size_t)n_sys))) return rc;
     }
-    /* the serial pass's claim order (order_kernel): where ser_kernel is launched and the
-     * budget pass writes the serial form */
-    const bool order = use_ser && (plain_only || pair) && !TRAFFIC_PROBE;
-    if (order && (rc = ensure(&c->d_susp_order, &c->susp_order_cap, (size_t)n_sys * 2))) return rc;
+    if (p.order && (rc = ensure(&c->d_susp_order, &c->susp_order_cap, (size_t)p.order_words))) return rc;
     if ((rc = ensure(&c->d_recs, &c->recs_cap, (size_t)n_sys * np * 8))) return rc;
-    /* the serial pass's grid: one workgroup per CU, fewer when the ensemble cannot fill
-     * them (at most n_sys systems are suspended); its spill FIFOs: S_SPILL words per lane
-     * (96 MiB on 256 CUs, 384 KiB per workgroup) */
-    const int ser_blocks = (int)((uint64_t)c->cus < (n_sys + 64 * SER_WAVES - 1) / (64 * SER_WAVES)
-                                     ? (uint64_t)c->cus : (n_sys + 64 * SER_WAVES - 1) / (64 * SER_WAVES));
-    if (use_ser && (rc = ensure(&c->d_spill, &c->spill_cap, (size_t)ser_blocks * 64 * SER_WAVES * dsms::S_SPILL))) return rc;
+    /* the serial pass's spill FIFOs: S_SPILL words per lane (96 MiB on 256 CUs, 384 KiB per
+     * workgroup) */
+    if (p.use_ser && (rc = ensure(&c->d_spill, &c->spill_cap, (size_t)p.spill_lanes * dsms::S_SPILL))) return rc;
     if (!d_results) {   /* the engine needs the per-system header even if the caller does not */
         if ((rc = ensure(&c->d_res, &c->res_cap, (size_t)n_sys + 1))) return rc;
         d_results = c->d_res;
@@ -2625,7 +2529,7 @@ static int run_engine(dsm_ctx *c, bool gen, const dsm_gen *g, uint64_t first_sys
 
     SimArgsPack pk;
     memset(&pk, 0, sizeof pk);
-    SimArgs &A = pk.a[0];
+    SimArgs &A = pk.a[ARGS_FAST];
     A.traces = d_traces;
     A.counts = d_counts;
     A.stride = c->cfg.max_instr;
@@ -2643,37 +2547,14 @@ static int run_engine(dsm_ctx *c, bool gen, const dsm_gen *g, uint64_t first_sys
     A.table = c->d_table;
     A.sched_seed = c->sched_seed;
     A.sched_thresh = c->sched_thresh;
-    A.lim_rsh = c->round_limit_log2;
-    A.icap = c->inbox_limit;
-    A.rsh = blog ? blog : RSH_MAX;
-    /* the fast-forward kernel's own budget (thr_ff rounds).  A short one suspends every
-     * system of a hit-run workload at the same round: each pass then holds the systems of a
-     * wave in the same phase, so the groups enter and leave fast-forward mode together and
-     * the normal round is skipped more often (measured on C4, budget 256 / 320 / 384 / 416 /
-     * 512 / 640 / 1024 / 2048 rounds: 50.9 / 48.7 / 48.3 / 48.4 / 49.0 / 50.0 / 53.4 /
-     * 57.7 ms; round 4, with the long runs: 320 / 384 / 416 / 448 / 480 / 512 / 640: 34.8 /
-     * 32.2 / 31.3 / 31.0 / 30.9 / 31.2 / 33.9 ms).  Bench mode only: with a round or inbox limit (M_LIM) the kernel always has
-     * the fast-forward step and takes the plain budget. */
-    A.budget = blog ? 1u : 0u;
-    A.thr_ff = (mode == 0) ? c->ff_budget_rounds : 0u;
-    A.lone = (use_ser && (plain_only || pair)) ? c->lone_rounds : 0u;   /* serial resume only */
-    A.lone_min = c->lone_min;
-
-    /* the serial-form record and suspend-on-lone are compiled into the plain budget kernel
-     * only (sim_kernel LONE): runs whose budget pass takes it, the pair's plain half or the
-     * plain-only bench mode; with limits (M_LIM) the budget pass writes the lock-step form */
-    A.serfmt = (use_ser && (plain_only || pair)) ? 1u : 0u;
-    A.split = (pair && use_ser) ? 1u : 0u;
-    A.late_rsh = (blog && c->late_log2 > 0 && c->late_log2 < blog) ? c->late_log2 : 0u;
     A.susp = c->d_susp;
     A.susp_list = c->d_susp_list;
     A.susp_count = c->d_ctrl + CTRL_SUSP;
-    A.susp_order = order ? c->d_susp_order : nullptr;
+    A.susp_order = p.order ? c->d_susp_order : nullptr;
     A.susp_multi = c->d_ctrl + CTRL_SUSPM;
     A.susp_long = c->d_ctrl + CTRL_SUSPL;
     A.susp_short = c->d_ctrl + CTRL_SUSPS;
     A.susp_cap = (uint32_t)n_sys;
-    A.susp_ring = (uint32_t)ring_eff;
     A.spill = c->d_spill;
     if (tr) {
         A.issue = c->d_issue;
@@ -2681,136 +2562,68 @@ static int run_engine(dsm_ctx *c, bool gen, const dsm_gen *g, uint64_t first_sys
         A.issue_cap = (uint32_t)((size_t)np * c->cfg.max_instr);
         c->issue_sys = n_sys;
     }
-    SimArgs &B = pk.a[1];           /* 256-deep re-run of the overflow list */
+    SimArgs &B = pk.a[ARGS_RERUN];    /* 256-deep re-run of the overflow list */
     B = A;
     B.d_n = c->d_ctrl + CTRL_OVF;
     B.list = c->d_ovf_list;
     B.claim = c->d_ctrl + CTRL_FB;
     B.ovf_list = nullptr;
     B.ovf_count = nullptr;
-    B.rsh = RSH_MAX;
-    B.budget = 0;
-    SimArgs &C = pk.a[2];           /* resume pass: the suspended list, count on the device */
+    SimArgs &C = pk.a[ARGS_RESUME];   /* resume pass: the suspended list, count on the device */
     C = A;
     C.n_sys = 0;
     C.d_n = c->d_ctrl + CTRL_SUSP;
     C.list = c->d_susp_list;
     C.claim = c->d_ctrl + CTRL_RES;
-    C.rsh = RSH_MAX;
-    C.budget = 0;
-    C.late_rsh = 0;
-    C.resume = 1;
     A.scan = C.scan = c->d_ctrl + CTRL_SCAN;
-    A.ffsel = C.ffsel = pair ? 1u : 0u;
+    for (int i = 0; i < 3; ++i) put_sched(pk.a[i], p.args[i]);
     hipLaunchKernelGGL(args_kernel, dim3(1), dim3(64), 0, st, pk, c->d_args);
     HIPCK(hipGetLastError());
 
+    /* DSM_F_TIMING: events around the transition launches, up to the re-run */
     const bool timed = (c->cfg.flags & DSM_F_TIMING) != 0;
     const int slot = (int)(c->runs_timed % DSM_TIMING_RING);
     if (timed) HIPCK(hipEventRecord(c->tev0[slot], st));
-    if (pair) {
-        const uint32_t S = n_sys < SCAN_SYS ? (uint32_t)n_sys : SCAN_SYS;
-        const unsigned sb = (unsigned)((S * (uint32_t)np + 255u) / 256u);
-        if (np == 4)
-            hipLaunchKernelGGL(ffscan_kernel<4>, dim3(sb), dim3(256), 0, st, d_traces, d_counts,
-                               (uint32_t)c->cfg.max_instr, n_sys, c->d_ctrl + CTRL_SCAN,
-                               reinterpret_cast<unsigned long long *>(d_counters));
-        else
-            hipLaunchKernelGGL(ffscan_kernel<8>, dim3(sb), dim3(256), 0, st, d_traces, d_counts,
-                               (uint32_t)c->cfg.max_instr, n_sys, c->d_ctrl + CTRL_SCAN,
-                               reinterpret_cast<unsigned long long *>(d_counters));
+    unsigned long long *dcnt = reinterpret_cast<unsigned long long *>(d_counters);
+    for (int i = 0; i < p.n_launch; ++i) {
+        const PlanLaunch &L = p.launch[i];
+        const SimArgs *a = (const SimArgs *)(c->d_args + L.args);
+        switch (L.kernel) {
+        case PK_SCAN:
+            hipLaunchKernelGGL(np == 4 ? ffscan_kernel<4> : ffscan_kernel<8>, dim3(p.scan_blocks), dim3(256),
+                               0, st, d_traces, d_counts, (uint32_t)c->cfg.max_instr, n_sys,
+                               c->d_ctrl + CTRL_SCAN, dcnt);
+            break;
+        case PK_SIM:
+            hipLaunchKernelGGL(sim[i], dim3(p.grid_fast), dim3(64 * FW), 0, st, a);
+            break;
+        case PK_ORDER:
+            hipLaunchKernelGGL(np == 4 ? order_kernel<4> : order_kernel<8>, dim3(p.order_blocks),
+                               dim3(ORD_THREADS), 0, st, a);
+            break;
+        case PK_SER:
+            hipLaunchKernelGGL(np == 4 ? (L.mode ? ser_kernel<4, true> : ser_kernel<4, false>)
+                                       : (L.mode ? ser_kernel<8, true> : ser_kernel<8, false>),
+                               dim3(p.ser_blocks), dim3(64 * SER_WAVES), 0, st, a);
+            break;
+        case PK_RERUN:
+            if (timed) {
+                HIPCK(hipEventRecord(c->tev1[slot], st));
+                c->runs_timed++;
+            }
+            hipLaunchKernelGGL(fb, dim3(p.grid_fb), dim3(64), 0, st, a);
+            break;
+        case PK_DIGEST:
+            if (REC_PROBE) break;
+            hipLaunchKernelGGL(np == 4 ? digest_kernel<4> : digest_kernel<8>, dim3(p.digest_blocks),
+                               dim3(256), 0, st, n_sys, (const uint4 *)c->d_recs, d_results, dcnt);
+            break;
+        }
         HIPCK(hipGetLastError());
     }
-    for (int pass = 0; pass < (blog ? 2 : 1); ++pass) {
-        /* resume pass at the budget pass's grid: it sizes itself from the suspended count;
-         * in serial form (ser_kernel) one workgroup per CU, one system per lane */
-        const SimArgs *a = (const SimArgs *)(c->d_args + 2 * pass);
-        const bool ser = pass == 1 && use_ser;
-        if (!ser || pair) {
-            hipLaunchKernelGGL(fast, dim3(grid_fast), dim3(64 * FW), 0, st, a);
-            HIPCK(hipGetLastError());
-        }
-        if (ser) {
-            /* the CAP build keeps per-node inbox counts for an inbox limit below 256 */
-            const bool capb = c->inbox_limit < (uint32_t)FB_RING;
-            if (order) {
-                const unsigned ob = (unsigned)((n_sys * (uint64_t)np + ORD_THREADS - 1) / ORD_THREADS);
-                hipLaunchKernelGGL(np == 4 ? order_kernel<4> : order_kernel<8>, dim3(ob), dim3(ORD_THREADS), 0, st, a);
-                HIPCK(hipGetLastError());
-            }
-            if (!TRAFFIC_PROBE)
-                hipLaunchKernelGGL(np == 4 ? (capb ? ser_kernel<4, true> : ser_kernel<4, false>)
-                                           : (capb ? ser_kernel<8, true> : ser_kernel<8, false>),
-                                   dim3(ser_blocks), dim3(64 * SER_WAVES), 0, st, a);
-            HIPCK(hipGetLastError());
-        } else if (pair) {
-            hipLaunchKernelGGL(fast_nf, dim3(grid_fast), dim3(64 * FW), 0, st, a);
-            HIPCK(hipGetLastError());
-            if (pass == 0 && fast_serb) {
-                hipLaunchKernelGGL(fast_serb, dim3(grid_fast), dim3(64 * FW), 0, st, a);
-                HIPCK(hipGetLastError());
-            }
-        }
-    }
-    if (timed) {
-        HIPCK(hipEventRecord(c->tev1[slot], st));
-        c->runs_timed++;
-    }
-
-    hipLaunchKernelGGL(fb, dim3(grid_fb), dim3(64), 0, st, (const SimArgs *)(c->d_args + 1));
-    HIPCK(hipGetLastError());
-
-    unsigned long long *dcnt = reinterpret_cast<unsigned long long *>(d_counters);
-    if (REC_PROBE) {}
-    else if (np == 4)
-        hipLaunchKernelGGL(digest_kernel<4>, dim3((unsigned)dblocks), dim3(256), 0, st, n_sys,
-                           (const uint4 *)c->d_recs, d_results, dcnt);
-    else
-        hipLaunchKernelGGL(digest_kernel<8>, dim3((unsigned)dblocks), dim3(256), 0, st, n_sys,
-                           (const uint4 *)c->d_recs, d_results, dcnt);
-    HIPCK(hipGetLastError());
-
-    c->info.grid_blocks = grid_fast;
-    c->info.block_threads = 64 * FW;
-    c->info.waves_per_cu = nb_fast * FW;
-    c->info.cus = c->cus;
-    c->info.ring_cap = ring_eff;
-    c->info.resume_blocks = blog ? (use_ser ? ser_blocks : grid_fast) : 0;
-    c->info.budget_log2 = (int)blog;
-    /* without the pair the host knows the passes; with it, dsm_launch_info_get reads the
-     * device's verdict */
-    const bool ff_kernel = !plain_only && (mode & (M_TR | M_SX)) == 0;   /* step (0) compiled in */
-    c->info.ff_picked = ff_kernel ? 1 : 0;
-    c->info.resume_form = !blog ? DSM_RESUME_NONE
-                        : use_ser ? DSM_RESUME_SERIAL
-                        : (ff_kernel ? DSM_RESUME_FASTFORWARD : DSM_RESUME_LOCKSTEP);
-    c->info.budget_rounds = blog ? (int)((ff_kernel && A.thr_ff) ? A.thr_ff : 1u << blog) : 0;
-    {   /* the MODE of `fast` as instantiated (fast_np_gen: the fused generator has no plain
-         * kernel); with the pair, dsm_launch_info_get replaces these with the picked halves */
-        const int fm = plain_only ? plain_mode : mode;
-        const int fmode = (gen && (fm & M_NOFF)) ? 0 : fm;
-        c->info.budget_mode = fmode;
-        c->info.resume_mode = (blog && !use_ser) ? fmode : -1;
-    }
-    c->info.np = np;
-    c->info.gen = gen ? 1 : 0;
-    c->info.occ = 5;                 /* sim_kernel's default OCC, every fast instantiation */
-    c->info.ser_cap = (use_ser && c->inbox_limit < (uint32_t)FB_RING) ? 1 : 0;
+    c->plan = p;
     c->last_st = st;
-    c->last_pair = pair ? 1 : 0;
-    c->last_use_ser = use_ser ? 1 : 0;
-    c->last_grid_fast = grid_fast;
-    c->last_ser_blocks = ser_blocks;
-    c->last_blog = blog;
-    c->last_thr_ff = A.thr_ff;
-    c->last_order = order ? 1 : 0;
-    c->last_n_sys = n_sys;
-    c->last_rec_words = A.serfmt ? (uint32_t)ssusp_words(ring_eff) : 0u;
-    c->info.lds_bytes_per_block = lds_bytes(ring_eff, FW);
-    c->info.late_log2 = (int)A.late_rsh;
-    c->info.round_limit_log2 = (int)c->round_limit_log2;
-    c->info.fmt_tile = c->fmt_tile;
-    c->info.parse_bpl = c->parse_bpl;
+    c->last_verdict = -1;
     return DSM_OK;
 }
 

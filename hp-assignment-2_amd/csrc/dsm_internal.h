@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include "dsm.h"
+#include "dsm_plan.h"
 
 struct SimArgs;   /* transition-kernel argument block (dsm_engine.hip) */
 
@@ -20,8 +21,12 @@ struct dsm_ctx {
     int ring;
     hipStream_t stream;
     int cus;
-    unsigned int *d_ctrl;            /* claim shards (fast, fallback) + overflow count      */
-    SimArgs *d_args;                 /* [0] fast kernel, [1] 256-deep re-run, [2] resume    */
+    unsigned int *d_ctrl;            /* CTRL_WORDS, zeroed per run (dsm_engine.hip CTRL_*): claim
+                                      * shards of the fast, re-run and resume launches, the
+                                      * overflow and suspended counts, order_kernel's class
+                                      * counts, ffscan_kernel's sample counts               */
+    SimArgs *d_args;                 /* the run's argument blocks (dsm_plan.h ARGS_*), written
+                                      * in stream order by args_kernel                      */
     uint32_t *d_ovf_list;
     size_t ovf_cap;
     uint32_t *d_susp;                /* two-pass schedule: suspended node states             */
@@ -47,22 +52,17 @@ struct dsm_ctx {
      * runs (run k uses slot k % DSM_TIMING_RING) */
     hipEvent_t tev0[DSM_TIMING_RING], tev1[DSM_TIMING_RING];
     uint64_t runs_timed;
-    dsm_launch_info info;
-    /* the last run's pass choice when the device picks it (DSM_FF_AUTO): dsm_launch_info_get
-     * reads the trace scan's verdict after waiting for last_st */
+    /* the last run's plan and stream.  Where the device picks the passes (plan.pair),
+     * dsm_launch_info_get waits for last_st and reads the trace scan's verdict once
+     * (last_verdict: -1 not read yet) */
+    dsmp::Plan plan;
     hipStream_t last_st;
-    int last_pair, last_use_ser, last_grid_fast, last_ser_blocks;
-    uint32_t last_blog, last_thr_ff;
-    /* the last run, for dsm_debug_order_state: order_kernel launched, the systems, the words of
-     * a serial-form record (0: the budget pass wrote the lock-step form) */
-    int last_order;
-    uint64_t last_n_sys;
-    uint32_t last_rec_words;
+    int last_verdict;
     /* two-pass schedule and round limit (dsm_set_budget / dsm_set_round_limit; defaults from
      * DSM_BUDGET_LOG2 / DSM_LATE_LOG2, read once at dsm_open) */
     uint32_t budget_log2, late_log2, round_limit_log2, inbox_limit;
-    uint32_t ff_budget_log2;         /* the fast-forward kernel's budget (DSM_FF_BUDGET_LOG2) */
-    uint32_t ff_budget_rounds;       /* ... as a round count, any value (DSM_FF_BUDGET_ROUNDS) */
+    uint32_t ff_budget_rounds;       /* the fast-forward kernel's budget in rounds
+                                      * (DSM_FF_BUDGET_ROUNDS, or 1 << DSM_FF_BUDGET_LOG2)   */
     int ff_mode;                       /* DSM_FF_OFF / ON / AUTO */
     int serial;                        /* resume pass in serial form (ser_kernel; DSM_SERIAL) */
     uint32_t lone_rounds;              /* budget pass: suspend quiet-lone systems, checked every
