@@ -60,6 +60,19 @@
 #define SER_DEAD_FWD 1      /* ser_macro also applies a system's dead-end forward */
 #endif
 
+/* Counting hooks of the host model (tests/model/serial_model.cpp defines them before this
+ * header: ser_step's actions by type, ser_macro's cases and decline reasons).  Empty here, so in
+ * the kernels' build their arguments are not even evaluated. */
+#ifndef SER_COUNT_STEP
+#define SER_COUNT_STEP(op) ((void)0)
+#endif
+#ifndef SER_COUNT_DECLINE
+#define SER_COUNT_DECLINE(home_ge_np, dead_fwd_off, em_no_owner, notice_home_off, notice_fwd_owner, notice_fan_sharer) ((void)0)
+#endif
+#ifndef SER_COUNT_MACRO
+#define SER_COUNT_MACRO(hit, upg, ev, mod, notice, notice_req_home, notice_vic_home, fwd, dead, wr, fan) ((void)0)
+#endif
+
 #include "dsm_table.h"
 
 namespace dsms {
@@ -300,6 +313,7 @@ DSM_HD uint32_t ser_step(M &m, SReg &r, const T &tab, F &&fetch, R &&on_dump, ui
     }
     ct += doIssue ? (1u << SC_IP) : 0u;
     const uint32_t op = doDump ? (uint32_t)DT_DUMP : dt_type(w);
+    SER_COUNT_STEP(op);
 
     /* decode + micro-op table + datapath (dsm_table.h), as in sim_kernel step (2)-(3) */
     DtIn in;
@@ -548,7 +562,12 @@ DSM_HD bool ser_macro(M &m, SReg &r, SCache &cc, F &&fetch, R &&on_dump, P &&sta
                     !((dH == 0u) & miss & (bvH == 0u)) &
                     !(notice & ((((x == h) | (x == vh)) & !SER_NOTICE_HOME) | (fwd & (x == o)) |
                                 (fan & (((others >> x) & 1u) != 0u))));
+    SER_COUNT_DECLINE(!((NP == 8) || (h < (uint32_t)NP)), !(SER_DEAD_FWD | !dead),
+                      (dH == 0u) & miss & (bvH == 0u),
+                      notice & ((x == h) | (x == vh)) & !SER_NOTICE_HOME, notice & fwd & (x == o),
+                      notice & fan & (((others >> x) & 1u) != 0u));
     if (!ok) return false;
+    SER_COUNT_MACRO(hit, upg, ev, mod, notice, notice & (x == h), selfn, fwd, dead, wr != 0u, fan);
     stamp(2);
     /* the home's directory entry and memory after the request (:188-236, :298-328, :375-435):
      * READ_REQUEST U -> EM {n}, S -> S + n, EM at n unchanged, EM at o -> S {o, n};

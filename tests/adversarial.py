@@ -1,0 +1,272 @@
+"""Adversarial inputs for the engine's launch routes (a helper module, imported like
+scenarios.py): a contention ensemble, the hand-derived quirk scenarios tiled into one ensemble,
+and ROUTES, the table of engine routes (hp-assignment-2_amd/csrc/dsm_plan.h) with the evidence
+that each really ran.
+
+tests/test_routes_model.py carries the CPU certificate of these inputs (micro-op rows reached,
+ser_macro cases, status mix, digest); tests/test_gpu_routes.py drives them through every route.
+"""
+import hashlib
+
+import numpy as np
+
+import scenarios
+
+STRIDE = 64
+# per-node instruction counts: empty, tiny, and one below / at / one past each 16-byte chunk
+# boundary of the packed trace (8 instructions to a chunk)
+COUNTS = (0, 1, 2, 7, 8, 9, 15, 16, 17, 31, 32, 33, 63, 64)
+SHORT = (0, 1, 2, 7, 8)                      # the nodes beside a long one
+T_ONE_INDEX, T_LONG_NODE, T_LOW, T_RACE = 1, 2, 4, 8    # family tag bits of contention()
+N_CONTENTION = 16384                         # the ensemble size the certificate is computed for
+SEED = 20
+
+
+def contention(np_, seed, n, stride=STRIDE):
+    """-> (traces u16 [n, np, stride], counts u32 [n, np], tag u8 [n]).
+
+    Every system works on a few addresses only, so its nodes collide at the homes from the
+    first round on.  Three families, drawn per system:
+      - the base one: 1-4 distinct addresses, half of the systems with all of them on one cache
+        index (T_ONE_INDEX: every miss evicts), per-node counts from COUNTS, and in a quarter
+        of the systems one node of `stride` instructions beside nodes of at most 8
+        (T_LONG_NODE: a long lone tail);
+      - T_LOW (one in five): 5-8 distinct addresses, and nine instructions in ten go to the
+        node's own one, so that more systems run to completion;
+      - T_RACE (one in six): one address, 1-4 instructions per node.  Nodes that finish early
+        while the home's inbox is still backed up are what makes a late FLUSH_INVACK overwrite
+        a newer owner, and a request whose EM owner is the requester (measured: this family
+        reaches those two rows in ~0.5% of its systems, the base one in ~0.02%).
+    The write share is 0.1 / 0.5 / 0.9 per system (0.4 / 0.6 in T_RACE).  Homes are < np.  The
+    slots past a node's count hold instructions too (valid ones): a reader that runs past the
+    count issues them.  Deterministic from numpy.random.default_rng(seed); digest() pins it."""
+    assert stride >= 64 and stride % 8 == 0
+    rng = np.random.default_rng(seed)
+    fam = rng.random(n)
+    race, low = fam < 1 / 6, (fam >= 1 / 6) & (fam < 1 / 6 + 0.2)
+    k = np.where(low, rng.integers(5, 9, n), rng.integers(1, 5, n))
+    k = np.where(race, 1, k)
+    one = (rng.random(n) < 0.5) & ~low & ~race
+    longn = (rng.random(n) < 0.25) & ~race
+    # 8 distinct addresses per system: the smallest random keys among the allowed ones
+    naddr = np_ * 16
+    a_all = np.arange(naddr)
+    idx = rng.integers(0, 4, n)
+    key = rng.random((n, naddr))
+    key = np.where(one[:, None] & ((a_all[None, :] & 3) != idx[:, None]), 2.0, key)
+    pool = np.argsort(key, axis=1, kind="stable")[:, :8]           # home << 4 | block
+    wshare = np.array([0.1, 0.5, 0.9])[rng.integers(0, 3, n)]
+    wshare = np.where(race, np.array([0.4, 0.6])[rng.integers(0, 2, n)], wshare)
+    pick = (rng.random((n, np_, stride)) * k[:, None, None]).astype(np.int64)
+    own = np.arange(np_)[None, :, None] % k[:, None, None]
+    pick = np.where(low[:, None, None] & (rng.random((n, np_, stride)) < 0.9), own, pick)
+    addr = np.take_along_axis(pool, pick.reshape(n, -1), axis=1).reshape(n, np_, stride)
+    wr = (rng.random((n, np_, stride)) < wshare[:, None, None]).astype(np.int64)
+    val = rng.integers(0, 256, (n, np_, stride)) * wr
+    traces = ((wr << 15) | (addr << 8) | val).astype(np.uint16)
+    counts = np.array(COUNTS)[rng.integers(0, len(COUNTS), (n, np_))]
+    short = np.array(SHORT)[rng.integers(0, len(SHORT), (n, np_))]
+    who = rng.integers(0, np_, n)
+    short[np.arange(n), who] = stride
+    counts = np.where(longn[:, None], short, counts)
+    counts = np.where(race[:, None], rng.integers(1, 5, (n, np_)), counts).astype(np.uint32)
+    tag = (one * T_ONE_INDEX + longn * T_LONG_NODE + low * T_LOW + race * T_RACE).astype(np.uint8)
+    assert int(((traces >> 12) & 7).max()) < np_
+    return traces, counts, tag
+
+
+def digest(traces, counts):
+    """sha256 of an ensemble, so the GPU machine's numpy provably builds the one the CPU
+    certificate (tests/test_routes_model.py) was computed for."""
+    h = hashlib.sha256()
+    h.update(np.ascontiguousarray(traces, dtype="<u2").tobytes())
+    h.update(np.ascontiguousarray(counts, dtype="<u4").tobytes())
+    return h.hexdigest()
+
+
+# contention(np, SEED, N_CONTENTION): measured by tests/test_routes_model.py
+CONTENTION_SHA256 = {
+    4: "94306ec20e3f06796f454be266d7d5f23ee25c06525c92b18d504aeb31d9d9ca",
+    8: "1c9e7355ce98ac465bc9682b980d7f3854863e9b9c45a3050404db3322309228",
+}
+
+TILE_STRIDE = 16
+
+
+def tiled_scenarios(np_):
+    """-> (traces [n, np, 16], counts [n, np], which [n], names): every scenario of
+    scenarios.py with np_ nodes -- at 8 nodes also the 4-node ones with nodes 4-7 idle (they
+    dump in round 1; only the oracle speaks for those, their `check` is for 4 nodes) --
+    re-packed to one stride and repeated.  The period is odd (the first scenarios come twice
+    if need be) and so is the number of periods: n >= 512 is coprime to 16, and each scenario
+    sits at every system slot of a wave and beside different neighbours.  which[i] indexes
+    names; names[j] is a key of scenarios.SCENARIOS."""
+    names, base_t, base_c = [], [], []
+    for name in sorted(scenarios.SCENARIOS):
+        tr, cn, _ = scenarios.SCENARIOS[name]()
+        if tr.shape[1] != np_ and not (np_ == 8 and tr.shape[1] == 4):
+            continue
+        assert int(cn.max()) <= TILE_STRIDE
+        t = np.zeros((np_, TILE_STRIDE), dtype=np.uint16)
+        c = np.zeros(np_, dtype=np.uint32)
+        t[:tr.shape[1]] = tr[0, :, :TILE_STRIDE]
+        c[:tr.shape[1]] = cn[0]
+        names.append(name)
+        base_t.append(t)
+        base_c.append(c)
+    period = list(range(len(names)))
+    if len(period) % 2 == 0:
+        period.append(0)
+    reps = -(-512 // len(period)) | 1
+    which = np.array(period * reps, dtype=np.int64)
+    assert len(which) >= 512 and len(which) % 2 == 1
+    return np.stack(base_t)[which], np.stack(base_c)[which], which, names
+
+
+def native(name, np_):
+    """The scenario's own check applies: it was derived for this node count."""
+    return scenarios.SCENARIOS[name]()[0].shape[1] == np_
+
+
+# ---- engine routes ------------------------------------------------------------------------
+# A route is one launch list of dsm_plan.h plan_build.  Per entry:
+#   env       DSM_* read at dsm_open (every route sets DSM_SERIAL; tests clear the other knobs)
+#   engine    pydsm.Engine keyword arguments (ring_cap, issue_trace)
+#   setters   (method, args) calls on the Engine before the run
+#   info      launch_info() fields the run must report; `kernels` is a template over np and the
+#             ring the plan gives the fast kernel (plan_ring: 12 for a MODE outside the bench
+#             ones unless 4 is configured).  Derived from plan_build / plan_info and the rows of
+#             tests/test_gpu_plan.py; tests/test_routes_model.py re-derives every entry on the
+#             CPU through tests/model/plan_model.cpp.
+#   counters  counters that must be non-zero when the oracle says the ensemble gives the route
+#             its work (a system outlasting the budget: resumed; an inbox deeper than the
+#             ring inside the budget: overflow_reruns), see tests/test_gpu_routes.py
+#   zero      counters that must be zero (ff_steps is never listed: the 256-deep re-run kernel
+#             of a bench-mode run has the fast-forward step whatever the fast kernel is)
+#   compare   what the oracle run is: "lockstep", "issue" (events of every system too) or
+#             "stalls" (the seeded schedule)
+#   pair      FF_AUTO: `info` is the plain verdict's, `info_ff` the fast-forward verdict's
+_SIM = "sim_kernel<{np}, {ring}, 4, false, %d, 5>"
+_SER = "ser_kernel<{np}, %s>"
+STALL_SEED, STALL_THRESH = 11, 0x8000
+LIMIT_LOG2 = 20          # a round limit no system reaches: the run-time-limit build, same results
+
+
+def _one(mode):
+    return "run=" + _SIM % mode
+
+
+def _two(budget, resume):
+    r = (_SIM % resume) if isinstance(resume, int) else _SER % resume
+    return "budget=" + _SIM % budget + " resume=" + r
+
+
+def _route(env=None, engine=None, setters=(), info=None, counters=(), zero=(), compare="lockstep",
+           info_ff=None):
+    e = {"DSM_SERIAL": "1"}
+    e.update(env or {})
+    return dict(env=e, engine=engine or {}, setters=list(setters), info=info, counters=counters,
+                zero=zero, compare=compare, info_ff=info_ff)
+
+
+_LONE = {"DSM_LONE": "8", "DSM_LONE_MIN": "0"}
+_ONE_PASS = dict(resume_form=0, budget_rounds=0, budget_log2=0, resume_mode=-1, ser_cap=0)
+
+
+def _serial(blog, ring, cap=0, extra_zero=()):
+    setters = [("set_fast_forward", ("FF_OFF",)), ("set_budget", (blog, 0))]
+    if cap:
+        setters.append(("set_inbox_limit", (cap,)))
+    return _route(
+        env=_LONE, engine=dict(ring_cap=ring), setters=setters,
+        info=dict(kernels=_two(48, "true" if cap else "false"), resume_form=2, ff_picked=0,
+                  budget_mode=48, resume_mode=-1, budget_rounds=1 << blog, budget_log2=blog,
+                  ser_cap=1 if cap else 0, ring_cap=ring),
+        # the lone-node macro-step runs only in the default (non-CAP) serial build
+        counters=("resumed",) + (() if cap else ("ser_macro_steps",)) + (("overflow_reruns",) if ring == 4 else ()),
+        zero=(("ser_macro_steps",) if cap else ()) + tuple(extra_zero))
+
+
+ROUTES = {
+    # one pass
+    "one_pass_plain": _route(
+        setters=[("set_fast_forward", ("FF_OFF",)), ("set_budget", (0, 0))],
+        info=dict(kernels=_one(16), ff_picked=0, budget_mode=16, ring_cap=12, **_ONE_PASS),
+        counters=("overflow_reruns",), zero=("resumed", "ser_macro_steps")),
+    "one_pass_plain_ring4": _route(
+        engine=dict(ring_cap=4),
+        setters=[("set_fast_forward", ("FF_OFF",)), ("set_budget", (0, 0))],
+        info=dict(kernels=_one(16), ff_picked=0, budget_mode=16, ring_cap=4, **_ONE_PASS),
+        counters=("overflow_reruns",), zero=("resumed", "ser_macro_steps")),
+    "one_pass_ff": _route(
+        setters=[("set_fast_forward", ("FF_ON",)), ("set_budget", (0, 0))],
+        info=dict(kernels=_one(0), ff_picked=1, budget_mode=0, ring_cap=12, **_ONE_PASS),
+        counters=("ff_steps", "overflow_reruns"), zero=("resumed", "ser_macro_steps")),
+    "one_pass_limits": _route(
+        setters=[("set_round_limit", (LIMIT_LOG2,)), ("set_budget", (0, 0))],
+        info=dict(kernels=_one(8), ff_picked=1, budget_mode=8, ring_cap=12,
+                  round_limit_log2=LIMIT_LOG2, **_ONE_PASS),
+        counters=("overflow_reruns",), zero=("resumed", "status_ROUND_LIMIT")),
+    "issue_trace": _route(
+        engine=dict(issue_trace=True),
+        info=dict(kernels=_one(2), ff_picked=0, budget_mode=2, ring_cap=12, **_ONE_PASS),
+        counters=("overflow_reruns",), zero=("resumed",), compare="issue"),
+    "seeded_stalls": _route(
+        setters=[("set_schedule", (STALL_SEED, STALL_THRESH))],
+        info=dict(kernels=_one(4), ff_picked=0, budget_mode=4, ring_cap=12, **_ONE_PASS),
+        zero=("resumed",), compare="stalls"),
+    # M_SERB budget pass -> order_kernel -> ser_kernel<NP, false>, from the serial-form record
+    "serial_b1_ring12": _serial(1, 12),
+    "serial_b2_ring4": _serial(2, 4),
+    "serial_b3_ring8": _serial(3, 8),
+    "serial_b5_ring16": _serial(5, 16),
+    # ... the CAP build (an inbox limit between the ring and 256 keeps the bench mode)
+    "serial_cap64": _serial(2, 12, cap=64),
+    # M_LIM budget pass -> ser_kernel from the lock-step form (start_ls), no order_kernel
+    "serial_from_lockstep": _route(
+        env=_LONE, setters=[("set_round_limit", (LIMIT_LOG2,)), ("set_budget", (2, 0))],
+        info=dict(kernels=_two(8, "false"), resume_form=2, ff_picked=1, budget_mode=8,
+                  resume_mode=-1, budget_rounds=4, budget_log2=2, ser_cap=0, ring_cap=12,
+                  round_limit_log2=LIMIT_LOG2),
+        counters=("resumed", "ser_macro_steps"), zero=("status_ROUND_LIMIT",)),
+    # lock-step resume: the plain kernel, and the run-time-limit one
+    "lockstep_resume": _route(
+        env={"DSM_SERIAL": "0"}, setters=[("set_fast_forward", ("FF_OFF",)), ("set_budget", (2, 0))],
+        info=dict(kernels=_two(16, 16), resume_form=1, ff_picked=0, budget_mode=16, resume_mode=16,
+                  budget_rounds=4, budget_log2=2, ser_cap=0, ring_cap=12),
+        counters=("resumed",), zero=("ser_macro_steps",)),
+    "lockstep_resume_limits": _route(
+        env={"DSM_SERIAL": "0"},
+        setters=[("set_fast_forward", ("FF_OFF",)), ("set_round_limit", (LIMIT_LOG2,)), ("set_budget", (2, 0))],
+        info=dict(kernels=_two(8, 8), resume_form=3, ff_picked=1, budget_mode=8, resume_mode=8,
+                  budget_rounds=4, budget_log2=2, ser_cap=0, ring_cap=12, round_limit_log2=LIMIT_LOG2),
+        counters=("resumed",), zero=("ser_macro_steps", "status_ROUND_LIMIT")),
+    # fast-forward two-pass: the fast-forward kernel's own budget, in rounds
+    "ff_two_pass_4": _route(
+        env={"DSM_FF_BUDGET_ROUNDS": "4"},
+        setters=[("set_fast_forward", ("FF_ON",)), ("set_budget", (3, 0))],
+        info=dict(kernels=_two(0, 0), resume_form=3, ff_picked=1, budget_mode=0, resume_mode=0,
+                  budget_rounds=4, budget_log2=3, ser_cap=0, ring_cap=12),
+        counters=("resumed", "ff_steps"), zero=("ser_macro_steps",)),
+    "ff_two_pass_100": _route(
+        env={"DSM_FF_BUDGET_ROUNDS": "100"},
+        setters=[("set_fast_forward", ("FF_ON",)), ("set_budget", (3, 0))],
+        info=dict(kernels=_two(0, 0), resume_form=3, ff_picked=1, budget_mode=0, resume_mode=0,
+                  budget_rounds=100, budget_log2=3, ser_cap=0, ring_cap=12),
+        counters=("resumed", "ff_steps"), zero=("ser_macro_steps",)),
+    # the pair: ffscan_kernel picks on the device; the info names the half that ran
+    "pair": _route(
+        env=_LONE, setters=[("set_fast_forward", ("FF_AUTO",)), ("set_budget", (3, 0))],
+        info=dict(kernels=_two(48, "false"), resume_form=2, ff_picked=0, budget_mode=48,
+                  resume_mode=-1, budget_rounds=8, budget_log2=3, ser_cap=0, ring_cap=12),
+        info_ff=dict(kernels=_two(16, 0), resume_form=3, ff_picked=1, budget_mode=16,
+                     resume_mode=0, budget_rounds=448, budget_log2=3, ser_cap=0, ring_cap=12),
+        counters=("resumed", "ff_sample_instrs")),
+}
+
+
+def route_info(route, np_, ff=False):
+    """The launch info the route must report at np_ nodes (the kernel label filled in)."""
+    want = dict(route["info_ff"] if ff else route["info"])
+    want["kernels"] = want["kernels"].format(np=np_, ring=want["ring_cap"])
+    return want

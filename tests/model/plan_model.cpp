@@ -291,9 +291,63 @@ int rows() {
     return n;
 }
 
+/* plan_model info key=value ...: the launches and the launch info of one configuration (the
+ * fields of PlanIn by name, over base(); verdict=0/1), as JSON, with the kernel label
+ * dsm_launch_kernel_names makes of it.  tests/test_routes_model.py derives the evidence of
+ * tests/adversarial.py's route table from it. */
+int info(int argc, char **argv) {
+    PlanIn in = base();
+    int v = 0;
+    for (int i = 2; i < argc; ++i) {
+        char *eq = strchr(argv[i], '=');
+        if (!eq) return 2;
+        const std::string k(argv[i], eq - argv[i]);
+        const long x = strtol(eq + 1, nullptr, 0);
+        if (k == "np") in.np = (int)x;
+        else if (k == "ring") in.ring = (int)x;
+        else if (k == "tc") in.tc = x != 0;
+        else if (k == "tr") in.tr = x != 0;
+        else if (k == "sx") in.sx = x != 0;
+        else if (k == "limit") in.round_limit_log2 = x ? (uint32_t)x : RSH_MAX;
+        else if (k == "inbox") in.inbox_limit = x ? (uint32_t)x : (uint32_t)FB_RING;
+        else if (k == "ff") in.ff_mode = (int)x;
+        else if (k == "serial") in.serial = (int)x;
+        else if (k == "budget") in.budget_log2 = (uint32_t)x;
+        else if (k == "late") in.late_log2 = (uint32_t)x;
+        else if (k == "ffb") in.ff_budget_rounds = (uint32_t)x;
+        else if (k == "lone") in.lone_rounds = (uint32_t)x;
+        else if (k == "lone_min") in.lone_min = (uint32_t)x;
+        else if (k == "n") in.n_sys = (uint64_t)x;
+        else if (k == "verdict") v = x != 0;
+        else return 2;
+    }
+    const Plan p = make(in, v);
+    const dsm_launch_info li = plan_info(p, v != 0);
+    char b[2][96], label[256];
+    auto sim = [&](char *o, int m) {
+        snprintf(o, 96, "sim_kernel<%d, %d, %d, %s, %d, %d>", li.np, li.ring_cap, li.block_threads / 64,
+                 li.gen ? "true" : "false", m, li.occ);
+    };
+    sim(b[0], li.budget_mode);
+    if (li.budget_mode < 0) snprintf(label, sizeof label, "none");
+    else if (li.resume_form == DSM_RESUME_NONE) snprintf(label, sizeof label, "run=%s", b[0]);
+    else {
+        if (li.resume_mode >= 0) sim(b[1], li.resume_mode);
+        else snprintf(b[1], 96, "ser_kernel<%d, %s>", li.np, li.ser_cap ? "true" : "false");
+        snprintf(label, sizeof label, "budget=%s resume=%s", b[0], b[1]);
+    }
+    printf("{\"launches\": \"%s\", \"pair\": %d, \"kernels\": \"%s\", \"budget_mode\": %d, \"resume_mode\": %d, "
+           "\"resume_form\": %d, \"ff_picked\": %d, \"budget_rounds\": %d, \"budget_log2\": %d, \"ser_cap\": %d, "
+           "\"ring_cap\": %d, \"round_limit_log2\": %d}\n", launches(p).c_str(), p.pair ? 1 : 0, label,
+           li.budget_mode, li.resume_mode, li.resume_form, li.ff_picked, li.budget_rounds, li.budget_log2,
+           li.ser_cap, li.ring_cap, li.round_limit_log2);
+    return 0;
+}
+
 }  // namespace
 
-int main() {
+int main(int argc, char **argv) {
+    if (argc > 1 && !strcmp(argv[1], "info")) return info(argc, argv);
     const long cases = enumerate();
     printf("{\"cases\": %ld, \"rows\": %d}\n", cases, rows());
     return 0;

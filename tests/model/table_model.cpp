@@ -4,9 +4,14 @@
  * datapath), run over generated systems.  tests/test_table_model.py compares its per-system
  * results with the oracle's; this pins the transition table without a GPU.
  *
- *   table_model gen <np> <dist> <seed> <n_instr> <first> <n> <ring_cap> <out.bin>
- *   table_model packed <np> <stride> <n> <traces.u16> <counts.u32> <ring_cap> <out.bin>
- * write n dsm_res records (oracle/dsm_common.h layout).
+ *   table_model gen <np> <dist> <seed> <n_instr> <first> <n> <ring_cap> <out.bin> [rows_out [min_round]]
+ *   table_model packed <np> <stride> <n> <traces.u16> <counts.u32> <ring_cap> <out.bin> [rows_out [min_round]]
+ * write n dsm_res records (oracle/dsm_common.h layout).  With rows_out, also the use of the
+ * micro-op table: one text line per table row, "row op' sub actions systems" -- the row's
+ * index, the name of its op' and its index among that op's rows, the number of node-actions
+ * that took the row (every action of a round goes through dt_index, an idle node's too) and the
+ * number of distinct systems with such an action -- counting only actions in rounds >
+ * min_round (default 0: all).  tests/test_routes_model.py compares ensembles by it.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -26,6 +31,17 @@ struct Sys {
     uint32_t head[8], cnt[8];
 };
 
+/* use of the table's rows (rows_out) */
+struct Rows {
+    uint32_t min_round;
+    uint64_t actions[DT_ENTRIES], systems[DT_ENTRIES];
+    uint64_t seen[DT_ENTRIES];          /* 1 + the last system that used the row */
+};
+const char *const OP_NAMES[DT_NOPS] = {
+    "READ_REQUEST", "WRITE_REQUEST", "REPLY_RD", "REPLY_WR", "REPLY_ID", "INV", "UPGRADE",
+    "WRITEBACK_INV", "WRITEBACK_INT", "FLUSH", "FLUSH_INVACK", "EVICT_SHARED", "EVICT_MODIFIED",
+    "ISSUE", "ISSUE_WR", "DUMP", "IDLE", "EVICT_SHARED_HOME", "ASSERT", "OP19"};
+
 struct Src {
     const uint16_t *trace;      /* packed: [np][stride] of this system, else null */
     const uint32_t *counts;
@@ -37,7 +53,7 @@ struct Src {
     }
 };
 
-int run_one(Sys &y, const uint32_t *tab, const Src &src, dsm_res *res) {
+int run_one(Sys &y, const uint32_t *tab, const Src &src, dsm_res *res, Rows *rows, uint64_t sys_no) {
     const int np = y.np;
     const uint32_t npm = (1u << np) - 1u;
     for (int i = 0; i < np; ++i) {
@@ -85,6 +101,10 @@ int run_one(Sys &y, const uint32_t *tab, const Src &src, dsm_res *res) {
             uint32_t evDb;
             const uint32_t opx = dt_opx(in);
             const uint32_t ti = dt_index(in, dt_hdr(tab, opx), &evDb);
+            if (rows && r > rows->min_round) {
+                rows->actions[ti]++;
+                if (rows->seen[ti] != sys_no + 1) { rows->seen[ti] = sys_no + 1; rows->systems[ti]++; }
+            }
             const DtOut o = dt_apply(in, tab[2 * ti], tab[2 * ti + 1], evDb);
             s.cache_addr[idx] = (uint8_t)o.nLa; s.cache_value[idx] = (uint8_t)o.nLv;
             s.cache_state[idx] = (uint8_t)o.nLs;
@@ -153,13 +173,17 @@ static uint8_t *slurp(const char *path, size_t *len) {
 }
 
 int main(int argc, char **argv) {
-    const bool gen = argc == 10 && !strcmp(argv[1], "gen");
-    const bool packed = argc == 9 && !strcmp(argv[1], "packed");
+    const bool gen = argc >= 10 && argc <= 12 && !strcmp(argv[1], "gen");
+    const bool packed = argc >= 9 && argc <= 11 && !strcmp(argv[1], "packed");
     if (!gen && !packed) {
-        fprintf(stderr, "usage: table_model gen np dist seed n_instr first n ring out\n"
-                        "       table_model packed np stride n traces counts ring out\n");
+        fprintf(stderr, "usage: table_model gen np dist seed n_instr first n ring out [rows_out [min_round]]\n"
+                        "       table_model packed np stride n traces counts ring out [rows_out [min_round]]\n");
         return 1;
     }
+    const int fixed = gen ? 10 : 9;
+    const char *rows_out = argc > fixed ? argv[fixed] : nullptr;
+    Rows *rows = rows_out ? (Rows *)calloc(1, sizeof(Rows)) : nullptr;
+    if (rows && argc > fixed + 1) rows->min_round = (uint32_t)strtoul(argv[fixed + 1], 0, 0);
     static uint32_t tab[DT_TABLE_WORDS];
     if (dt_build(tab) > DT_ENTRIES) {
         fprintf(stderr, "micro-op table rows exceed DT_ENTRIES\n");
@@ -182,7 +206,7 @@ int main(int argc, char **argv) {
         res = (dsm_res *)calloc(n ? n : 1, sizeof(dsm_res));
         for (uint64_t i = 0; i < n; ++i) {
             Src src = {nullptr, nullptr, 0, dist, seed, n_instr, first + i};
-            run_one(*y, tab, src, &res[i]);
+            run_one(*y, tab, src, &res[i], rows, i);
         }
     } else {
         const uint32_t stride = (uint32_t)strtoul(argv[3], 0, 0);
@@ -197,11 +221,23 @@ int main(int argc, char **argv) {
         res = (dsm_res *)calloc(n ? n : 1, sizeof(dsm_res));
         for (uint64_t i = 0; i < n; ++i) {
             Src src = {tr + i * np * stride, cn + i * np, stride, 0, 0, 0, 0};
-            run_one(*y, tab, src, &res[i]);
+            run_one(*y, tab, src, &res[i], rows, i);
         }
     }
     FILE *f = fopen(out, "wb");
     if (!f || fwrite(res, sizeof(dsm_res), n, f) != n) return 1;
     fclose(f);
+    if (rows) {
+        FILE *g = fopen(rows_out, "w");
+        if (!g) return 1;
+        for (uint32_t op = 0; op < DT_NOPS; ++op) {
+            const uint32_t hdr = dt_hdr(tab, op), first = hdr >> 16, w = (hdr >> 5) & 7u;
+            for (uint32_t sub = 0; sub < (1u << w); ++sub)
+                fprintf(g, "%u %s %u %llu %llu\n", first + sub, OP_NAMES[op], sub,
+                        (unsigned long long)rows->actions[first + sub],
+                        (unsigned long long)rows->systems[first + sub]);
+        }
+        fclose(g);
+    }
     return 0;
 }

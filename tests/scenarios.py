@@ -266,3 +266,43 @@ def write_hit_on_exclusive_is_local():
         assert mem(fin[1], 9) == 29
         assert dirent(fin[1], 9) == (EM, 0x02)
     return tr, cn, check
+
+
+# ---- found by a search over the serial model's decline counters (tests/model/serial_model.cpp),
+# shrunk, derived by hand ------------------------------------------------------------------
+
+@scenario
+def notice_and_forward_meet_at_one_node():
+    """A lone node's miss whose eviction notice and whose forward go to the SAME node: the one
+    transaction of a quiet system that dsm_serial.h ser_macro declines for the order of that
+    node's inbox (its `ok`: notice & fwd & x == o).  Home 2 serves 0x28 and 0x2c, both on cache
+    index 0.  R1: all four nodes issue on 0x28.  R2-R5: the home takes them in sender order --
+    node 0's WRITE_REQUEST (U -> EM{0}), node 1's (EM owner 0 -> WRITEBACK_INV r2=1, bv {1}),
+    its own READ_REQUEST (EM{1} -> WRITEBACK_INT r2=2, S{1,2}), node 3's WRITE_REQUEST(189)
+    (S{1,2} -> REPLY_ID{1,2}, EM{3}).  R6: the home part of node 0's FLUSH_INVACK arrives late
+    and sets EM{r2 = 1} over EM{3} (:478-480); node 3 installs 189 as M and invalidates 1 and
+    2.  R8: node 3 reads 0x2c and evicts 0x28 (EVICT_MODIFIED 189); node 1 reads 0x2c too.
+    R9-R10: node 1 gets 0x2c exclusive; the home stores 189 and keeps EM{1} for 0x28 (sender 3
+    not in bv): stale, node 1 does not hold 0x28.  R11-R13: node 3's READ_REQUEST(0x2c) meets
+    EM{1} -> WRITEBACK_INT, S{1,3}; node 1 flushes 52 to the home and node 3.  Nodes 0, 1, 2
+    have dumped (R5, R11, R12): node 3 is alone, nothing is queued.  R14: node 3 reads 0x28:
+    miss, the victim 0x2c is SHARED -> EVICT_SHARED(0x2c), then READ_REQUEST(0x28), both to
+    home 2.  R15: the eviction leaves one sharer: EM{1} and a notice to node 1 (:507-519).
+    R16: node 1 takes the notice (0x2c S -> E); the home takes the request: the stale EM{1} ->
+    WRITEBACK_INT(r2=3) to node 1, S{1,3}.  R17: node 1's line holds 0x2c: ignored (:265-270).
+    Node 3 waits forever."""
+    tr, cn = build(4, [[("WR", 0x28, 234)], [("WR", 0x28, 122), ("RD", 0x2C)], [("RD", 0x28)],
+                       [("WR", 0x28, 189), ("RD", 0x28), ("RD", 0x2C), ("RD", 0x28)]])
+
+    def check(res, dump, fin):
+        assert int(res["status"]) == DEADLOCKED | (0b0111 << 8)
+        assert (int(res["rounds"]), int(res["msgs"]), int(res["instrs"])) == (17, 24, 8)
+        assert int(fin[3][61]) & 1 == 1           # node 3 still waitingForReply
+        assert line(fin[3], 0) == (0x28, 0, I)
+        assert dirent(fin[2], 8) == (DS, 0x0A)    # the forward's S{1,3} over the stale EM{1}
+        assert dirent(fin[2], 12) == (EM, 0x02)   # the eviction's EM{1}
+        assert mem(fin[2], 8) == 189 and mem(fin[2], 12) == 52
+        assert line(dump[1], 0) == (0x2C, 52, E)  # dumped at R11, exclusive since R10
+        assert line(fin[1], 0) == (0x2C, 52, E)   # SHARED at R12, EXCLUSIVE again by the notice
+        assert line(fin[0], 0) == (0x28, 234, I)
+    return tr, cn, check
