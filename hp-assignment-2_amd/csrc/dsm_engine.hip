@@ -519,6 +519,24 @@ sim_kernel(const SimArgs *Ap) {
     const uint16_t *tb = nullptr;
     uint32_t rounds = 0, rmsg = 0;
     bool live = false;
+    /* TC: messages this node handled in the current system, two types to a register as 16-bit
+     * halves (type t in tc[t >> 1], half t & 1).  A field never reaches 2^16: a system issues at
+     * most I = DSM_MAX_NP * DSM_MAX_INSTR = 32,768 instructions, a node 4,096 of them, and
+     *   - READ_REQUEST, WRITE_REQUEST, UPGRADE: an instruction sends at most one request: <= I;
+     *   - REPLY_RD, REPLY_WR, REPLY_ID: answers to the node's own requests: <= 4,096;
+     *   - WRITEBACK_INT, WRITEBACK_INV: a home sends at most one per request it handles: <= I;
+     *   - FLUSH, FLUSH_INVACK: a write-back sends one to the home and one to the requester where
+     *     that is another node, so a node receives at most one per write-back: <= I;
+     *   - INV: a REPLY_ID sends each other node at most one: <= the requests, <= I;
+     *   - EVICT_MODIFIED, EVICT_SHARED: a line is replaced only at an issue (a node has one
+     *     request outstanding and a request at most one reply, which finds the line already
+     *     tagged with its address by that issue), at most one per instruction, and a node's first
+     *     instruction finds its cache empty: <= I - 8 = 32,760 replacements in all.  An
+     *     EVICT_SHARED handled at its home makes the home send at most one more, to the last
+     *     sharer, which sends none: <= 2 * 32,760 = 65,520 EVICT_SHARED at one node.
+     * The largest count the oracle reaches on tests/adversarial.py's one-home storms (8 nodes x
+     * 4,096 instructions): 16,398 READ_REQUEST, all at node 0, and 16,393 EVICT_SHARED in the
+     * system (tests/test_routes_model.py test_storm_counts, tests/test_gpu_observers.py). */
     uint32_t tc[7] = {0, 0, 0, 0, 0, 0, 0};                                  /* TC only */
     uint32_t nev = 0;                          /* TR: issue events of the system so far */
     const uint64_t smul = SX ? Ap->sched_seed * 0x9E3779B97F4A7C15ULL : 0;

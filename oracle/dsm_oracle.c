@@ -500,11 +500,11 @@ int orc_run_generated(int np, int dist, uint64_t seed, uint32_t n_instr, uint64_
     return err ? -1 : 0;
 }
 
-int orc_run_packed_ex(int np, const uint16_t *traces, const uint32_t *counts, uint32_t stride,
-                      uint64_t n_sys, uint32_t ring_cap, uint64_t sched_seed,
-                      uint32_t sched_thresh, uint64_t first_sys, dsm_res *res, dsm_rec *dump,
-                      dsm_rec *fin, uint32_t *issue, uint32_t issue_cap, uint32_t *issue_n,
-                      int nthreads) {
+int orc_run_packed_ex_types(int np, const uint16_t *traces, const uint32_t *counts,
+                            uint32_t stride, uint64_t n_sys, uint32_t ring_cap, uint64_t sched_seed,
+                            uint32_t sched_thresh, uint64_t first_sys, dsm_res *res, dsm_rec *dump,
+                            dsm_rec *fin, uint32_t *issue, uint32_t issue_cap, uint32_t *issue_n,
+                            uint32_t *by_type, int nthreads) {
     int err = 0;
     (void)nthreads;
 #pragma omp parallel num_threads(nthreads > 0 ? nthreads : 1) reduction(|:err)
@@ -518,14 +518,27 @@ int orc_run_packed_ex(int np, const uint16_t *traces, const uint32_t *counts, ui
             memset(&x, 0, sizeof x);
             x.seed = sched_seed; x.thresh = sched_thresh; x.sys = first_sys + (uint64_t)i;
             if (issue) { x.ev = issue + (size_t)i * issue_cap; x.ev_cap = issue_cap; }
+            uint64_t bt[DSM_NTYPES] = {0};
             err |= run_one(np, &t, counts + (size_t)i * np, ring_cap, &res[i],
                            dump ? dump + (size_t)i * np : NULL, fin ? fin + (size_t)i * np : NULL,
-                           NULL, ring_mem, &x);
+                           by_type ? bt : NULL, ring_mem, &x);
             if (issue_n) issue_n[i] = x.ev_n;
+            if (by_type)
+                for (int k = 0; k < DSM_NTYPES; ++k) by_type[(size_t)i * DSM_NTYPES + k] = (uint32_t)bt[k];
         }
         free(ring_mem);
     }
     return err ? -1 : 0;
+}
+
+int orc_run_packed_ex(int np, const uint16_t *traces, const uint32_t *counts, uint32_t stride,
+                      uint64_t n_sys, uint32_t ring_cap, uint64_t sched_seed,
+                      uint32_t sched_thresh, uint64_t first_sys, dsm_res *res, dsm_rec *dump,
+                      dsm_rec *fin, uint32_t *issue, uint32_t issue_cap, uint32_t *issue_n,
+                      int nthreads) {
+    return orc_run_packed_ex_types(np, traces, counts, stride, n_sys, ring_cap, sched_seed,
+                                   sched_thresh, first_sys, res, dump, fin, issue, issue_cap,
+                                   issue_n, NULL, nthreads);
 }
 
 void orc_generate(int np, int dist, uint64_t seed, uint32_t n_instr, uint64_t first_sys,

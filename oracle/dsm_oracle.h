@@ -42,6 +42,15 @@ int orc_run_packed_ex(int np, const uint16_t *traces, const uint32_t *counts, ui
                       dsm_rec *fin, uint32_t *issue, uint32_t issue_cap, uint32_t *issue_n,
                       int nthreads);
 
+/* orc_run_packed_ex plus the messages each system handled, by type: by_type
+ * [n_sys][DSM_NTYPES] (may be NULL), written, not accumulated; a row sums to that system's
+ * res.msgs under any schedule, inbox limit and round limit. */
+int orc_run_packed_ex_types(int np, const uint16_t *traces, const uint32_t *counts,
+                            uint32_t stride, uint64_t n_sys, uint32_t ring_cap, uint64_t sched_seed,
+                            uint32_t sched_thresh, uint64_t first_sys, dsm_res *res, dsm_rec *dump,
+                            dsm_rec *fin, uint32_t *issue, uint32_t issue_cap, uint32_t *issue_n,
+                            uint32_t *by_type, int nthreads);
+
 /* Round limit (active rounds before ST_ROUND_LIMIT) of the following runs; 0 = the default
  * DSM_ROUND_LIMIT.  Process-wide (test use). */
 void orc_set_round_limit(uint32_t limit);

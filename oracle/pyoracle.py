@@ -31,6 +31,8 @@ def lib():
         L.orc_run_generated.argtypes = [i32, i32, u64, u32, u64, u64, u32, vp, vp, i32]
         L.orc_run_packed_ex.argtypes = [i32, vp, vp, u32, u64, u32, u64, u32, u64, vp, vp, vp, vp,
                                         u32, vp, i32]
+        L.orc_run_packed_ex_types.argtypes = [i32, vp, vp, u32, u64, u32, u64, u32, u64, vp, vp, vp,
+                                              vp, u32, vp, vp, i32]
         L.orc_generate.argtypes = [i32, i32, u64, u32, u64, u64, vp, vp]
         L.orc_generate.restype = None
         L.orc_format_dump.argtypes = [i32, vp, ctypes.c_char_p, i32]
@@ -82,6 +84,35 @@ def run_packed_ex(np_, traces, counts, sched_seed=0, sched_thresh=LOCKSTEP, firs
                                  _p(evn), nthreads)
     assert rc == 0
     return res, dump, fin, ev, evn
+
+
+def run_packed_ex_types(np_, traces, counts, sched_seed=0, sched_thresh=LOCKSTEP, first_sys=0,
+                        ring_cap=256, nthreads=8, issue=False, round_limit=0):
+    """run_packed_ex plus the messages every system handled by type, under the same schedule,
+    inbox limit and (round_limit > 0: for this call only) round limit:
+    (res, dump, fin, events, n_events, by_type u32 [n, 13]); by_type[i].sum() == res[i].msgs."""
+    traces = np.ascontiguousarray(traces, dtype=np.uint16)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    n, _, stride = traces.shape
+    res = np.zeros(n, dtype=RES_DT)
+    dump = np.zeros((n, np_, 64), dtype=np.uint8)
+    fin = np.zeros((n, np_, 64), dtype=np.uint8)
+    cap = np_ * stride
+    ev = np.zeros((n, cap), dtype=np.uint32) if issue else None
+    evn = np.zeros(n, dtype=np.uint32) if issue else None
+    bt = np.zeros((n, 13), dtype=np.uint32)
+    L = lib()
+    if round_limit:
+        L.orc_set_round_limit(round_limit)
+    try:
+        rc = L.orc_run_packed_ex_types(np_, _p(traces), _p(counts), stride, n, ring_cap, sched_seed,
+                                       sched_thresh, first_sys, _p(res), _p(dump), _p(fin), _p(ev),
+                                       cap, _p(evn), _p(bt), nthreads)
+    finally:
+        if round_limit:
+            L.orc_set_round_limit(0)
+    assert rc == 0
+    return res, dump, fin, ev, evn, bt
 
 
 def issue_lines(events):

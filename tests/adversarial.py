@@ -3,8 +3,13 @@ scenarios.py): a contention ensemble, the hand-derived quirk scenarios tiled int
 and ROUTES, the table of engine routes (hp-assignment-2_amd/csrc/dsm_plan.h) with the evidence
 that each really ran.
 
+OBSERVER_ROUTES is the table of the observer modes beside it (type counts, issue trace and seeded
+stalls combined, at both fast rings and with limits that end systems), and storm() the one-home
+inputs for the type counters' field width.
+
 tests/test_routes_model.py carries the CPU certificate of these inputs (micro-op rows reached,
-ser_macro cases, status mix, digest); tests/test_gpu_routes.py drives them through every route.
+ser_macro cases, status mix, digest, the observer routes' limits); tests/test_gpu_routes.py drives
+them through every route, tests/test_gpu_observers.py through every observer route.
 """
 import hashlib
 
@@ -263,6 +268,96 @@ ROUTES = {
                      resume_mode=0, budget_rounds=448, budget_log2=3, ser_cap=0, ring_cap=12),
         counters=("resumed", "ff_sample_instrs")),
 }
+
+
+# ---- observer routes ------------------------------------------------------------------------
+# The MODE of a run is M_TC | M_TR | M_SX of its settings (type counts 1, issue trace 2, seeded
+# stalls 4); each MODE is its own sim_kernel per node count, fast ring (4, 12) and entry, and its
+# own 256-deep re-run kernel, all with run-time round and inbox limits.  ROUTES holds MODE 2 and
+# MODE 4 at ring 12; OBSERVER_ROUTES the other non-empty subsets at ring 12, all seven at ring 4,
+# and four cases in which a limit ends systems while the observers run.  Entries as in ROUTES;
+# `compare` names the oracle run's schedule ("lockstep" / "stalls"), what is compared follows
+# from the engine's flags (observers()).
+#
+# The limits are chosen with the oracle and certified by tests/test_routes_model.py on the
+# contention ensemble: under the route's schedule the round limit ends between a tenth and nine
+# tenths of the systems with ROUND_LIMIT at both node counts (measured: 2^6 in lock-step rounds
+# 39% at 4 nodes, 46% at 8; 2^7 under the stalls 41% / 48%), and an inbox limit of 3 ends
+# thousands with RING_OVERFLOW.  The round limit of MODE 7 runs at ring 4, so that the re-run
+# kernel meets it too: its systems restart from round 1 there.
+OBS_ROUND_LOG2 = {"lockstep": 6, "stalls": 7}
+OBS_INBOX = 3
+ROUND_LIMIT_SHARE = (0.1, 0.9)
+
+
+def _observer(tc, tr, sx, ring, limit=0, inbox=0):
+    mode = (1 if tc else 0) | (2 if tr else 0) | (4 if sx else 0)
+    engine = {}
+    if ring != 12:
+        engine["ring_cap"] = ring
+    if tc:
+        engine["type_counts"] = True
+    if tr:
+        engine["issue_trace"] = True
+    setters = [("set_schedule", (STALL_SEED, STALL_THRESH))] if sx else []
+    info = dict(kernels=_one(mode), ff_picked=int(mode == 1), budget_mode=mode, ring_cap=ring, **_ONE_PASS)
+    if limit:
+        setters.append(("set_round_limit", (limit,)))
+        info["round_limit_log2"] = limit
+    if inbox:
+        setters.append(("set_inbox_limit", (inbox,)))
+    return _route(engine=engine, setters=setters, info=info, zero=("resumed", "ser_macro_steps"),
+                  compare="stalls" if sx else "lockstep")
+
+
+def _observer_name(tc, tr, sx):
+    return "_".join(n for n, on in (("tc", tc), ("tr", tr), ("sx", sx)) if on)
+
+
+OBSERVER_ROUTES = {}
+for _ring in (12, 4):
+    for _m in range(1, 8):
+        if _ring == 12 and _m in (2, 4):       # ROUTES: issue_trace, seeded_stalls
+            continue
+        _f = (bool(_m & 1), bool(_m & 2), bool(_m & 4))
+        OBSERVER_ROUTES[_observer_name(*_f) + f"_ring{_ring}"] = _observer(*_f, _ring)
+OBSERVER_ROUTES.update({
+    "tc_tr_round_limit": _observer(True, True, False, 12, limit=OBS_ROUND_LOG2["lockstep"]),
+    "tc_tr_sx_round_limit_ring4": _observer(True, True, True, 4, limit=OBS_ROUND_LOG2["stalls"]),
+    "tc_sx_inbox_limit": _observer(True, False, True, 12, inbox=OBS_INBOX),
+    "tc_tr_sx_inbox_limit": _observer(True, True, True, 12, inbox=OBS_INBOX),
+})
+assert len(OBSERVER_ROUTES) == 16
+
+
+def observers(route):
+    """-> (type counts, issue trace, stalls, round limit in rounds or 0, inbox limit or 256) of a
+    route's settings: what its oracle run takes and what of it is compared."""
+    s = dict(route["setters"])
+    limit = s.get("set_round_limit", (0,))[0]
+    return (bool(route["engine"].get("type_counts")), bool(route["engine"].get("issue_trace")),
+            "set_schedule" in s, (1 << limit) if limit else 0, s.get("set_inbox_limit", (256,))[0])
+
+
+# ---- the type counters' field width ---------------------------------------------------------
+# One system whose nodes all work on one home (node 0): the most messages of one type one node
+# handles.  tests/test_routes_model.py pins the counts the oracle gives.
+STORM_INSTR = 4096
+STORMS = ("read_two_lines", "write_one_line", "write_two_lines")
+
+
+def storm(name, np_=8):
+    """-> (traces u16 [1, np, 4096], counts u32 [1, np]): every node alternating RD 0x00 / RD 0x04
+    (both at home 0, cache index 0: every miss evicts the other), every node WR 0x00, or every
+    node alternating WR 0x00 / WR 0x04.  Written values: the instruction index + node."""
+    i = np.arange(STORM_INSTR)
+    alt = ((i & 1) * 0x04) << 8
+    t = np.zeros((1, np_, STORM_INSTR), dtype=np.uint16)
+    for nd in range(np_):
+        val = (i + nd) & 0xFF
+        t[0, nd] = {"read_two_lines": alt, "write_one_line": 0x8000 | val,
+                    "write_two_lines": 0x8000 | alt | val}[name]
+    return t, np.full((1, np_), STORM_INSTR, dtype=np.uint32)
 
 
 def route_info(route, np_, ff=False):

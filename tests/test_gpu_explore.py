@@ -106,9 +106,13 @@ def test_gpu_exploration_with_inbox_overflow_rerun(dsm):
     n = 8192
     tr, cn = orc.generate(8, "uniform", 5, 1024, 0, n)
     ores, _, _, _, _ = orc.run_packed_ex(8, tr, cn, sched_seed=5, sched_thresh=0xA000)
+    obt = orc.run_packed_ex_types(8, tr, cn, sched_seed=5, sched_thresh=0xA000)[5]
     with dsm.Engine(8, 1024, ring_cap=4, type_counts=True) as eng:
         eng.set_schedule(5, 0xA000)
         res, cnt = eng.run_packed(tr, cn)
     assert cnt["overflow_reruns"] > 0
     assert np.array_equal(res_to_u64(res), res_to_u64(ores))
     assert cnt["msgs"] == int(ores["msgs"].sum())
+    # the type counts of MODE 5: a stalled lane adds nothing, a re-run system counts once
+    by_type = [cnt[f"msgs_{t}"] for t in dsm.TYPE_NAMES]
+    assert by_type == obt.sum(axis=0, dtype=np.uint64).tolist() and sum(by_type) == cnt["msgs"]

@@ -19,7 +19,8 @@ packed command):
       for it (scenarios.notice_and_forward_meet_at_one_node), which the tiled scenarios carry;
   (e) 4,047 completed / 12,337 deadlocked at 8 nodes, 7,672 / 8,712 at 4; 8 systems at 8 nodes
       pass a 12-deep inbox (RING_OVERFLOW at inbox 12);
-  (f) the sha256 of traces and counts, asserted by tests/test_gpu_routes.py too."""
+  (f) the sha256 of traces and counts, asserted by tests/test_gpu_routes.py too;
+  (g)-(i), at the end of the file: the observer routes of tests/test_gpu_observers.py."""
 import json
 import os
 import subprocess
@@ -247,6 +248,7 @@ FF = {"FF_OFF": 0, "FF_ON": 1, "FF_AUTO": 2}
 def _plan_args(route, np_):
     a = {"np": np_, "n": adv.N_CONTENTION, "ring": route["engine"].get("ring_cap", 12),
          "tr": int(bool(route["engine"].get("issue_trace"))),
+         "tc": int(bool(route["engine"].get("type_counts"))),
          "serial": int(route["env"]["DSM_SERIAL"]), "lone": int(route["env"].get("DSM_LONE", 8)),
          "lone_min": int(route["env"].get("DSM_LONE_MIN", 160)),
          "ffb": int(route["env"].get("DSM_FF_BUDGET_ROUNDS", 448))}
@@ -306,3 +308,137 @@ def test_routes_cover_the_launch_lists(plan_model):
               "order", "ser0", "ser1", "scan", "rerun0", "rerun2", "rerun4",
               ("form", 0), ("form", 1), ("form", 2), ("form", 3)):
         assert k in seen, (k, sorted(map(str, seen)))
+
+
+# ---- observer routes (adversarial.OBSERVER_ROUTES, tests/test_gpu_observers.py) ---------------
+# Measured on contention(np, SEED 20, 16,384 systems), 4 / 8 nodes:
+#   (g) ROUND_LIMIT at 2^6 lock-step rounds ends 39% / 46% of the systems, at 2^7 rounds under
+#       the stall schedule 41% / 48%;
+#   (h) RING_OVERFLOW at inbox 4: 278 / 9,259 in lock-step rounds, 624 / 8,993 under the stalls;
+#       at inbox 3 under the stalls 4,274 / 12,258;
+#   (i) the read storm (adversarial.storm) issues 16,398 instructions before it deadlocks and
+#       all 16,398 READ_REQUEST are handled at node 0, the one home, and so are the EVICT_SHARED
+#       (16,393 in the system, the home's notices to a last sharer among them): the largest
+#       count of one type at one node found; a 16-bit field holds it four times over.
+def _plan(plan_model, route, np_, verdict=0):
+    r = subprocess.run([plan_model, "info", f"verdict={verdict}"] +
+                       [f"{k}={v}" for k, v in _plan_args(route, np_).items()],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    return json.loads(r.stdout)
+
+
+@pytest.mark.parametrize("name", list(adv.OBSERVER_ROUTES))
+def test_observer_route_table_is_the_plan(plan_model, name):
+    route = adv.OBSERVER_ROUTES[name]
+    tc, tr, sx, _, _ = adv.observers(route)
+    mode = tc | tr << 1 | sx << 2
+    for np_ in (4, 8):
+        got = _plan(plan_model, route, np_)
+        want = adv.route_info(route, np_)
+        assert {k: got[k] for k in want} == want, (np_, got)
+        assert want["kernels"] == f"run=sim_kernel<{np_}, {want['ring_cap']}, 4, false, {mode}, 5>"
+        assert got["launches"] == f"sim{mode}/0 rerun{mode} digest" and not got["pair"]
+        assert _plan(plan_model, route, np_, 1) == got
+
+
+def test_observer_routes_are_the_subsets():
+    """Every non-empty subset of the three observers at ring 12 and at ring 4, ROUTES' two left
+    out; the limit cases are MODE 3 and 7 (round limit), 5 and 7 (inbox limit below the ring)."""
+    plain, limits = {}, []
+    for name, route in adv.OBSERVER_ROUTES.items():
+        tc, tr, sx, limit, inbox = adv.observers(route)
+        key = (tc | tr << 1 | sx << 2, route["info"]["ring_cap"])
+        if limit or inbox != 256:
+            limits.append((key[0], bool(limit), inbox))
+            assert inbox == 256 or inbox < key[1]
+        else:
+            assert key not in plain
+            plain[key] = name
+    have = {(2, 12), (4, 12)}
+    for r in ("issue_trace", "seeded_stalls"):
+        tc, tr, sx, limit, inbox = adv.observers(adv.ROUTES[r])
+        assert (tc | tr << 1 | sx << 2, adv.ROUTES[r]["info"]["ring_cap"]) in have and not limit and inbox == 256
+    assert set(plain) | have == {(m, r) for m in range(1, 8) for r in (4, 12)} and len(plain) == 12
+    assert sorted(limits) == [(3, True, 256), (5, False, 3), (7, False, 3), (7, True, 256)]
+
+
+def test_observer_modes_cover_the_launch_lists(plan_model):
+    """Over ROUTES and OBSERVER_ROUTES every observer MODE's fast kernel and re-run kernel is
+    launched, at either node count, and at both rings."""
+    for np_ in (4, 8):
+        seen = set()
+        for route in list(adv.ROUTES.values()) + list(adv.OBSERVER_ROUTES.values()):
+            got = _plan(plan_model, route, np_)
+            seen |= {(k, got["ring_cap"]) for k in got["launches"].split()}
+        for m in range(1, 8):
+            for ring in (4, 12):
+                assert (f"sim{m}/0", ring) in seen and (f"rerun{m}", ring) in seen, (np_, m, ring)
+
+
+@pytest.fixture(scope="module")
+def observer_oracle():
+    """The oracle on the contention ensemble under a route's schedule and limits, at an inbox
+    depth: (np, stalls, round limit, inbox) -> results."""
+    cache, ens = {}, {}
+
+    def get(np_, sx, limit, inbox):
+        key = (np_, sx, limit, inbox)
+        if key not in cache:
+            if np_ not in ens:
+                ens[np_] = adv.contention(np_, adv.SEED, adv.N_CONTENTION)[:2]
+            sched = dict(sched_seed=adv.STALL_SEED, sched_thresh=adv.STALL_THRESH) if sx else {}
+            cache[key] = pyoracle.run_packed_ex_types(np_, *ens[np_], ring_cap=inbox, round_limit=limit,
+                                                      nthreads=8, **sched)[0]
+        return cache[key]
+    return get
+
+
+@pytest.mark.parametrize("np_", [4, 8])
+def test_observer_limits_bite(observer_oracle, np_):
+    """(g), (h): conditions on the input -- each limit case ends systems by its limit, and every
+    ring-4 case hands systems to the re-run kernel."""
+    n = adv.N_CONTENTION
+    for name, route in adv.OBSERVER_ROUTES.items():
+        _, _, sx, limit, inbox = adv.observers(route)
+        ring = route["info"]["ring_cap"]
+        st = observer_oracle(np_, sx, limit, inbox)["status"] & 0xFF
+        nlim, novf = int((st == 4).sum()), int((st == 2).sum())
+        fast = observer_oracle(np_, sx, limit, min(ring, inbox))["status"] & 0xFF
+        handed = int((fast == 2).sum())
+        print(name, np_, "ROUND_LIMIT", nlim, "RING_OVERFLOW", novf, "handed to the re-run", handed)
+        if limit:
+            lo, hi = adv.ROUND_LIMIT_SHARE
+            assert lo * n <= nlim <= hi * n, (name, nlim)
+            assert limit == 1 << adv.OBS_ROUND_LOG2[route["compare"]]
+        else:
+            assert nlim == 0
+        if inbox != 256:
+            assert novf > 0 and inbox == adv.OBS_INBOX, name
+        else:
+            assert novf == 0
+        if ring == 4:
+            assert handed > 0, name
+            if limit:       # ... and some of those meet the round limit in the re-run kernel
+                assert int(((fast == 2) & (st == 4)).sum()) > 0, name
+
+
+def test_storm_counts():
+    """(i): the largest count of one message type at one node, for the 16-bit fields of the
+    kernel's per-lane type counters (dsm_engine.hip, tc[7])."""
+    top = {}
+    for name in adv.STORMS:
+        tr, cn = adv.storm(name)
+        assert tr.shape == (1, 8, 4096) and int(((tr >> 12) & 7).max()) == 0     # one home
+        for sx in (False, True):
+            sched = dict(sched_seed=adv.STALL_SEED, sched_thresh=adv.STALL_THRESH) if sx else {}
+            res, _, _, _, _, bt = pyoracle.run_packed_ex_types(8, tr, cn, **sched)
+            assert int(bt[0].sum()) == int(res[0]["msgs"])
+            print(name, "stalls" if sx else "lockstep", "instrs", int(res[0]["instrs"]),
+                  "status", int(res[0]["status"]) & 0xFF, dict(zip(range(13), bt[0].tolist())))
+            top[(name, sx)] = (int(res[0]["instrs"]), bt[0])
+    instrs, bt = top[("read_two_lines", False)]
+    assert instrs == 16398 and int(bt[0]) == 16398 and int(bt[11]) == 16393
+    assert int(bt[0]) >= 16000
+    # every count of one type, at all nodes together, stays far below a 16-bit field
+    assert max(int(b.max()) for _, b in top.values()) < 1 << 15
