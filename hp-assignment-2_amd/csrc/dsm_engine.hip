@@ -1360,6 +1360,18 @@ constexpr int SER_MACRO = SER_MACRO_DEF;   /* lone-node macro-steps per iteratio
 #ifndef SER_HT
 #define SER_HT 32           /* ... or iterations the oldest finished lane has waited */
 #endif
+/* the run phase (dsm_serial.h ser_solo) in front of each refill period's iterations: taken by a
+ * wave when at least SER_SOLO_MIN of 64 of its running lanes are eligible; 0: the loop without
+ * it, exactly (A/B through tools/build_variant.sh) */
+#ifndef SER_SOLO
+#define SER_SOLO 1
+#endif
+#ifndef SER_SOLO_MIN
+#define SER_SOLO_MIN 48     /* C3 64 / 56 / 48 / 32: 32.45 / 31.97 / 32.30 / 32.29 ms; C5 21.98 / 21.86 / 21.80 / 21.81 */
+#endif
+#ifndef SER_SOLO_HW
+#define SER_SOLO_HW 4       /* a run's weight in SER_HT's iterations */
+#endif
 
 template <int W>
 struct LdsCol {
@@ -1580,6 +1592,12 @@ ser_kernel(const SimArgs *Ap) {
         r.E = r.nz;
         r.A = r.nz | r.iss;
         ser_cache_clear(cc);
+        if (SER_SOLO && !CAP && serfmt && tn != 0xFFu) {
+            /* a lone system: its node's words into the register cache, so that the first
+             * period's gate already finds the lane eligible */
+            cc.ct = m.ld(S_CT + tn); cc.la = m.ld(S_LA + tn); cc.lv = m.ld(S_LV + tn);
+            cc.node = tn;
+        }
         if (r.A == 0u) {
             r.st = (r.dmp == NPM) ? SS_COMPLETED : SS_DEADLOCKED;
             return SR_DONE;
@@ -1716,17 +1734,75 @@ ser_kernel(const SimArgs *Ap) {
      * the wave have finished, or the oldest has waited SER_HT iterations, or no running
      * system is left in the wave; then they hand over together (wave-uniform) */
     uint32_t hwait = 0;
+    /* the run phase (SER_SOLO): a refill period starts with the gate -- a lane is eligible when
+     * it runs a quiet-lone system whose node's words are in the register cache and whose next
+     * instruction's chunk is in cur (after the nx rotation, if due) -- and, when SER_SOLO_MIN
+     * of 64 of the wave's running lanes are eligible (one ballot, wave-uniform), one ser_solo
+     * run over the rest of each eligible lane's chunk.  In the iterations after a run
+     *   - a lane that consumed its chunk rests (`rest`): its next chunk comes with the refill;
+     *   - a lane that stopped mid-run, and a lane the gate left out, takes the iterations it
+     *     needs to get its instruction applied (ser_macro, or ser_step until the system is
+     *     quiet again, or ended) and rests after its first macro-step: its node's words are in
+     *     the register cache then, and it enters the next run, mid-chunk, and is aligned
+     *     after it;
+     *   - finished lanes wait for the batched hand-over as before, a run counting SER_SOLO_HW
+     *     iterations of SER_HT;
+     * and the iterations end as soon as every running lane rests: after a run that consumed
+     * every lane's chunk they cost two ballots.  cur / nx / pf stay two chunks ahead as
+     * before: a period still consumes at most one chunk per lane.  ser_iterations counts the
+     * iterations taken, a run as one. */
+    uint64_t pb_runs = 0, pb_steps = 0, pb_idle = 0, pb_cyc = 0;      /* SER_PROBE: lane 0's */
     for (;;) {
+        bool taken = false, rest = false;
 #pragma unroll 1
         for (int k = 0; k < SER_RF; ++k) {
+            bool ran_now = false, gen = true;
+            if (SER_SOLO && !CAP) {
+                if (k == 0) {
+                    uint64_t ts0 = 0;
+                    if (SER_PROBE >= 2) ts0 = __builtin_amdgcn_s_memtime();
+                    const bool run = live && v == SR_RUN;
+                    const bool ql = run && ser_quiet_lone(r, lim_rsh);
+                    const uint32_t sn = ql ? dsms::s_ctz(r.A) : 0xFEu;
+                    const uint32_t c = cc.ct >> (SC_IP + 3u);
+                    const bool hotq = ql & (cc.node == sn) & (tn == sn);
+                    const bool rot = hotq & (tci + 1u == c) & nxv;
+                    cur.x = rot ? nx.x : cur.x; cur.y = rot ? nx.y : cur.y;
+                    cur.z = rot ? nx.z : cur.z; cur.w = rot ? nx.w : cur.w;
+                    nxv = nxv & !rot;
+                    tci = rot ? c : tci;
+                    const bool elig = hotq & (tci == c);
+                    const uint32_t ne = (uint32_t)__builtin_popcountll(__ballot(elig));
+                    const uint32_t nr = (uint32_t)__builtin_popcountll(__ballot(run));
+                    if (ne != 0u && ne * 64u >= nr * (uint32_t)SER_SOLO_MIN) {
+                        uint32_t ns = 0;
+                        if (elig) ns = ser_solo<NP>(m, r, cc, cur.x, cur.y, cur.z, cur.w, lim_rsh);
+                        nmac += ns;
+                        taken = ran_now = true;
+                        rest = elig & (ns != 0u) & (((cc.ct >> SC_IP) & 7u) == 0u);
+                        iters += 1u;
+                        if (SER_PROBE) {
+                            uint32_t t = ns;
+                            for (int o = 1; o < 64; o <<= 1) t += __shfl_xor(t, o, 64);
+                            pb_runs += 1u; pb_steps += t; pb_idle += 8u * nr - t;
+                            if (SER_PROBE >= 2) pb_cyc += __builtin_amdgcn_s_memtime() - ts0;
+                        }
+                    }
+                }
+                if (taken) {
+                    gen = __ballot(live && v == SR_RUN && !rest) != 0ull;
+                    if (!gen && !ran_now) break;
+                }
+                iters += gen ? 1u : 0u;
+            }
             /* a lone node's whole transaction at once (ser_macro), else one node-action */
             bool mac = false;
             uint64_t tp0 = 0, tp1 = 0, tp2 = 0;
             if (SER_PROBE >= 2) tp0 = __builtin_amdgcn_s_memtime();
-            if (!CAP) {
+            if (!CAP && gen) {
 #pragma unroll
                 for (int j = 0; j < SER_MACRO; ++j) {
-                    const bool q = live && v == SR_RUN && ser_quiet_lone(r, lim_rsh) && (j == 0 || mac);
+                    const bool q = live && v == SR_RUN && !rest && ser_quiet_lone(r, lim_rsh) && (j == 0 || mac);
                     bool did = false;
                     bool nohave = false;
                     if (SER_PROBE && q) {         /* the instruction not at hand in registers */
@@ -1768,6 +1844,7 @@ ser_kernel(const SimArgs *Ap) {
                 }
                 /* a macro-step that ended the system (the dead-end forward): quiescent */
                 if (mac && r.A == 0u) v = SR_DONE;
+                if (SER_SOLO) rest = rest | (taken & mac);
             }
             if (SER_PROBE) {
                 const uint64_t gm = __ballot(live && v == SR_RUN && !mac), mm = __ballot(mac);
@@ -1781,7 +1858,7 @@ ser_kernel(const SimArgs *Ap) {
                 }
             }
             if (SER_PROBE >= 2) tp1 = __builtin_amdgcn_s_memtime();
-            if (live && v == SR_RUN && !mac && (k % SER_GE) == 0) {
+            if (live && v == SR_RUN && !mac && gen && !rest && (k % SER_GE) == 0) {
                 v = ser_step<NP, S_QN, CAP>(m, r, T, fetch, on_dump, lim_rsh, cap);
                 ser_cache_clear(cc);
             }
@@ -1796,7 +1873,7 @@ ser_kernel(const SimArgs *Ap) {
                 if (fin) {
                     hgo = (uint32_t)__builtin_popcountll(fin) >= (uint32_t)SER_HB ||
                           hwait >= (uint32_t)SER_HT || fin == __ballot(live);
-                    hwait = hgo ? 0u : hwait + 1u;
+                    hwait = hgo ? 0u : hwait + (gen ? 1u : 0u) + (ran_now ? (uint32_t)SER_SOLO_HW : 0u);
                 }
             } else {
                 hgo = true;
@@ -1843,6 +1920,7 @@ ser_kernel(const SimArgs *Ap) {
                 if (SER_PROBE >= 3) { __builtin_amdgcn_s_waitcnt(0); th2 = __builtin_amdgcn_s_memtime(); }
                 live = nl;
                 sys = ns;
+                rest = false;
                 v = live ? start() : SR_RUN;
                 if (SER_PROBE >= 3) {    /* hand-over cycles: finish, claim, start (lowest lane) */
                     __builtin_amdgcn_s_waitcnt(0);
@@ -1861,12 +1939,13 @@ ser_kernel(const SimArgs *Ap) {
                 atomicAdd(&s_cnt[6], tp2 - tp1);
                 atomicAdd(&s_cnt[7], tp3 - tp2);
             }
+            if (!gen) break;                 /* a run alone: every running lane rests */
         }
         uint64_t tr0 = 0;
         if (SER_PROBE >= 2) tr0 = __builtin_amdgcn_s_memtime();
         refill();
         (void)tr0;
-        iters += SER_RF;
+        if (!(SER_SOLO && !CAP)) iters += SER_RF;
         if (__ballot(live) == 0) break;
     }
 #if SIM_TAILPROBE == 2
@@ -1890,6 +1969,14 @@ ser_kernel(const SimArgs *Ap) {
     if (lane == 0) {
         atomicAdd(&s_cnt[K_WROUNDS], (unsigned long long)iters);
         atomicAdd(&Ap->counters[K_SERIT], (unsigned long long)iters);
+        if (SER_PROBE && SER_SOLO && !CAP && !SIM_TAILPROBE) {
+            /* probe build: runs, steps taken in runs, lane-steps idle in runs (8 per running
+             * lane less the steps), and at SER_PROBE >= 2 the runs' cycles */
+            atomicAdd(&Ap->counters[K_SERPROBE], (unsigned long long)pb_runs);
+            atomicAdd(&Ap->counters[K_SERPROBE + 1], (unsigned long long)pb_steps);
+            atomicAdd(&Ap->counters[K_SERPROBE + 2], (unsigned long long)pb_idle);
+            atomicAdd(&Ap->counters[K_SERPROBE + 3], (unsigned long long)pb_cyc);
+        }
 #if SIM_TAILPROBE
         /* probe build: when the serial pass's waves end, ms after the wave started -- slot 34:
          * before 11 ms, 35..38: [10 + k, 11 + k) for k = 1..4, 39: 15 ms and later */
@@ -2377,6 +2464,9 @@ static const char *build_variant() {
     add("SER_HT", SER_HT, 32);
     add("SER_RF_DEF", SER_RF_DEF, 8);
     add("SER_MACRO_DEF", SER_MACRO_DEF, 1);
+    add("SER_SOLO", SER_SOLO, 1);
+    add("SER_SOLO_MIN", SER_SOLO_MIN, 48);
+    add("SER_SOLO_HW", SER_SOLO_HW, 4);
     add("FF_LONG", FF_LONG, 1);
     add("FF_LONG_U", FF_LONG_U, 8);
     add("SER_DEAD_FWD", SER_DEAD_FWD, 1);

@@ -73,6 +73,14 @@
 #define SER_COUNT_MACRO(hit, upg, ev, mod, notice, notice_req_home, notice_vic_home, fwd, dead, wr, fan) ((void)0)
 #endif
 
+/* ser_solo's ways out of a run (cause: SOLO_*), at half-word j of the chunk, and its entries */
+#ifndef SER_COUNT_SOLO_STOP
+#define SER_COUNT_SOLO_STOP(cause, j) ((void)0)
+#endif
+#ifndef SER_COUNT_SOLO_ENTRY
+#define SER_COUNT_SOLO_ENTRY(j0) ((void)0)
+#endif
+
 #include "dsm_table.h"
 
 namespace dsms {
@@ -447,46 +455,25 @@ struct SCache {
 };
 DSM_HD void ser_cache_clear(SCache &c) { c.ct = c.la = c.lv = 0u; c.node = 0xFFu; }
 
-/* stamp(i): diagnostic hook (the kernel's SER_PROBE 4 build times the step's phases; else a
- * no-op) */
-template <int NP, class M, class F, class R, class P>
-DSM_HD bool ser_macro(M &m, SReg &r, SCache &cc, F &&fetch, R &&on_dump, P &&stamp) {
-    constexpr uint32_t NPM = (1u << NP) - 1u;
-    const uint32_t n = s_ctz(r.A), bit = 1u << n;
-    const bool hot = cc.node == n;
-    uint32_t ct = cc.ct;
-    if (s_any(!hot)) {
-        const uint32_t x = m.ld(S_CT + n);
-        ct = hot ? ct : x;
-    }
-    const uint32_t ip = ct >> SC_IP;
-    if (ip >= s_ni(r, n)) {
-        /* the trace is done: the dump (:688-697), the round's one action; then no node can
-         * act and the system is quiescent (the caller ends it when r.A is empty) */
-        if (!SER_DUMP) return false;
-        ct |= SC_DUMPED;
-        m.st(S_CT + n, ct);
-        r.dmp |= bit;
-        on_dump(n);                          /* printProcessorState(threadId, node), :695 */
-        r.iss &= ~bit;
-        r.A = r.iss;
-        r.rounds += 1u;
-        r.E = 0u;
-        r.st = (r.dmp == NPM) ? SS_COMPLETED : SS_DEADLOCKED;
-        cc.ct = ct; cc.node = n;
-        return true;
-    }
-    uint32_t ins;
-    if (!fetch(n, ip, ins)) return false;                     /* not at hand: ser_step loads it */
-    stamp(0);
+/* ---- the transaction's front, shared by ser_macro and ser_solo ---------------------------
+ * Instruction `ins` of the lone node n (bit = 1 << n) whose control, line-address and
+ * line-value words are ct, laW, lvW: the line it maps to, the victim's and the request's home
+ * words (four LDS loads, all issued at once), the eviction applied at the victim's home
+ * (:498-561) and forwarded to the request's home when they share a word, and what the
+ * request's home would send besides its reply (fwd, fan) or the eviction's home besides
+ * nothing (notice). */
+struct STxn {
+    uint32_t a, wr, val, h, b, sh8, lsh, La, Lv, Ls;
+    bool hit, upg, miss, ev, mod;
+    uint32_t vh, wV, wH, mbV2, dsV2, mbH, dsH, hh, shb, memH, bvH, dH;
+    bool notice, selfn, fwd, fan;
+    uint32_t x, owner, others;
+};
+template <class M, class P>
+DSM_HD void ser_txn_front(M &m, STxn &t, uint32_t ins, uint32_t ct, uint32_t laW, uint32_t lvW,
+                          uint32_t n, uint32_t bit, P &&stamp) {
     const uint32_t a = (ins >> 8) & 0x7Fu, wr = ins >> 15, val = ins & 0xFFu;
     const uint32_t h = a >> 4, b = a & 15u, idx = a & 3u, sh8 = 8u * idx;
-    uint32_t laW = cc.la, lvW = cc.lv;
-    if (s_any(!hot)) {
-        const uint32_t x = m.ld(S_LA + n), y = m.ld(S_LV + n);
-        laW = hot ? laW : x;
-        lvW = hot ? lvW : y;
-    }
     const uint32_t La = (laW >> sh8) & 0xFFu, Lv = (lvW >> sh8) & 0xFFu;
     const uint32_t lsh = SC_LS + 2u * idx, Ls = (ct >> lsh) & 3u;          /* M0 E1 S2 I3 */
     const bool hit = (La == a) & (Ls != 3u);                   /* :608, :635 */
@@ -538,6 +525,84 @@ DSM_HD bool ser_macro(M &m, SReg &r, SCache &cc, F &&fetch, R &&on_dump, P &&sta
      * (:366-373). */
     const bool fwd = miss & (dH == 0u) & (owner != n);
     const bool fan = (miss | upg) & (dH == 1u) & (others != 0u) & ((wr != 0u) | upg);
+    t.a = a; t.wr = wr; t.val = val; t.h = h; t.b = b; t.sh8 = sh8; t.lsh = lsh;
+    t.La = La; t.Lv = Lv; t.Ls = Ls;
+    t.hit = hit; t.upg = upg; t.miss = miss; t.ev = ev; t.mod = mod;
+    t.vh = vh; t.wV = wV; t.wH = wH; t.mbV2 = mbV2; t.dsV2 = dsV2; t.mbH = mbH; t.dsH = dsH;
+    t.hh = hh; t.shb = shb; t.memH = memH; t.bvH = bvH; t.dH = dH;
+    t.notice = notice; t.selfn = selfn; t.fwd = fwd; t.fan = fan;
+    t.x = x; t.owner = owner; t.others = others;
+}
+/* the home's directory entry and memory after the request (:188-236, :298-328, :375-435):
+ * READ_REQUEST U -> EM {n}, S -> S + n, EM at n unchanged, EM at o -> S {o, n};
+ * WRITE_REQUEST writes memory first, then U / S -> EM {n}, EM at n unchanged, EM at o ->
+ * EM {n}; UPGRADE -> EM {n}.  A flush then writes o's value to memory (FLUSH_INVACK also
+ * EM {n}: unchanged).  Then the requester's line (:243-246, :291-294, :445-447, :334-336,
+ * :491-494; a write hit :642-643, :656-657).  fwd / dead / vO: the forward, its dead end and
+ * the value the owner flushes (ser_solo: none). */
+struct SHome {
+    bool req;
+    uint32_t nmemH, nbvH, ndH, nLv, nLs;
+};
+DSM_HD void ser_txn_home(SHome &o, const STxn &t, uint32_t bit, bool fwd, bool dead, uint32_t vO) {
+    const bool miss = t.miss, upg = t.upg;
+    const uint32_t wr = t.wr, dH = t.dH, bvH = t.bvH;
+    const bool rdq = miss & (wr == 0u), req = miss | upg;
+    const bool keep = miss & (dH == 0u) & !fwd;                 /* EM at the requester */
+    const bool excl = !(rdq & (dH == 1u)) & !fwd;               /* REPLY_RD's bitVector == 2 */
+    o.req = req;
+    o.nmemH = (fwd & !dead) ? vO : ((miss & (wr != 0u)) ? t.val : t.memH);
+    o.nbvH = rdq ? (dH == 2u ? bit : (((dH == 1u) | fwd) ? (bvH | bit) : bvH)) : (keep ? bvH : bit);
+    o.ndH = rdq ? (dH == 2u ? 0u : (fwd ? 1u : dH)) : 0u;
+    o.nLv = dead ? 0u : (fwd ? vO : (wr ? t.val : (miss ? t.memH : t.Lv)));
+    o.nLs = dead ? 3u : (wr ? 0u : (miss ? (excl ? 1u : 2u) : t.Ls));
+}
+
+/* stamp(i): diagnostic hook (the kernel's SER_PROBE 4 build times the step's phases; else a
+ * no-op) */
+template <int NP, class M, class F, class R, class P>
+DSM_HD bool ser_macro(M &m, SReg &r, SCache &cc, F &&fetch, R &&on_dump, P &&stamp) {
+    constexpr uint32_t NPM = (1u << NP) - 1u;
+    const uint32_t n = s_ctz(r.A), bit = 1u << n;
+    const bool hot = cc.node == n;
+    uint32_t ct = cc.ct;
+    if (s_any(!hot)) {
+        const uint32_t x = m.ld(S_CT + n);
+        ct = hot ? ct : x;
+    }
+    const uint32_t ip = ct >> SC_IP;
+    if (ip >= s_ni(r, n)) {
+        /* the trace is done: the dump (:688-697), the round's one action; then no node can
+         * act and the system is quiescent (the caller ends it when r.A is empty) */
+        if (!SER_DUMP) return false;
+        ct |= SC_DUMPED;
+        m.st(S_CT + n, ct);
+        r.dmp |= bit;
+        on_dump(n);                          /* printProcessorState(threadId, node), :695 */
+        r.iss &= ~bit;
+        r.A = r.iss;
+        r.rounds += 1u;
+        r.E = 0u;
+        r.st = (r.dmp == NPM) ? SS_COMPLETED : SS_DEADLOCKED;
+        cc.ct = ct; cc.node = n;
+        return true;
+    }
+    uint32_t ins;
+    if (!fetch(n, ip, ins)) return false;                     /* not at hand: ser_step loads it */
+    stamp(0);
+    uint32_t laW = cc.la, lvW = cc.lv;
+    if (s_any(!hot)) {
+        const uint32_t x = m.ld(S_LA + n), y = m.ld(S_LV + n);
+        laW = hot ? laW : x;
+        lvW = hot ? lvW : y;
+    }
+    STxn t;
+    ser_txn_front(m, t, ins, ct, laW, lvW, n, bit, stamp);
+    const uint32_t a = t.a, wr = t.wr, val = t.val, h = t.h, sh8 = t.sh8, lsh = t.lsh, La = t.La;
+    const bool hit = t.hit, upg = t.upg, miss = t.miss, ev = t.ev;
+    const uint32_t vh = t.vh, wV = t.wV, wH = t.wH, mbV2 = t.mbV2, dsV2 = t.dsV2, mbH = t.mbH, dsH = t.dsH;
+    const uint32_t hh = t.hh, shb = t.shb, bvH = t.bvH, dH = t.dH, x = t.x, owner = t.owner, others = t.others;
+    const bool notice = t.notice, selfn = t.selfn, fwd = t.fwd, fan = t.fan;
     const uint32_t o = owner & 7u;
     bool oflush = false;
     uint32_t ctO = 0u, vO = 0u;                                 /* o's control word, the value it flushes */
@@ -567,19 +632,12 @@ DSM_HD bool ser_macro(M &m, SReg &r, SCache &cc, F &&fetch, R &&on_dump, P &&sta
                       notice & ((x == h) | (x == vh)) & !SER_NOTICE_HOME, notice & fwd & (x == o),
                       notice & fan & (((others >> x) & 1u) != 0u));
     if (!ok) return false;
-    SER_COUNT_MACRO(hit, upg, ev, mod, notice, notice & (x == h), selfn, fwd, dead, wr != 0u, fan);
+    SER_COUNT_MACRO(hit, upg, ev, t.mod, notice, notice & (x == h), selfn, fwd, dead, wr != 0u, fan);
     stamp(2);
-    /* the home's directory entry and memory after the request (:188-236, :298-328, :375-435):
-     * READ_REQUEST U -> EM {n}, S -> S + n, EM at n unchanged, EM at o -> S {o, n};
-     * WRITE_REQUEST writes memory first, then U / S -> EM {n}, EM at n unchanged, EM at o ->
-     * EM {n}; UPGRADE -> EM {n}.  A flush then writes o's value to memory (FLUSH_INVACK also
-     * EM {n}: unchanged). */
-    const bool rdq = miss & (wr == 0u), req = miss | upg;
-    const bool keep = miss & (dH == 0u) & !fwd;                 /* EM at the requester */
-    const bool excl = !(rdq & (dH == 1u)) & !fwd;               /* REPLY_RD's bitVector == 2 */
-    const uint32_t nmemH = (fwd & !dead) ? vO : ((miss & (wr != 0u)) ? val : memH);
-    const uint32_t nbvH = rdq ? (dH == 2u ? bit : (((dH == 1u) | fwd) ? (bvH | bit) : bvH)) : (keep ? bvH : bit);
-    const uint32_t ndH = rdq ? (dH == 2u ? 0u : (fwd ? 1u : dH)) : 0u;
+    SHome hm;
+    ser_txn_home(hm, t, bit, fwd, dead, vO);
+    const bool req = hm.req;
+    const uint32_t nmemH = hm.nmemH, nbvH = hm.nbvH, ndH = hm.ndH;
     /* write-back, branch-free (a disabled store goes to the dummy word); when the eviction's
      * and the request's words coincide the request's write holds both */
     m.st_if(req, S_DS + h, (dsH & ~(3u << shb)) | (ndH << shb));
@@ -605,8 +663,7 @@ DSM_HD bool ser_macro(M &m, SReg &r, SCache &cc, F &&fetch, R &&on_dump, P &&sta
     }
     /* the requester's line (:243-246, :291-294, :445-447, :334-336, :491-494; a write hit
      * :642-643, :656-657), pendingWriteValue (:633), the instruction index */
-    const uint32_t nLv = dead ? 0u : (fwd ? vO : (wr ? val : (miss ? memH : Lv)));
-    const uint32_t nLs = dead ? 3u : (wr ? 0u : (miss ? (excl ? 1u : 2u) : Ls));
+    const uint32_t nLv = hm.nLv, nLs = hm.nLs;
     const uint32_t nla = (laW & ~(0xFFu << sh8)) | (a << sh8);
     const uint32_t nlv = (lvW & ~(0xFFu << sh8)) | (nLv << sh8);
     ct = (ct & ~(3u << lsh)) | (nLs << lsh);
@@ -636,6 +693,86 @@ DSM_HD bool ser_macro(M &m, SReg &r, SCache &cc, F &&fetch, R &&on_dump, P &&sta
     r.A = r.iss;
     r.st = (r.dmp == NPM) ? SS_COMPLETED : SS_DEADLOCKED;
     return true;
+}
+
+/* ---- a run of simple transactions (round 8) ------------------------------------------------
+ * Once a lone system has run for a while nearly every transaction is of the simple kind: a hit,
+ * or a miss with its own eviction, a request and a reply -- no forward, no upgrade notice, no
+ * INV fan-out (98.2% of C3's macro-steps, all of them after ~1,700 steps of a system).  ser_macro
+ * pays its whole skeleton for each: the quiet test, the pick of the trace length, the fetch
+ * from a run-time half-word, three stores of the node's own words.  ser_solo applies up to 8 of
+ * them in one call: the instructions of the trace chunk (c0..c3: 8 half-words) from half-word
+ * ip & 7 through 7, each extracted with a constant shift; the node's own words, the rounds and
+ * the messages stay in registers and are written once at the end (before anything else reads
+ * the column: the caller's next ser_macro / ser_step / record store comes after the call).
+ * Requires ser_quiet_lone(r), cc.node == the lone node (its words in cc) and the chunk of its
+ * next instruction in c0..c3.  A lane stops, leaving the instruction to the general path, at
+ * the first step that is not simple: a forward, a notice, a fan-out, !ok as ser_macro defines
+ * it for a simple step (a home >= NP, EM with no bit), the end of the trace, or the round
+ * limit within reach (ser_quiet_lone's test, again before every step: a run adds up to 8 x 4
+ * rounds).  A stopped lane idles through the rest of the run (its stores go to the dummy
+ * word).  Returns the steps applied. */
+enum : uint32_t { SOLO_FWD = 0, SOLO_NOTICE, SOLO_FAN, SOLO_HOME, SOLO_TRACE_END, SOLO_ROUND_LIMIT, SOLO_CAUSES };
+template <int NP, class M>
+DSM_HD uint32_t ser_solo(M &m, SReg &r, SCache &cc, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
+                         uint32_t lim_rsh) {
+    constexpr uint32_t NPM = (1u << NP) - 1u;
+    const uint32_t n = s_ctz(r.A), bit = 1u << n, nins = s_ni(r, n);
+    uint32_t ct = cc.ct, la = cc.la, lv = cc.lv;
+    uint32_t rounds = r.rounds, msgs = r.msgs, steps = 0u;
+    const uint32_t j0 = (ct >> SC_IP) & 7u;
+    SER_COUNT_SOLO_ENTRY(j0);
+    bool go = true;
+#ifdef __clang__
+#pragma unroll
+#endif
+    for (uint32_t j = 0; j < 8u; ++j) {
+        if (!s_any(go)) break;
+        const uint32_t w = j < 2u ? c0 : (j < 4u ? c1 : (j < 6u ? c2 : c3));
+        const uint32_t ins = (w >> (16u * (j & 1u))) & 0xFFFFu;
+        const bool act = go & (j >= j0);
+        STxn t;
+        ser_txn_front(m, t, ins, ct, la, lv, n, bit, [](int) {});
+        const bool end = (ct >> SC_IP) >= nins;
+        const bool lim = ((rounds + SER_MACRO_MAX_ROUNDS + 1u) >> lim_rsh) != 0u;
+        const bool home = (!((NP == 8) || (t.h < (uint32_t)NP))) | ((t.dH == 0u) & t.miss & (t.bvH == 0u));
+        const bool simple = !(end | lim | home | t.fwd | t.notice | t.fan);
+        const bool en = act & simple;
+        if (act & !simple)
+            SER_COUNT_SOLO_STOP(end ? SOLO_TRACE_END : lim ? SOLO_ROUND_LIMIT : home ? SOLO_HOME :
+                                t.fwd ? SOLO_FWD : t.fan ? SOLO_FAN : SOLO_NOTICE, j);
+        go = go & (!act | simple);
+        SHome hm;
+        ser_txn_home(hm, t, bit, false, false, 0u);
+        if (en) SER_COUNT_MACRO(t.hit, t.upg, t.ev, t.mod, false, false, false, false, false, t.wr != 0u, false);
+        /* write-back as ser_macro's, every store under the lane's flag */
+        m.st_if(en & hm.req, S_DS + t.h, (t.dsH & ~(3u << t.shb)) | (hm.ndH << t.shb));
+        m.st_if(en & hm.req, t.wH, (t.mbH & ~(0xFFFFu << t.hh)) | ((hm.nmemH | (hm.nbvH << 8)) << t.hh));
+        m.st_if(en & t.ev & (t.vh != t.h), S_DS + t.vh, t.dsV2);
+        m.st_if(en & t.ev & (t.wV != t.wH), t.wV, t.mbV2);
+        const uint32_t nla = (la & ~(0xFFu << t.sh8)) | (t.a << t.sh8);
+        const uint32_t nlv = (lv & ~(0xFFu << t.sh8)) | (hm.nLv << t.sh8);
+        uint32_t nct = (ct & ~(3u << t.lsh)) | (hm.nLs << t.lsh);
+        nct = (t.wr ? ((nct & ~0xFFu) | t.val) : nct) + (1u << SC_IP);
+        la = en ? nla : la;
+        lv = en ? nlv : lv;
+        ct = en ? nct : ct;
+        /* rounds and messages as ser_macro's, without a forward, a notice or a fan-out */
+        const bool lone = t.hit & !t.upg;
+        const uint32_t treq = (t.ev & (t.vh == t.h)) ? 3u : 2u;
+        rounds += en ? (lone ? 1u : treq + 1u) : 0u;
+        msgs += en ? (lone ? 0u : (t.ev ? 1u : 0u) + 2u) : 0u;
+        steps += en ? 1u : 0u;
+    }
+    m.st(S_LA + n, la);
+    m.st(S_LV + n, lv);
+    m.st(S_CT + n, ct);
+    cc.ct = ct; cc.la = la; cc.lv = lv;
+    r.rounds = rounds;
+    r.msgs = msgs;
+    r.E = steps ? 0u : r.E;
+    r.st = steps ? ((r.dmp == NPM) ? (uint32_t)SS_COMPLETED : (uint32_t)SS_DEADLOCKED) : r.st;
+    return steps;
 }
 
 /* ---- claim order of the resume pass (round 7) ----------------------------------------------

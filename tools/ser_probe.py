@@ -30,4 +30,9 @@ names = ["iters", "iters_macro", "iters_one_action", "iters_chunk_miss", "iters_
          "cyc_macro_phase", "cyc_one_action_phase", "cyc_handover_phase", "live_lanes",
          "lanes_not_quiet", "lanes_quiet_declined", "lanes_instr_not_at_hand", "iters_lt32_live",
          "cyc13", "cyc14", "cyc15", "cyc16"]
-print(json.dumps({k: int(raw[i]) for i, k in enumerate(names)}), flush=True)
+d = {k: int(raw[i]) for i, k in enumerate(names)}
+# the run phase (SER_SOLO): slots 34-37; wave iterations and macro-steps of any build: 33, 32
+d.update({k: int(raw[34 + i]) for i, k in enumerate(["solo_runs", "solo_steps", "solo_idle_lane_steps",
+                                                      "cyc_solo_runs"])})
+d.update(ser_iterations=int(raw[33]), ser_macro_steps=int(raw[32]))
+print(json.dumps(d), flush=True)
