@@ -37,10 +37,6 @@
 #include <string.h>
 
 #include "dsm.h"
-#ifndef SIM_BF
-#define SIM_BF 0            /* A/B: bit 0 the first receive-mask ORs without a branch, bit 1 the
-                               first destination index as a mask select (dsm_table.h) */
-#endif
 #include "dsm_table.h"
 #include "dsm_internal.h"   /* and dsm_plan.h: the schedule */
 #include "dsm_gen.h"
@@ -135,19 +131,6 @@ DEVI uint64_t uni64(uint64_t x) { return ((uint64_t)uni32((uint32_t)(x >> 32)) <
 #define TRAFFIC_PROBE 0     /* traffic attribution builds (results invalid): 1 no serial pass, 2 and
                                no serial-form suspend records (tools/traffic_streams.sh) */
 #endif
-#ifndef SIM_UNI
-#define SIM_UNI 1           /* the suspend-on-lone budget pass's per-round end test as one per-lane
-                               ballot, not 64-bit mask arithmetic (0: the mask form everywhere) */
-#endif
-#ifndef SIM_RFL
-#define SIM_RFL 1           /* the round loop's wave-uniform values (the live mask, the end test,
-                               the lone-check countdown) pinned uniform with readfirstlane */
-#endif
-#ifndef SIM_R2
-#define SIM_R2 0            /* plain budget kernels: a third trace chunk in registers and the refill
-                               as one 32-B load every 16 instructions (half the chunk loads, each
-                               a line fetch: the scattered 16-B loads find no line in L2) */
-#endif
 #ifndef REC_PROBE
 #define REC_PROBE 0         /* probe build (hashes invalid): no node records and no digest pass, to
                                time what the records cost the step */
@@ -156,11 +139,26 @@ DEVI uint64_t uni64(uint64_t x) { return ((uint64_t)uni32((uint32_t)(x >> 32)) <
 #define SIM_TAILPROBE 0     /* budget-pass wave end-time histogram (probe build, results exact;
                                tools/tail_probe.py) */
 #endif
-#ifndef FF_LONG
-#define FF_LONG 1           /* fast-forward runs past the 8-instruction window */
-#endif
+/* SIM_TAILPROBE in sim_kernel (ser_kernel's part is inline there).  At 1, when the budget pass's
+ * waves end: a histogram in the msgs_by_type slots of the wave's counter row -- 0: before 14 ms, k = 1..11:
+ * [13 + k, 14 + k) ms, 12: the waves' summed lifetimes in 10-ns ticks (s_memrealtime, 100 MHz) */
+struct SimTailProbe {
+    uint64_t t0 = 0;
+    DEVI void wave_begin() {
+        if constexpr (SIM_TAILPROBE != 0) t0 = __builtin_amdgcn_s_memrealtime();
+    }
+    DEVI void wave_end(unsigned long long *row) const {
+        if constexpr (SIM_TAILPROBE == 1) {
+            const uint64_t dt = __builtin_amdgcn_s_memrealtime() - t0;
+            const uint64_t ms = dt / 100000u;
+            row[ms < 14u ? 0u : (ms - 13u < 11u ? ms - 13u : 11u)] += 1;
+            row[12] += dt;
+        }
+    }
+};
 #ifndef FF_LONG_U
-#define FF_LONG_U 8         /* trace chunks per step of that scan (hot, C4: 1 / 2 / 4 / 6 / 8 -> 49.6 / 39.3 / 34.1 / 32.6 / 32.1 ms) */
+#define FF_LONG_U 8         /* trace chunks per step of the fast-forward scan past the 8-instruction
+                               window (hot, C4: 1 / 2 / 4 / 6 / 8 -> 49.6 / 39.3 / 34.1 / 32.6 / 32.1 ms) */
 #endif
 
 namespace {
@@ -429,9 +427,7 @@ sim_kernel(const SimArgs *Ap) {
     constexpr bool TC = (MODE & M_TC) != 0, TR = (MODE & M_TR) != 0, SX = (MODE & M_SX) != 0;
     constexpr SimTraits T = sim_traits(MODE, GEN, FB);
     constexpr bool BUD = T.bud, LIM = T.lim, FF = T.ff, LONE = T.lone;
-    constexpr bool UNI = SIM_UNI != 0 && LONE;     /* the per-round end test as one ballot */
-    /* paired refills (SIM_R2): the plain kernels, whose ip only ever moves by one issue */
-    constexpr bool R2 = SIM_R2 != 0 && BUD && !FF && !GEN;
+    constexpr bool UNI = LONE;     /* the per-round end test as one ballot */
     constexpr int SW = susp_words(RING);
     /* fast-forward probe interval: FF_PROBE iterations after a probe that found a group,
      * doubling up to FF_PROBE_MAX after each one that found none (workloads without hit
@@ -458,16 +454,14 @@ sim_kernel(const SimArgs *Ap) {
     s_rm[wv][lane] = 0;
     for (uint32_t i = threadIdx.x; i < DT_TABLE_WORDS / 2; i += 64 * WAVES) s_tab[i] = Ap->table[i];
     __syncthreads();
-#if SIM_TAILPROBE
-    const uint64_t tprobe0 = __builtin_amdgcn_s_memrealtime();
-#endif
+    SimTailProbe tail;
+    tail.wave_begin();
 
     /* values read through loaded (generic) pointers count as lane-varying to the compiler's
      * uniformity analysis, which then takes every branch that depends on them -- the round
-     * loop's -- as divergent: SIM_RFL states them uniform */
-    const uint64_t n = SIM_RFL ? uni64(Ap->d_n ? (uint64_t)*Ap->d_n : Ap->n_sys)
-                               : (Ap->d_n ? (uint64_t)*Ap->d_n : Ap->n_sys);
-    const bool ffv = SIM_RFL ? uni32(ff_verdict(Ap->scan)) != 0u : ff_verdict(Ap->scan);
+     * loop's -- as divergent: uni32 / uni64 state them uniform */
+    const uint64_t n = uni64(Ap->d_n ? (uint64_t)*Ap->d_n : Ap->n_sys);
+    const bool ffv = uni32(ff_verdict(Ap->scan)) != 0u;
     const uint32_t *list = Ap->list;
     const uint64_t G = ((uint64_t)blockIdx.x * WAVES + wv) * GPW + lane / NP;
     uint32_t shard = blockIdx.x & 7u, tried = 0;
@@ -504,9 +498,6 @@ sim_kernel(const SimArgs *Ap) {
 
     Node nd;
     uint32_t cur[4] = {0, 0, 0, 0}, nxt[4] = {0, 0, 0, 0};
-    /* R2: chunk k + 2 while the chunk in cur (k = ip >> 3) is even; the refill consuming an
-     * odd chunk loads k + 2 and k + 3 together (one line fetch for both) */
-    uint32_t nx2[4] = {0, 0, 0, 0};
     /* FF: the line tags for a hit, a byte per line (RD needs a valid line, state != I; WR one
      * in M or E, state <= E; 0xFF never equals a 7-bit address), set at mode entry: in the
      * mode no message arrives and a write hit on E leaves M, still a hit for both */
@@ -563,12 +554,6 @@ sim_kernel(const SimArgs *Ap) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) { cur[k] = q[(7 + k) * NP]; nxt[k] = q[(11 + k) * NP]; }
             if (!GEN) tb = tslot();
-            if (R2 && ((nd.ip >> 3) & 1u) == 0u) {          /* the even phase needs k + 2 */
-                const uint32_t pc = (nd.ip & ~7u) + 16u;
-                const uint4 v2 = ld16(tb + (pc + 8u <= stride ? pc : stride - 8u));
-                nx2[0] = v2.x; nx2[1] = v2.y; nx2[2] = v2.z; nx2[3] = v2.w;
-                wait_vmcnt0();
-            }
             rmsg = s_ring[wv][nd.rh & 0xFFu][lane];          /* the head, as the loop keeps it */
             return;
         }
@@ -600,10 +585,6 @@ sim_kernel(const SimArgs *Ap) {
             const uint4 v0 = ld16(tb), v1 = ld16(tb + (stride > 8 ? 8 : 0));
             cur[0] = v0.x; cur[1] = v0.y; cur[2] = v0.z; cur[3] = v0.w;
             nxt[0] = v1.x; nxt[1] = v1.y; nxt[2] = v1.z; nxt[3] = v1.w;
-            if (R2) {
-                const uint4 v2 = ld16(tb + (stride > 16 ? 16 : stride - 8));
-                nx2[0] = v2.x; nx2[1] = v2.y; nx2[2] = v2.z; nx2[3] = v2.w;
-            }
             wait_vmcnt0();
         }
     };
@@ -711,7 +692,7 @@ sim_kernel(const SimArgs *Ap) {
                 const bool inff = __builtin_amdgcn_inverse_ballot_w64(ffm);
                 if (lane == 0) s_cnt[wv][K_FFITER] += 1;     /* fast-forward steps of the wave */
                 uint32_t k = 8;
-                bool lng = false;          /* the group's step ran past the window (FF_LONG) */
+                bool lng = false;          /* the group's step ran past the window */
                 if (inff) {
                     const bool iss = (nd.ctl & C_WAIT) == 0u && nd.ip < nd.nins;
                     const bool dpend = (nd.ctl & (C_WAIT | C_DUMPED)) == 0u && nd.ip >= nd.nins;
@@ -751,7 +732,7 @@ sim_kernel(const SimArgs *Ap) {
                     const uint32_t rmax = rounds + 1u >= thr ? 0u : thr - 1u - rounds;
                     if (r > rmax) r = rmax;
                     k = gmin<NP>(r);
-                    /* ---- the run past the window (FF_LONG) ---------------------------------
+                    /* ---- the run past the window -------------------------------------------
                      * a group whose issuing nodes all hit the whole window scans on, FF_LONG_U
                      * chunks per step straight from the trace, for the first miss of each node
                      * (or its trace end, or the group's round bound rmax); k = the group's
@@ -759,7 +740,7 @@ sim_kernel(const SimArgs *Ap) {
                      * group leaves the mode and the round that breaks the run follows in this
                      * iteration (C4 runs hundreds of hits per node between misses, where the
                      * 8-wide window took one loop iteration per 8). */
-                    if (FF_LONG && __ballot(k == 8u)) {
+                    if (__ballot(k == 8u)) {
                         /* chunks per scan step: generated chunks hide no latency and eight
                          * unrolled generator calls spilled the fused kernel (103 VGPRs) */
                         constexpr int LU = GEN ? 1 : FF_LONG_U;
@@ -870,24 +851,8 @@ sim_kernel(const SimArgs *Ap) {
              * HBM latency overlaps this round's transition and delivery (a load consumed in the
              * same basic block stalls the whole wave on HBM). */
             const bool refill = !GEN && doIssue && ((nd.ip + 1) & 7u) == 0 && nd.ip + 1 < nd.nins;
-            uint4 pf, pf2;
-            if (R2 && SIM_R2 == 2) {
-                /* the rotation consuming an odd chunk loads the next two, 32 B in one line:
-                 * k + 2 straight into nx2 (dead in this phase), k + 3 into pf */
-                if (refill && ((nd.ip + 1) & 15u) == 0u) {
-                    const uint4 a2 = ld16(tb + (nd.ip + 9 < stride ? nd.ip + 9 : stride - 8));
-                    pf = ld16(tb + (nd.ip + 17 < stride ? nd.ip + 17 : stride - 8));
-                    nx2[0] = a2.x; nx2[1] = a2.y; nx2[2] = a2.z; nx2[3] = a2.w;
-                }
-            } else if (R2) {
-                /* the rotation consuming an odd chunk loads the next two, 32 B in one line */
-                if (refill && ((nd.ip + 1) & 15u) == 0u) {
-                    pf = ld16(tb + (nd.ip + 9 < stride ? nd.ip + 9 : stride - 8));
-                    pf2 = ld16(tb + (nd.ip + 17 < stride ? nd.ip + 17 : stride - 8));
-                }
-            } else if (refill) {
-                pf = ld16(tb + (nd.ip + 9 < stride ? nd.ip + 9 : stride - 8));
-            }
+            uint4 pf;
+            if (refill) pf = ld16(tb + (nd.ip + 9 < stride ? nd.ip + 9 : stride - 8));
             const uint32_t headn = (head0 + 1 == (uint32_t)RING) ? 0u : head0 + 1;
             nd.rh = hasMsg ? (headn | ((cnt0 - 1) << 8)) : nd.rh;
             uint32_t w = rmsg;
@@ -969,17 +934,8 @@ sim_kernel(const SimArgs *Ap) {
                 uint32_t m0 = o0 >> 24, m1 = o1 >> 24;
                 const uint32_t b0 = 2 * node;
                 const uint32_t bit0 = 1u << b0, bit1 = 2u << b0;
-#if SIM_BF & 1
-                /* each word's first destination without a branch: a lane with none ORs 0 into
-                 * its own mask */
-                atomicOr(&s_rm[wv][m0 ? gbase + __builtin_ctz(m0) : lane], m0 ? bit0 : 0u);
-                atomicOr(&s_rm[wv][m1 ? gbase + __builtin_ctz(m1) : lane], m1 ? bit1 : 0u);
-                m0 &= m0 - 1;
-                m1 &= m1 - 1;
-#else
                 if (m0) { atomicOr(&s_rm[wv][gbase + __builtin_ctz(m0)], bit0); m0 &= m0 - 1; }
                 if (m1) { atomicOr(&s_rm[wv][gbase + __builtin_ctz(m1)], bit1); m1 &= m1 - 1; }
-#endif
                 while (m0) { atomicOr(&s_rm[wv][gbase + __builtin_ctz(m0)], bit0); m0 &= m0 - 1; }
                 while (m1) { atomicOr(&s_rm[wv][gbase + __builtin_ctz(m1)], bit1); m1 &= m1 - 1; }
             }
@@ -1011,20 +967,7 @@ sim_kernel(const SimArgs *Ap) {
                 rmsg = s_ring[wv][hh][lane];          /* next round's head, prefetched */
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            if (R2 && SIM_R2 == 2 && refill) {
-                /* cur <- nxt <- nx2 always; after a pair load nx2 <- pf (k + 3) */
-    #pragma unroll
-                for (int k = 0; k < 4; ++k) { cur[k] = nxt[k]; nxt[k] = nx2[k]; }
-                if ((nd.ip & 15u) == 0u) { nx2[0] = pf.x; nx2[1] = pf.y; nx2[2] = pf.z; nx2[3] = pf.w; }
-            } else if (R2 && refill) {
-                /* ip is already past the issue: an even ip means an odd chunk was consumed */
-                const bool pair = (nd.ip & 15u) == 0u;
-    #pragma unroll
-                for (int k = 0; k < 4; ++k) cur[k] = nxt[k];
-                nxt[0] = pair ? pf.x : nx2[0]; nxt[1] = pair ? pf.y : nx2[1];
-                nxt[2] = pair ? pf.z : nx2[2]; nxt[3] = pair ? pf.w : nx2[3];
-                if (pair) { nx2[0] = pf2.x; nx2[1] = pf2.y; nx2[2] = pf2.z; nx2[3] = pf2.w; }
-            } else if (refill) {
+            if (refill) {
     #pragma unroll
                 for (int k = 0; k < 4; ++k) cur[k] = nxt[k];
                 nxt[0] = pf.x; nxt[1] = pf.y; nxt[2] = pf.z; nxt[3] = pf.w;
@@ -1045,7 +988,7 @@ sim_kernel(const SimArgs *Ap) {
             asm volatile("" : "+v"(opv));
             const uint64_t actb = __ballot(opv != OP_IDLE || stall) | (WFF ? ffm : 0ull);
             uint64_t loneb = 0;
-            if (SIM_RFL) lcd = uni32(lcd);
+            lcd = uni32(lcd);
             if (!WFF && LONE && lone_on && --lcd == 0u) {
                 lcd = lone_on;
                 loneb = lone_mask();
@@ -1056,17 +999,7 @@ sim_kernel(const SimArgs *Ap) {
                  * with an assert, the round limit / budget or an overflowing inbox (C3 budget
                  * pass 24.5 -> 23.8 ms, C5 15.9 -> 15.5; in the kernel without suspend-on-lone,
                  * C4's, 17.3 -> 17.6: there the mask form below is kept) */
-                uint32_t gidle;
-                if constexpr (SIM_UNI == 2) {
-                    /* the groups with an active lane as a wave mask, each such group's field
-                     * all ones (scalar ops on the uniform actb), read per lane as a lane mask */
-                    constexpr uint64_t FTOP = NP == 8 ? 0x8080808080808080ull : 0x8888888888888888ull;
-                    constexpr uint64_t FLOW = ~FTOP;
-                    const uint64_t one = ((((actb & FLOW) + FLOW) | actb) & FTOP) >> (NP - 1);
-                    gidle = __builtin_amdgcn_inverse_ballot_w64((one << NP) - one) ? 0u : 1u;
-                } else {
-                    gidle = ((uint32_t)(actb >> gbase) & NPM) == 0u;
-                }
+                const uint32_t gidle = ((uint32_t)(actb >> gbase) & NPM) == 0u;
                 /* bitwise, not && / ||: short-circuit conditions are compiled into branches */
                 const uint32_t endc = (uint32_t)live & (gidle | (uint32_t)((nd.ctl & C_ASSERT) != 0u) |
                                                         (uint32_t)(rounds >= thr) | (uint32_t)(nccv > ocap));
@@ -1215,7 +1148,7 @@ sim_kernel(const SimArgs *Ap) {
                     }
                 }
             }
-            const uint64_t nlive = SIM_RFL ? uni64(__ballot(live)) : __ballot(live);
+            const uint64_t nlive = uni64(__ballot(live));
             /* budget pass: once a slot of this wave found no new system, the wave's remaining
              * systems get the late budget, so the launch's tail is not a system claimed last
              * running its full budget at falling occupancy (the resume pass continues them) */
@@ -1293,17 +1226,7 @@ sim_kernel(const SimArgs *Ap) {
      * depend on the order, so no separate reduction pass is needed) */
     if (lane == 0) {
         s_cnt[wv][K_WROUNDS] = wrounds;
-#if SIM_TAILPROBE == 1
-        /* probe build (results exact, not the default): when the budget pass's waves end, a
-         * histogram in the msgs_by_type slots -- 0: before 14 ms, k = 1..11: [13 + k, 14 + k)
-         * ms, 12: the waves' summed lifetimes in 10-ns ticks (s_memrealtime, 100 MHz) */
-        if (BUD && budget) {
-            const uint64_t dt = __builtin_amdgcn_s_memrealtime() - tprobe0;
-            const uint64_t ms = dt / 100000u;
-            s_cnt[wv][ms < 14u ? 0u : (ms - 13u < 11u ? ms - 13u : 11u)] += 1;
-            s_cnt[wv][12] += dt;
-        }
-#endif
+        if (BUD && budget) tail.wave_end(s_cnt[wv]);
     }
     __syncthreads();
     if (threadIdx.x < K_N) {
@@ -1335,25 +1258,8 @@ sim_kernel(const SimArgs *Ap) {
  * beyond the inbox limit hands the system to the 256-deep re-run, as a ring overflow of the
  * lock-step kernel does.  The issuing node's trace chunk and the next one are kept in
  * registers (refill step below). */
-#ifndef SER_RF_DEF
-#define SER_RF_DEF 8
-#endif
-#ifndef SER_GE_DEF
-#define SER_GE_DEF 1
-#endif
-#ifndef SER_MACRO_DEF
-#define SER_MACRO_DEF 1     /* lone-node macro-steps per iteration (0: off) */
-#endif
-/* SER_RF: iterations between trace refills; SER_GE: the one-action step (ser_step) runs in
- * every SER_GE-th iteration (the macro-step in every one) */
-constexpr int SER_RF = SER_RF_DEF, SER_GE = SER_GE_DEF;
-constexpr int SER_MACRO = SER_MACRO_DEF;   /* lone-node macro-steps per iteration */
-/* SER_PROBE builds (diagnostics, never the default): per-wave event counts of the serial pass
- * in the counter slots the pass leaves unused (msgs_by_type 0-4): iterations, iterations with
- * a macro-step, with a one-action step, with a chunk miss, hand-overs */
-#ifndef SER_PROBE
-#define SER_PROBE 0
-#endif
+constexpr int SER_RF = 8;   /* iterations between trace refills */
+constexpr int SER_MACRO = 1;   /* lone-node macro-steps per iteration */
 #ifndef SER_HB
 #define SER_HB 8            /* finished lanes that trigger a batched hand-over (1: at once) */
 #endif
@@ -1361,16 +1267,19 @@ constexpr int SER_MACRO = SER_MACRO_DEF;   /* lone-node macro-steps per iteratio
 #define SER_HT 32           /* ... or iterations the oldest finished lane has waited */
 #endif
 /* the run phase (dsm_serial.h ser_solo) in front of each refill period's iterations: taken by a
- * wave when at least SER_SOLO_MIN of 64 of its running lanes are eligible; 0: the loop without
- * it, exactly (A/B through tools/build_variant.sh) */
-#ifndef SER_SOLO
-#define SER_SOLO 1
-#endif
+ * wave when at least SER_SOLO_MIN of 64 of its running lanes are eligible */
 #ifndef SER_SOLO_MIN
 #define SER_SOLO_MIN 48     /* C3 64 / 56 / 48 / 32: 32.45 / 31.97 / 32.30 / 32.29 ms; C5 21.98 / 21.86 / 21.80 / 21.81 */
 #endif
 #ifndef SER_SOLO_HW
 #define SER_SOLO_HW 4       /* a run's weight in SER_HT's iterations */
+#endif
+
+/* SER_PROBE builds (diagnostics, never the default; tools/ser_probe.py): per-wave event counts
+ * of the serial pass in the counter slots the pass leaves unused (msgs_by_type 0-4): iterations,
+ * iterations with a macro-step, with a one-action step, with a chunk miss, hand-overs */
+#ifndef SER_PROBE
+#define SER_PROBE 0
 #endif
 
 template <int W>
@@ -1413,6 +1322,7 @@ __global__ void __launch_bounds__(64 * SER_WAVES) __attribute__((amdgpu_waves_pe
 ser_kernel(const SimArgs *Ap) {
     using namespace dsms;
     constexpr uint32_t NPM = (1u << NP) - 1u;
+    constexpr bool SOLO = !CAP;    /* the run phase (below): not in the kernel with an inbox limit */
     /* one of a fast-forward / serial pair: the fast-forward lock-step resume takes the run
      * when the trace scan picked fast-forward */
     if (DSM_SER_EXITS(Ap)) return;
@@ -1439,7 +1349,7 @@ ser_kernel(const SimArgs *Ap) {
     const bool ordered = Ap->serfmt != 0u && Ap->susp_order != nullptr;
     const uint32_t nmulti = ordered ? *Ap->susp_multi : 0u;
     const uint32_t nlong = nmulti + (ordered ? *Ap->susp_long : 0u);
-    const uint32_t n = SIM_RFL ? uni32(*Ap->d_n) : *Ap->d_n;   /* (sim_kernel's n) */
+    const uint32_t n = uni32(*Ap->d_n);   /* (sim_kernel's n) */
     const uint32_t lcap = Ap->susp_cap;
     const uint32_t *const list = ordered ? Ap->susp_order : Ap->list;
     /* global (not flat) accesses: a pending flat operation makes every later wait a full
@@ -1592,7 +1502,7 @@ ser_kernel(const SimArgs *Ap) {
         r.E = r.nz;
         r.A = r.nz | r.iss;
         ser_cache_clear(cc);
-        if (SER_SOLO && !CAP && serfmt && tn != 0xFFu) {
+        if (SOLO && serfmt && tn != 0xFFu) {
             /* a lone system: its node's words into the register cache, so that the first
              * period's gate already finds the lane eligible */
             cc.ct = m.ld(S_CT + tn); cc.la = m.ld(S_LA + tn); cc.lv = m.ld(S_LV + tn);
@@ -1721,20 +1631,19 @@ ser_kernel(const SimArgs *Ap) {
     }
     v = live ? start() : SR_RUN;
     uint32_t iters = 0, nmac = 0;
-#if SIM_TAILPROBE == 2
-    /* probe: per lane, the iteration its system started at and whether it was lone at
+    /* SIM_TAILPROBE 2: per lane, the iteration its system started at and whether it was lone at
      * suspension (header word 121), and running maxima / sums published at the kernel's end */
-    uint32_t tclaim = 0;
-    bool lone0 = live && serfmt && (rr[30].y & 0x100u);
-    uint64_t pr_long = 0, pr_last = 0, pr_n4k = 0, pr_nl_it = 0, pr_it = 0, pr_nl_n = 0;
-#endif
+    uint32_t tclaim = 0, now_it = 0;
+    bool lone0 = false;
+    [[maybe_unused]] uint64_t pr_long = 0, pr_last = 0, pr_n4k = 0, pr_nl_it = 0, pr_it = 0, pr_nl_n = 0;
+    if constexpr (SIM_TAILPROBE == 2) lone0 = live && serfmt && (rr[30].y & 0x100u);
     /* batched hand-overs: a hand-over is a wave-wide phase (~19k cycles on C3, most of it
      * waits on the claim, the lookup, the successor's rows and the record stores) however
      * few lanes take part, so a finished system waits, its lane idle, until SER_HB lanes of
      * the wave have finished, or the oldest has waited SER_HT iterations, or no running
      * system is left in the wave; then they hand over together (wave-uniform) */
     uint32_t hwait = 0;
-    /* the run phase (SER_SOLO): a refill period starts with the gate -- a lane is eligible when
+    /* the run phase: a refill period starts with the gate -- a lane is eligible when
      * it runs a quiet-lone system whose node's words are in the register cache and whose next
      * instruction's chunk is in cur (after the nx rotation, if due) -- and, when SER_SOLO_MIN
      * of 64 of the wave's running lanes are eligible (one ballot, wave-uniform), one ser_solo
@@ -1757,7 +1666,7 @@ ser_kernel(const SimArgs *Ap) {
 #pragma unroll 1
         for (int k = 0; k < SER_RF; ++k) {
             bool ran_now = false, gen = true;
-            if (SER_SOLO && !CAP) {
+            if (SOLO) {
                 if (k == 0) {
                     uint64_t ts0 = 0;
                     if (SER_PROBE >= 2) ts0 = __builtin_amdgcn_s_memtime();
@@ -1800,6 +1709,8 @@ ser_kernel(const SimArgs *Ap) {
             uint64_t tp0 = 0, tp1 = 0, tp2 = 0;
             if (SER_PROBE >= 2) tp0 = __builtin_amdgcn_s_memtime();
             if (!CAP && gen) {
+                /* (a loop of one: with its body written straight, ser_kernel<NP, false> -- at the
+                 * VGPR limit -- compiles to other code than the one that was measured) */
 #pragma unroll
                 for (int j = 0; j < SER_MACRO; ++j) {
                     const bool q = live && v == SR_RUN && !rest && ser_quiet_lone(r, lim_rsh) && (j == 0 || mac);
@@ -1844,7 +1755,7 @@ ser_kernel(const SimArgs *Ap) {
                 }
                 /* a macro-step that ended the system (the dead-end forward): quiescent */
                 if (mac && r.A == 0u) v = SR_DONE;
-                if (SER_SOLO) rest = rest | (taken & mac);
+                if (SOLO) rest = rest | (taken & mac);
             }
             if (SER_PROBE) {
                 const uint64_t gm = __ballot(live && v == SR_RUN && !mac), mm = __ballot(mac);
@@ -1858,7 +1769,7 @@ ser_kernel(const SimArgs *Ap) {
                 }
             }
             if (SER_PROBE >= 2) tp1 = __builtin_amdgcn_s_memtime();
-            if (live && v == SR_RUN && !mac && gen && !rest && (k % SER_GE) == 0) {
+            if (live && v == SR_RUN && !mac && gen && !rest) {
                 v = ser_step<NP, S_QN, CAP>(m, r, T, fetch, on_dump, lim_rsh, cap);
                 ser_cache_clear(cc);
             }
@@ -1868,20 +1779,14 @@ ser_kernel(const SimArgs *Ap) {
                 if (lane == 0 && hm) atomicAdd(&s_cnt[4], 1ull);
             }
             bool hgo = false;
-            if (SER_HB > 1) {
-                const uint64_t fin = __ballot(live && v != SR_RUN);
-                if (fin) {
-                    hgo = (uint32_t)__builtin_popcountll(fin) >= (uint32_t)SER_HB ||
-                          hwait >= (uint32_t)SER_HT || fin == __ballot(live);
-                    hwait = hgo ? 0u : hwait + (gen ? 1u : 0u) + (ran_now ? (uint32_t)SER_SOLO_HW : 0u);
-                }
-            } else {
-                hgo = true;
+            const uint64_t fin = __ballot(live && v != SR_RUN);
+            if (fin) {
+                hgo = (uint32_t)__builtin_popcountll(fin) >= (uint32_t)SER_HB ||
+                      hwait >= (uint32_t)SER_HT || fin == __ballot(live);
+                hwait = hgo ? 0u : hwait + (gen ? 1u : 0u) + (ran_now ? (uint32_t)SER_SOLO_HW : 0u);
             }
             if (hgo && live && v != SR_RUN) {
-#if SIM_TAILPROBE == 2
-                const uint32_t now_it = iters + (uint32_t)k;   /* this iteration (before the claim's k) */
-#endif
+                if constexpr (SIM_TAILPROBE == 2) now_it = iters + (uint32_t)k;   /* this iteration (before the claim's k) */
                 uint64_t th0 = 0, th1 = 0, th2 = 0;
                 if (SER_PROBE >= 3) th0 = __builtin_amdgcn_s_memtime();
                 /* the successor: claimed and looked up first (waits that cover nothing but
@@ -1901,8 +1806,7 @@ ser_kernel(const SimArgs *Ap) {
                 const uint32_t ns = nl ? sel(k) : 0u;
                 if (nl && serfmt) load_rec(ns);
                 if (SER_PROBE >= 3) { __builtin_amdgcn_s_waitcnt(0); th1 = __builtin_amdgcn_s_memtime(); }
-#if SIM_TAILPROBE == 2
-                {   /* probe: the longest system, and the duration of the system that ends last */
+                if constexpr (SIM_TAILPROBE == 2) {   /* probe: the longest system, and the duration of the system that ends last */
                     const uint64_t dur = (uint64_t)(now_it - tclaim);
                     const uint64_t a = (dur << 32) | (uint64_t)sys;
                     const uint64_t b = ((uint64_t)now_it << 32) | ((uint64_t)lone0 << 31) | dur;
@@ -1915,7 +1819,6 @@ ser_kernel(const SimArgs *Ap) {
                     tclaim = now_it;
                     lone0 = nl && serfmt && (rr[30].y & 0x100u);
                 }
-#endif
                 finish(v);
                 if (SER_PROBE >= 3) { __builtin_amdgcn_s_waitcnt(0); th2 = __builtin_amdgcn_s_memtime(); }
                 live = nl;
@@ -1945,7 +1848,7 @@ ser_kernel(const SimArgs *Ap) {
         if (SER_PROBE >= 2) tr0 = __builtin_amdgcn_s_memtime();
         refill();
         (void)tr0;
-        if (!(SER_SOLO && !CAP)) iters += SER_RF;
+        if (!SOLO) iters += SER_RF;
         if (__ballot(live) == 0) break;
     }
 #if SIM_TAILPROBE == 2
@@ -1969,7 +1872,7 @@ ser_kernel(const SimArgs *Ap) {
     if (lane == 0) {
         atomicAdd(&s_cnt[K_WROUNDS], (unsigned long long)iters);
         atomicAdd(&Ap->counters[K_SERIT], (unsigned long long)iters);
-        if (SER_PROBE && SER_SOLO && !CAP && !SIM_TAILPROBE) {
+        if (SER_PROBE && SOLO && !SIM_TAILPROBE) {
             /* probe build: runs, steps taken in runs, lane-steps idle in runs (8 per running
              * lane less the steps), and at SER_PROBE >= 2 the runs' cycles */
             atomicAdd(&Ap->counters[K_SERPROBE], (unsigned long long)pb_runs);
@@ -2452,22 +2355,14 @@ static const char *build_variant() {
     auto add = [&](const char *name, long v, long def) {
         if (v != def && n < (int)sizeof tag) n += snprintf(tag + n, sizeof tag - n, " %s=%ld", name, v);
     };
-    add("SIM_BF", SIM_BF, 0);
     add("REC_PROBE", REC_PROBE, 0);
-    add("SIM_UNI", SIM_UNI, 1);
-    add("SIM_RFL", SIM_RFL, 1);
-    add("SIM_R2", SIM_R2, 0);
     add("SIM_TAILPROBE", SIM_TAILPROBE, 0);
     add("TRAFFIC_PROBE", TRAFFIC_PROBE, 0);
     add("SER_PROBE", SER_PROBE, 0);
     add("SER_HB", SER_HB, 8);
     add("SER_HT", SER_HT, 32);
-    add("SER_RF_DEF", SER_RF_DEF, 8);
-    add("SER_MACRO_DEF", SER_MACRO_DEF, 1);
-    add("SER_SOLO", SER_SOLO, 1);
     add("SER_SOLO_MIN", SER_SOLO_MIN, 48);
     add("SER_SOLO_HW", SER_SOLO_HW, 4);
-    add("FF_LONG", FF_LONG, 1);
     add("FF_LONG_U", FF_LONG_U, 8);
     add("SER_DEAD_FWD", SER_DEAD_FWD, 1);
     add("SER_NOTICE_HOME", SER_NOTICE_HOME, 1);

@@ -262,7 +262,7 @@ enum : uint32_t {
 #define W1_O1(x) ((uint32_t)(x) << 27)     /* second word: 0 none, 1 RREQ, 2 WREQ, 3 UPGRADE  */
 #define W1_BSEL(x) ((uint32_t)(x) << 29)   /* the dir bv base again, as a byte-permute selector
                                             * over {0 (bytes 4-7), Y (bytes 0-3)}: 2 Db, 3 Db &
-                                            * ~sbit, 4 zero -- one v_perm_b32 (DT_BSEL)       */
+                                            * ~sbit, 4 zero -- one v_perm_b32                 */
 
 /* The 0xFF gates of dt_entry are resolved here.  A line leaves INVALID only by being filled
  * (line.address = a <= 0x7F), and line.address never returns to 0xFF, so a valid line never
@@ -361,11 +361,9 @@ DSM_HD void dt_decode(uint32_t w, uint32_t *a, uint32_t *v, uint32_t *excl, uint
  * (a & b) | c is 0xEA).  On gfx950 it issues at full rate with VGPR or inline-constant
  * operands, where the v_or3_b32 / v_and_or_b32 the compiler picks for the same expressions
  * issue at half rate (tools/calib/valu_rate.hip); the transition round is bound by its VALU
- * issue, so the datapath's three-way combinations are stated with it (DT_B3). */
-#ifndef DT_B3
-#define DT_B3 1
-#endif
-#if defined(__HIP_DEVICE_COMPILE__) && DT_B3
+ * issue, so the datapath's three-way combinations are stated with it (the host build
+ * evaluates the truth table bit by bit). */
+#ifdef __HIP_DEVICE_COMPILE__
 #define dt_b3(a, b, c, tt) __builtin_amdgcn_bitop3_b32((a), (b), (c), (tt))
 #else
 DSM_HD uint32_t dt_b3(uint32_t a, uint32_t b, uint32_t c, uint32_t tt) {
@@ -377,9 +375,6 @@ DSM_HD uint32_t dt_b3(uint32_t a, uint32_t b, uint32_t c, uint32_t tt) {
 }
 #endif
 #define DT_OR3 0xFEu
-#ifndef DT_BSEL
-#define DT_BSEL 1
-#endif
 
 /* bit-field extract; width 0 gives 0 (v_bfe_u32) */
 DSM_HD uint32_t dt_ubfe(uint32_t x, uint32_t lo, uint32_t w) {
@@ -453,14 +448,9 @@ DSM_HD DtOut dt_apply_xy(const DtIn &in, uint32_t X, uint32_t Y, uint32_t W0, ui
     o.S = S;
     o.nLs = S & 0xFFu;
     o.nDs = S >> 24;
-#if DT_BSEL
     /* the base byte picked from Y = {pend, Mv, Db, Db & ~sbit} by the entry's selector: one
      * half-rate permute where the two-level select took two compares and two selects */
     const uint32_t base = dt_perm(0u, Y, (W1 >> 29) | 0x0C0C0C00u);
-#else
-    const uint32_t db = (W1 >> 5) & 3u;
-    const uint32_t base = (db & 2u) ? 0u : (db ? (evDb & 0xFFu) : in.Db);
-#endif
     o.nDb = base | ((W1 & W1_ORS) ? sbit : 0u) | ((W1 & W1_ORR) ? (1u << in.r2) : 0u);
     /* first outgoing word: payload and address bytes by one permute of {P, X} (payload =
      * P byte 3; address = X byte 0 (a) or byte 2 (La), per W1_O0LA at selector bit 9),
@@ -471,12 +461,7 @@ DSM_HD DtOut dt_apply_xy(const DtIn &in, uint32_t X, uint32_t Y, uint32_t W0, ui
     const bool d0 = dc & 1u, d1 = dc & 2u, d2 = dc & 4u;
     const uint32_t ctzEv = (uint32_t)__builtin_ctz((evDb & in.np_mask) | 0x80000000u);
     const uint32_t own = (uint32_t)__builtin_ctz((in.Db & in.np_mask) | 0x80000000u);  /* findOwner */
-#if defined(SIM_BF) && (SIM_BF & 2)
-    const uint32_t m1s = 0u - (uint32_t)d1;                    /* no branch on d1 */
-    const uint32_t didx = ((d0 ? ctzEv : (in.La >> 4)) & m1s) | ((d0 ? own : in.s) & ~m1s);
-#else
     const uint32_t didx = d1 ? (d0 ? ctzEv : (in.La >> 4)) : (d0 ? own : in.s);
-#endif
     const uint32_t mset = d0 ? (in.v & in.np_mask & ~(1u << in.node)) : ((1u << H) | (1u << in.r2));
     const uint32_t dm = d2 ? mset : (1u << didx);
     /* a word is sent iff its destination mask is non-zero; the body of an unsent word is

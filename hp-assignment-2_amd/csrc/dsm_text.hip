@@ -346,12 +346,6 @@ DEVI uint32_t lowmask(uint32_t n) { return n >= 32u ? 0xFFFFFFFFu : (1u << n) - 
 #ifndef PARSE_OCC
 #define PARSE_OCC 6
 #endif
-#ifndef PARSE_TRANSPOSE
-#define PARSE_TRANSPOSE 1   /* newline mask by one 4 x 8 bit transpose: 8.23-8.36 vs 8.91-8.96 ms */
-#endif
-#ifndef PARSE_UNI
-#define PARSE_UNI 1         /* wave index, and so the file loop, uniform (readfirstlane) */
-#endif
 #ifndef PARSE_PROBE
 #define PARSE_PROBE 0       /* timing probes of the FAST pass (results invalid): 1 no decode, 2 decode
                                without the store, 3 decode with the chunk words from registers */
@@ -367,7 +361,7 @@ parse_kernel(const uint8_t *text, const uint64_t *off, uint64_t n_files, uint32_
      * compiler's uniformity analysis takes it as lane-varying, and with it the file index,
      * the window position and every loop over them (exec-masked loops, state in VGPRs) */
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wv = PARSE_UNI ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : threadIdx.x >> 6;
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     uint8_t *const st = s_txt[wv];
     /* FAST: every file; EXACT: the files FAST abandoned (flist[0 .. *fcount)) */
     const uint64_t nf = FAST ? n_files : (uint64_t)*fcount;
@@ -412,11 +406,11 @@ parse_kernel(const uint8_t *text, const uint64_t *off, uint64_t n_files, uint32_
             const uint32_t hi = base + BPL <= e0 ? BPL : (base < e0 ? e0 - base : 0u);
             const uint32_t fm = hi > lo ? (lowmask(hi) & ~lowmask(lo)) : 0u;
             uint32_t nl = 0;
-#if PARSE_TRANSPOSE
             if (4 * K == 8) {
                 /* word k's newline flags (bit 8i+7 of byte i) into bit 8i+k of one word, then
                  * that 4 x 8 bit matrix transposed to byte order (bit 4k+i) by four delta swaps
-                 * (the index bits rotated by two): fewer VALU than packing word by word */
+                 * (the index bits rotated by two): fewer VALU than packing word by word as the
+                 * general loop below does (8.23-8.36 vs 8.91-8.96 ms) */
 #pragma unroll
                 for (uint32_t k = 0; k < 8; ++k) {
                     const uint4 &q = v[k >> 2];
@@ -431,7 +425,6 @@ parse_kernel(const uint8_t *text, const uint64_t *off, uint64_t n_files, uint32_
                 tt = (nl ^ (nl >> 2)) & 0x0C0C0C0Cu;  nl ^= tt ^ (tt << 2);
                 tt = (nl ^ (nl >> 14)) & 0x0000CCCCu; nl ^= tt ^ (tt << 14);
             } else
-#endif
 #pragma unroll
             for (uint32_t k = 0; k < 4 * K; ++k) {       /* bytes == '\n', 4 at a time */
                 const uint4 &q = v[k >> 2];

@@ -31,7 +31,7 @@ names = ["iters", "iters_macro", "iters_one_action", "iters_chunk_miss", "iters_
          "lanes_not_quiet", "lanes_quiet_declined", "lanes_instr_not_at_hand", "iters_lt32_live",
          "cyc13", "cyc14", "cyc15", "cyc16"]
 d = {k: int(raw[i]) for i, k in enumerate(names)}
-# the run phase (SER_SOLO): slots 34-37; wave iterations and macro-steps of any build: 33, 32
+# the run phase: slots 34-37; wave iterations and macro-steps of any build: 33, 32
 d.update({k: int(raw[34 + i]) for i, k in enumerate(["solo_runs", "solo_steps", "solo_idle_lane_steps",
                                                       "cyc_solo_runs"])})
 d.update(ser_iterations=int(raw[33]), ser_macro_steps=int(raw[32]))
