@@ -3,6 +3,9 @@ scenarios.py): a contention ensemble, the hand-derived quirk scenarios tiled int
 and ROUTES, the table of engine routes (hp-assignment-2_amd/csrc/dsm_plan.h) with the evidence
 that each really ran.
 
+INSTANCE_CASES is the table of cases that launch every kernel instantiation the dispatch has
+(tests/test_instances_model.py, tests/test_gpu_instances.py).
+
 OBSERVER_ROUTES is the table of the observer modes beside it (type counts, issue trace and seeded
 stalls combined, at both fast rings and with limits that end systems), and storm() the one-home
 inputs for the type counters' field width.
@@ -358,6 +361,114 @@ def storm(name, np_=8):
         t[0, nd] = {"read_two_lines": alt, "write_one_line": 0x8000 | val,
                     "write_two_lines": 0x8000 | alt | val}[name]
     return t, np.full((1, np_), STORM_INSTR, dtype=np.uint32)
+
+
+# ---- kernel instantiations ---------------------------------------------------------------------
+# INSTANCE_CASES: the cases that between them launch, with work, every kernel instantiation the
+# dispatch has (tests/model/plan_model.cpp `instances`: 96 fast sim_kernel, 32 re-run kernels, 4
+# ser_kernel, 2 order_kernel, 2 ffscan_kernel).  tests/test_instances_model.py proves on the CPU
+# that the union is complete; tests/test_gpu_instances.py runs the cases no other module runs.
+# Entries as in ROUTES, plus
+#   entry    "packed" (run_packed on contention(np, SEED, N_CONTENTION)) or "generated"
+#            (run_generated on GEN_ENSEMBLE: the fused generator takes no packed traces)
+#   claims   the passes of the plan (plan_model `launches`: fast, resume with order_kernel, rerun,
+#            scan) whose kernels this case is the evidence for.  "rerun" is claimed by one-pass
+#            ring-4 cases only; the AUTO pair claims only the trace scan (which kernels it picks
+#            is the device's verdict; the FF_OFF / FF_ON cases cover both halves)
+#   reuse    "ROUTES" / "OBSERVER_ROUTES": tests/test_gpu_routes.py / tests/test_gpu_observers.py
+#            run this entry on the contention ensemble at both node counts already
+#   late     (resumed must exceed the systems that reach the full budget) for the late budget
+# The generated ensemble, picked with the oracle (tests/test_instances_model.py measures it):
+# uniform, seed 3, 253 instructions (the last 16-byte chunk of the 256-slot stride is ragged),
+# systems 700 .. 4792 (4,093 of them: a ragged last workgroup).
+GEN_ENSEMBLE = dict(dist="uniform", seed=3, n_instr=253, first=700, n=4093)
+GEN_STRIDE = 256
+_GSIM = "sim_kernel<{np}, {ring}, 4, true, %d, 5>"
+LATE_BUDGET = (5, 2)     # set_budget(5, 2): 2^5 rounds, 2^2 once a wave finds no new system
+
+
+def _instance(route, entry="packed", claims=("fast",), reuse=None, late=False):
+    return dict(route, entry=entry, claims=tuple(claims), reuse=reuse, late=late)
+
+
+def _gen_case(mode, ring):
+    """The fused generator under MODE `mode` (M_TC | M_TR | M_SX, or 8: a run-time round limit)."""
+    tc, tr, sx = bool(mode & 1), bool(mode & 2), bool(mode & 4)
+    engine = dict(ring_cap=ring)
+    if tc:
+        engine["type_counts"] = True
+    if tr:
+        engine["issue_trace"] = True
+    setters = [("set_schedule", (STALL_SEED, STALL_THRESH))] if sx else []
+    info = dict(kernels="run=" + _GSIM % mode, ff_picked=int(mode in (0, 1, 8)), budget_mode=mode,
+                ring_cap=ring, **_ONE_PASS)
+    if mode == 8:
+        setters.append(("set_round_limit", (LIMIT_LOG2,)))
+        info["round_limit_log2"] = LIMIT_LOG2
+    return _instance(_route(engine=engine, setters=setters, info=info, zero=("resumed", "ser_macro_steps"),
+                            compare="stalls" if sx else "lockstep"),
+                     entry="generated", claims=("fast", "rerun") if ring == 4 else ("fast",))
+
+
+def _packed_one_pass(mode, ring, setters, ff_picked, counters=(), limit=0):
+    info = dict(kernels=_one(mode), ff_picked=ff_picked, budget_mode=mode, ring_cap=ring, **_ONE_PASS)
+    if limit:
+        info["round_limit_log2"] = limit
+    return _instance(_route(engine=dict(ring_cap=ring), setters=setters + [("set_budget", (0, 0))],
+                            info=info, counters=counters, zero=("resumed", "ser_macro_steps")),
+                     claims=("fast", "rerun") if ring == 4 else ("fast",))
+
+
+def _late(serial, budget=LATE_BUDGET, late=True):
+    blog, llog = budget
+    info = dict(ff_picked=0, budget_rounds=1 << blog, budget_log2=blog,
+                late_log2=llog if llog < blog else 0, ser_cap=0, ring_cap=12)
+    if serial:
+        info.update(kernels=_two(48, "false"), resume_form=2, budget_mode=48, resume_mode=-1)
+    else:
+        info.update(kernels=_two(16, 16), resume_form=1, budget_mode=16, resume_mode=16)
+    return _instance(_route(env=dict(_LONE, DSM_SERIAL="1") if serial else {"DSM_SERIAL": "0"},
+                            setters=[("set_fast_forward", ("FF_OFF",)), ("set_budget", budget)],
+                            info=info, counters=("resumed",)),
+                     claims=("fast", "resume"), late=late)
+
+
+def _route_claims(route, ring_rerun):
+    if route["info_ff"]:
+        return ("scan",)
+    claims = ("fast", "resume") if route["info"]["resume_form"] else ("fast",)
+    return claims + (("rerun",) if ring_rerun else ())
+
+
+INSTANCE_CASES = {}
+for _n, _r in ROUTES.items():
+    INSTANCE_CASES["routes/" + _n] = _instance(
+        _r, claims=_route_claims(_r, _n == "one_pass_plain_ring4"), reuse="ROUTES")
+for _n, _r in OBSERVER_ROUTES.items():
+    _, _, _, _lim, _inb = observers(_r)
+    INSTANCE_CASES["observers/" + _n] = _instance(
+        _r, claims=_route_claims(_r, _r["info"]["ring_cap"] == 4 and not _lim and _inb == 256),
+        reuse="OBSERVER_ROUTES")
+INSTANCE_CASES.update({
+    # packed traces: the run-time-limit kernel at ring 4; the two bench kernels at the rings only
+    # they have (8, 16), and the fast-forward one at ring 4
+    "packed_limits_ring4": _packed_one_pass(8, 4, [("set_round_limit", (LIMIT_LOG2,))], 1, limit=LIMIT_LOG2),
+    "packed_plain_ring8": _packed_one_pass(16, 8, [("set_fast_forward", ("FF_OFF",))], 0),
+    "packed_plain_ring16": _packed_one_pass(16, 16, [("set_fast_forward", ("FF_OFF",))], 0),
+    "packed_ff_ring4": _packed_one_pass(0, 4, [("set_fast_forward", ("FF_ON",))], 1, counters=("ff_steps",)),
+    "packed_ff_ring8": _packed_one_pass(0, 8, [("set_fast_forward", ("FF_ON",))], 1, counters=("ff_steps",)),
+    "packed_ff_ring16": _packed_one_pass(0, 16, [("set_fast_forward", ("FF_ON",))], 1, counters=("ff_steps",)),
+    # the late budget: under the serial resume, under the lock-step resume, and off (late >= budget)
+    "late_serial": _late(True),
+    "late_lockstep": _late(False),
+    "late_not_below_budget": _late(False, budget=(LATE_BUDGET[0], LATE_BUDGET[0]), late=False),
+})
+# the fused generator: MODE 0 at every ring, the observer MODEs and the run-time-limit one (8) at
+# rings 4 and 12
+for _m in range(9):
+    for _ring in ((4, 8, 12, 16) if _m == 0 else (4, 12)):
+        INSTANCE_CASES[f"generated_mode{_m}_ring{_ring}"] = _gen_case(_m, _ring)
+assert len(INSTANCE_CASES) == len(ROUTES) + len(OBSERVER_ROUTES) + 9 + 20
 
 
 def route_info(route, np_, ff=False):

@@ -8,6 +8,9 @@
  * and the launch info of the configurations the other tests and the benchmark rely on.
  *
  *   plan_model  -> JSON {"cases", "rows"}; exit 1 with the first failing case on stderr
+ *   plan_model info key=value ...      the launch info of one configuration
+ *   plan_model instances               every kernel instantiation the dispatch can launch
+ *   plan_model launches key=value ...  a configuration's launches, each with its instantiation
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -291,20 +294,16 @@ int rows() {
     return n;
 }
 
-/* plan_model info key=value ...: the launches and the launch info of one configuration (the
- * fields of PlanIn by name, over base(); verdict=0/1), as JSON, with the kernel label
- * dsm_launch_kernel_names makes of it.  tests/test_routes_model.py derives the evidence of
- * tests/adversarial.py's route table from it. */
-int info(int argc, char **argv) {
-    PlanIn in = base();
-    int v = 0;
+/* the fields of PlanIn by name, over base(): key=value ... (verdict=0/1 too) */
+bool parse_in(int argc, char **argv, PlanIn &in, int &v) {
     for (int i = 2; i < argc; ++i) {
         char *eq = strchr(argv[i], '=');
-        if (!eq) return 2;
+        if (!eq) return false;
         const std::string k(argv[i], eq - argv[i]);
         const long x = strtol(eq + 1, nullptr, 0);
         if (k == "np") in.np = (int)x;
         else if (k == "ring") in.ring = (int)x;
+        else if (k == "gen") in.gen = x != 0;
         else if (k == "tc") in.tc = x != 0;
         else if (k == "tr") in.tr = x != 0;
         else if (k == "sx") in.sx = x != 0;
@@ -319,11 +318,14 @@ int info(int argc, char **argv) {
         else if (k == "lone_min") in.lone_min = (uint32_t)x;
         else if (k == "n") in.n_sys = (uint64_t)x;
         else if (k == "verdict") v = x != 0;
-        else return 2;
+        else return false;
     }
-    const Plan p = make(in, v);
-    const dsm_launch_info li = plan_info(p, v != 0);
-    char b[2][96], label[256];
+    return true;
+}
+
+/* the launch info as JSON fields, with the kernel label dsm_launch_kernel_names makes of it */
+std::string info_json(const Plan &p, const dsm_launch_info &li) {
+    char b[2][96], label[256], out[1024];
     auto sim = [&](char *o, int m) {
         snprintf(o, 96, "sim_kernel<%d, %d, %d, %s, %d, %d>", li.np, li.ring_cap, li.block_threads / 64,
                  li.gen ? "true" : "false", m, li.occ);
@@ -336,11 +338,99 @@ int info(int argc, char **argv) {
         else snprintf(b[1], 96, "ser_kernel<%d, %s>", li.np, li.ser_cap ? "true" : "false");
         snprintf(label, sizeof label, "budget=%s resume=%s", b[0], b[1]);
     }
-    printf("{\"launches\": \"%s\", \"pair\": %d, \"kernels\": \"%s\", \"budget_mode\": %d, \"resume_mode\": %d, "
-           "\"resume_form\": %d, \"ff_picked\": %d, \"budget_rounds\": %d, \"budget_log2\": %d, \"ser_cap\": %d, "
-           "\"ring_cap\": %d, \"round_limit_log2\": %d}\n", launches(p).c_str(), p.pair ? 1 : 0, label,
-           li.budget_mode, li.resume_mode, li.resume_form, li.ff_picked, li.budget_rounds, li.budget_log2,
-           li.ser_cap, li.ring_cap, li.round_limit_log2);
+    snprintf(out, sizeof out, "\"launches\": \"%s\", \"pair\": %d, \"kernels\": \"%s\", \"budget_mode\": %d, "
+             "\"resume_mode\": %d, \"resume_form\": %d, \"ff_picked\": %d, \"budget_rounds\": %d, "
+             "\"budget_log2\": %d, \"ser_cap\": %d, \"ring_cap\": %d, \"round_limit_log2\": %d, "
+             "\"late_log2\": %d, \"gen\": %d", launches(p).c_str(), p.pair ? 1 : 0, label, li.budget_mode,
+             li.resume_mode, li.resume_form, li.ff_picked, li.budget_rounds, li.budget_log2, li.ser_cap,
+             li.ring_cap, li.round_limit_log2, li.late_log2, li.gen);
+    return out;
+}
+
+/* plan_model info key=value ...: the launches and the launch info of one configuration, as
+ * JSON.  tests/test_routes_model.py derives the evidence of tests/adversarial.py's route table
+ * from it. */
+int info(int argc, char **argv) {
+    PlanIn in = base();
+    int v = 0;
+    if (!parse_in(argc, argv, in, v)) return 2;
+    const Plan p = make(in, v);
+    printf("{%s}\n", info_json(p, plan_info(p, v != 0)).c_str());
+    return 0;
+}
+
+/* ---- kernel instantiations --------------------------------------------------------------- */
+std::string sim_name(int np, int ring, int waves, bool gen, int mode, int occ) {
+    char b[96];
+    snprintf(b, sizeof b, "sim_kernel<%d, %d, %d, %s, %d, %d>", np, ring, waves, gen ? "true" : "false", mode, occ);
+    return b;
+}
+std::string np_name(const char *kernel, int np) {
+    char b[64];
+    snprintf(b, sizeof b, "%s<%d>", kernel, np);
+    return b;
+}
+std::string ser_name(int np, bool cap) {
+    char b[64];
+    snprintf(b, sizeof b, "ser_kernel<%d, %s>", np, cap ? "true" : "false");
+    return b;
+}
+
+/* the instantiation a launch of a plan is, as the dispatch picks it (dsm_engine.hip pick_fast,
+ * pick_fallback and run_engine's switch) */
+std::string launch_name(const Plan &p, const PlanLaunch &L) {
+    const int np = p.in.np;
+    switch (L.kernel) {
+    case PK_SCAN: return np_name("ffscan_kernel", np);
+    case PK_SIM: return sim_name(np, p.ring_eff, SIM_WAVES, p.in.gen, L.mode, SIM_OCC);
+    case PK_ORDER: return np_name("order_kernel", np);
+    case PK_SER: return ser_name(np, L.mode != 0);
+    case PK_RERUN: return sim_name(np, FB_RING, 1, p.in.gen, L.mode, 1);
+    case PK_DIGEST: return np_name("digest_kernel", np);
+    }
+    return "";
+}
+
+/* plan_model instances: every instantiation of the transition, serial, ordering and trace-scan
+ * kernels the dispatch can launch, one per line: sim_instantiated over SIM_MODES, the rings, the
+ * node counts and the entries; the eight 256-deep re-run kernels; ser_kernel in both builds;
+ * order_kernel; ffscan_kernel */
+int instances() {
+    const int nps[] = {4, 8}, rings[] = {4, 8, 12, 16};
+    for (int np : nps) {
+        for (int gen = 0; gen < 2; ++gen) {
+            for (int i = 0; i < SIM_NMODES; ++i) for (int ring : rings)
+                if (sim_instantiated(gen != 0, ring, SIM_MODES[i]))
+                    puts(sim_name(np, ring, SIM_WAVES, gen != 0, SIM_MODES[i], SIM_OCC).c_str());
+            for (int m = 0; m < 8; ++m) puts(sim_name(np, FB_RING, 1, gen != 0, m, 1).c_str());
+        }
+        for (int cap = 0; cap < 2; ++cap) puts(ser_name(np, cap != 0).c_str());
+        puts(np_name("order_kernel", np).c_str());
+        puts(np_name("ffscan_kernel", np).c_str());
+    }
+    return 0;
+}
+
+/* plan_model launches key=value ...: the launches of one configuration in order, each with the
+ * instantiation it is, its pass and whether it does work under the plain ([0]) and the
+ * fast-forward ([1]) verdict of the trace scan; and the launch info under either verdict */
+int launch_list(int argc, char **argv) {
+    PlanIn in = base();
+    int v = 0;
+    if (!parse_in(argc, argv, in, v)) return 2;
+    const Plan p0 = make(in, 0), p1 = make(in, 1);
+    printf("{\"launches\": [");
+    for (int i = 0; i < p0.n_launch; ++i) {
+        const PlanLaunch &L = p0.launch[i];
+        const char *pass = L.kernel == PK_SCAN ? "scan" : L.kernel == PK_ORDER ? "order"
+                         : L.kernel == PK_RERUN ? "rerun" : L.kernel == PK_DIGEST ? "digest"
+                         : L.args == ARGS_RESUME ? "resume" : "fast";
+        printf("%s{\"kernel\": \"%s\", \"pass\": \"%s\", \"runs\": [%s, %s]}", i ? ", " : "",
+               launch_name(p0, L).c_str(), pass, runs(p0, L) ? "true" : "false",
+               runs(p1, p1.launch[i]) ? "true" : "false");
+    }
+    printf("], \"info\": [{%s}, {%s}]}\n", info_json(p0, plan_info(p0, false)).c_str(),
+           info_json(p1, plan_info(p1, true)).c_str());
     return 0;
 }
 
@@ -348,6 +438,8 @@ int info(int argc, char **argv) {
 
 int main(int argc, char **argv) {
     if (argc > 1 && !strcmp(argv[1], "info")) return info(argc, argv);
+    if (argc > 1 && !strcmp(argv[1], "instances")) return instances();
+    if (argc > 1 && !strcmp(argv[1], "launches")) return launch_list(argc, argv);
     const long cases = enumerate();
     printf("{\"cases\": %ld, \"rows\": %d}\n", cases, rows());
     return 0;

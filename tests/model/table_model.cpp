@@ -4,14 +4,17 @@
  * datapath), run over generated systems.  tests/test_table_model.py compares its per-system
  * results with the oracle's; this pins the transition table without a GPU.
  *
- *   table_model gen <np> <dist> <seed> <n_instr> <first> <n> <ring_cap> <out.bin> [rows_out [min_round]]
- *   table_model packed <np> <stride> <n> <traces.u16> <counts.u32> <ring_cap> <out.bin> [rows_out [min_round]]
+ *   table_model gen <np> <dist> <seed> <n_instr> <first> <n> <ring_cap> <out.bin> [rows_out [min_round [sched_seed sched_thresh]]]
+ *   table_model packed <np> <stride> <n> <traces.u16> <counts.u32> <ring_cap> <out.bin> [rows_out [min_round [sched_seed sched_thresh]]]
  * write n dsm_res records (oracle/dsm_common.h layout).  With rows_out, also the use of the
  * micro-op table: one text line per table row, "row op' sub actions systems" -- the row's
  * index, the name of its op' and its index among that op's rows, the number of node-actions
  * that took the row (every action of a round goes through dt_index, an idle node's too) and the
  * number of distinct systems with such an action -- counting only actions in rounds >
- * min_round (default 0: all).  tests/test_routes_model.py compares ensembles by it.
+ * min_round (default 0: all).  tests/test_routes_model.py compares ensembles by it.  With
+ * sched_seed and sched_thresh the rounds run under the seeded stall schedule (oracle/dsm_common.h
+ * dsm_sched_act, the system's id in the hash its index in the run): a node that has an action
+ * and stalls takes no row that round and keeps the round alive, as in oracle/dsm_oracle.c.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -53,7 +56,10 @@ struct Src {
     }
 };
 
-int run_one(Sys &y, const uint32_t *tab, const Src &src, dsm_res *res, Rows *rows, uint64_t sys_no) {
+struct Sched { uint64_t seed; uint32_t thresh; };
+
+int run_one(Sys &y, const uint32_t *tab, const Src &src, dsm_res *res, Rows *rows, uint64_t sys_no,
+            const Sched &sched) {
     const int np = y.np;
     const uint32_t npm = (1u << np) - 1u;
     for (int i = 0; i < np; ++i) {
@@ -70,6 +76,14 @@ int run_one(Sys &y, const uint32_t *tab, const Src &src, dsm_res *res, Rows *row
         for (int me = 0; me < np; ++me) {
             dsm_rec &s = y.n[me];
             uint32_t w = 0, op;
+            if (sched.thresh < DSM_SCHED_LOCKSTEP) {                /* exploration: may stall */
+                const bool avail = y.cnt[me] > 0 ||
+                    (!(s.flags & 1) && (s.issued < src.count(me) || !(s.flags & 2)));
+                if (avail && !dsm_sched_act(sched.seed, sched.thresh, sys_no, r, me)) {
+                    acted = 1;
+                    continue;
+                }
+            }
             if (y.cnt[me]) {
                 w = y.ring[me][y.head[me]];
                 y.head[me] = (y.head[me] + 1) % 256;
@@ -173,17 +187,22 @@ static uint8_t *slurp(const char *path, size_t *len) {
 }
 
 int main(int argc, char **argv) {
-    const bool gen = argc >= 10 && argc <= 12 && !strcmp(argv[1], "gen");
-    const bool packed = argc >= 9 && argc <= 11 && !strcmp(argv[1], "packed");
+    const bool gen = argc >= 10 && argc <= 14 && argc != 13 && !strcmp(argv[1], "gen");
+    const bool packed = argc >= 9 && argc <= 13 && argc != 12 && !strcmp(argv[1], "packed");
     if (!gen && !packed) {
-        fprintf(stderr, "usage: table_model gen np dist seed n_instr first n ring out [rows_out [min_round]]\n"
-                        "       table_model packed np stride n traces counts ring out [rows_out [min_round]]\n");
+        fprintf(stderr, "usage: table_model gen np dist seed n_instr first n ring out [rows_out [min_round [sched_seed sched_thresh]]]\n"
+                        "       table_model packed np stride n traces counts ring out [rows_out [min_round [sched_seed sched_thresh]]]\n");
         return 1;
     }
     const int fixed = gen ? 10 : 9;
     const char *rows_out = argc > fixed ? argv[fixed] : nullptr;
     Rows *rows = rows_out ? (Rows *)calloc(1, sizeof(Rows)) : nullptr;
     if (rows && argc > fixed + 1) rows->min_round = (uint32_t)strtoul(argv[fixed + 1], 0, 0);
+    Sched sched = {0, DSM_SCHED_LOCKSTEP};
+    if (argc > fixed + 3) {
+        sched.seed = strtoull(argv[fixed + 2], 0, 0);
+        sched.thresh = (uint32_t)strtoul(argv[fixed + 3], 0, 0);
+    }
     static uint32_t tab[DT_TABLE_WORDS];
     if (dt_build(tab) > DT_ENTRIES) {
         fprintf(stderr, "micro-op table rows exceed DT_ENTRIES\n");
@@ -206,7 +225,7 @@ int main(int argc, char **argv) {
         res = (dsm_res *)calloc(n ? n : 1, sizeof(dsm_res));
         for (uint64_t i = 0; i < n; ++i) {
             Src src = {nullptr, nullptr, 0, dist, seed, n_instr, first + i};
-            run_one(*y, tab, src, &res[i], rows, i);
+            run_one(*y, tab, src, &res[i], rows, i, sched);
         }
     } else {
         const uint32_t stride = (uint32_t)strtoul(argv[3], 0, 0);
@@ -221,7 +240,7 @@ int main(int argc, char **argv) {
         res = (dsm_res *)calloc(n ? n : 1, sizeof(dsm_res));
         for (uint64_t i = 0; i < n; ++i) {
             Src src = {tr + i * np * stride, cn + i * np, stride, 0, 0, 0, 0};
-            run_one(*y, tab, src, &res[i], rows, i);
+            run_one(*y, tab, src, &res[i], rows, i, sched);
         }
     }
     FILE *f = fopen(out, "wb");

@@ -135,7 +135,7 @@ def test_ring_capacity_and_overflow_rerun(dsm, orc, ring):
 def test_generator_kernel_matches_oracle(dsm, orc):
     import torch
     n = 64
-    for np_, dist in [(8, "uniform"), (8, "hot"), (8, "evict"), (4, "uniform")]:
+    for np_, dist in [(8, "uniform"), (8, "hot"), (8, "evict"), (4, "uniform"), (4, "hot"), (4, "evict")]:
         with dsm.Engine(np_, 4096) as eng:
             tr = torch.empty((n, np_, 4096), dtype=torch.int16, device="cuda")
             cn = torch.empty((n, np_), dtype=torch.int32, device="cuda")

@@ -20,7 +20,13 @@ packed command):
   (e) 4,047 completed / 12,337 deadlocked at 8 nodes, 7,672 / 8,712 at 4; 8 systems at 8 nodes
       pass a 12-deep inbox (RING_OVERFLOW at inbox 12);
   (f) the sha256 of traces and counts, asserted by tests/test_gpu_routes.py too;
-  (g)-(i), at the end of the file: the observer routes of tests/test_gpu_observers.py."""
+  (g)-(i), at the end of the file: the observer routes of tests/test_gpu_observers.py;
+  (j) under the seeded stalls (seed 11, threshold 0x8000, the system's index as its id: what the
+      stall routes of tests/test_gpu_routes.py and tests/test_gpu_observers.py run) table_model
+      equals the oracle on every system of the contention ensemble, and the rows reached are the
+      same 100 at 8 nodes, each in at least 8 systems; at 4 nodes the 100 plus FLUSH_INVACK/11
+      (one system) and without the lock-step run's FLUSH/11, and three rows are thin:
+      READ_REQUEST/4 in 3 systems, WRITE_REQUEST/4 in 2, FLUSH_INVACK/11 in 1."""
 import json
 import os
 import subprocess
@@ -39,6 +45,12 @@ GXX = ["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror"]
 MIN_SYSTEMS = 8
 # rows the contention ensemble reaches beyond the generator ensembles' set
 EXTRA_ROWS = {4: {"FLUSH/11"}, 8: set()}
+# (j): under the seeded stalls of the GPU tests (adv.STALL_SEED, adv.STALL_THRESH, first_sys 0)
+# the contention ensemble reaches the generator ensembles' lock-step set plus these ...
+EXTRA_ROWS_STALLS = {4: {"FLUSH_INVACK/11"}, 8: set()}
+# ... and these of them in fewer than MIN_SYSTEMS systems (row -> systems): the GPU's stall routes
+# (MODE 4-7) have that little evidence for them
+THIN_ROWS_STALLS = {4: {"READ_REQUEST/4": 3, "WRITE_REQUEST/4": 2, "FLUSH_INVACK/11": 1}, 8: {}}
 # (c): rows that by their nature occur only in the first rounds (at most 5 may be listed)
 EARLY_ONLY = {}
 # (d): decline reasons of ser_macro's `ok` expression no trace with homes < np can produce
@@ -117,11 +129,11 @@ def _generator_rows(table_model, tmp_path, np_, min_round=0):
     return rows
 
 
-def _packed_rows(table_model, tmp_path, np_, f, min_round=0):
+def _packed_rows(table_model, tmp_path, np_, f, min_round=0, sched=()):
     tp, cp, n, stride = f
     out, ro = str(tmp_path / "p.bin"), str(tmp_path / "p.rows")
     subprocess.run([table_model, "packed", str(np_), str(stride), str(n), tp, cp, "256", out, ro,
-                    str(min_round)], check=True)
+                    str(min_round)] + [str(x) for x in sched], check=True)
     return _rows(ro), np.fromfile(out, dtype=pyoracle.RES_DT)
 
 
@@ -139,7 +151,7 @@ def test_digest(np_):
 
 @pytest.mark.parametrize("np_", [4, 8])
 def test_rows_reached(table_model, files, tmp_path, np_):
-    """(a), (b), (c)"""
+    """(a), (b), (c), (j)"""
     gen = _generator_rows(table_model, tmp_path, np_)
     rows, res = _packed_rows(table_model, tmp_path, np_, files[("contention", np_)])
     print("generator rows", len(gen), "contention rows", len(rows), "extra", sorted(set(rows) - gen),
@@ -158,6 +170,17 @@ def test_rows_reached(table_model, files, tmp_path, np_):
     # the scenarios add no row (they pin quirks by hand-derived values instead)
     trows, _ = _packed_rows(table_model, tmp_path, np_, files[("tiled", np_)])
     assert set(trows) <= set(rows)
+    # (j) the same ensemble under the seeded stalls of the GPU's stall routes
+    srows, sres = _packed_rows(table_model, tmp_path, np_, files[("contention", np_)],
+                               sched=(adv.STALL_SEED, adv.STALL_THRESH))
+    so = pyoracle.run_packed_ex(np_, tr, cn, sched_seed=adv.STALL_SEED, sched_thresh=adv.STALL_THRESH,
+                                first_sys=0, nthreads=8)[0]
+    assert np.array_equal(sres, so)
+    assert not np.array_equal(sres, res)                     # the schedule was applied
+    thin = {k: v[1] for k, v in srows.items() if v[1] < MIN_SYSTEMS}
+    print("rows under the stalls", len(srows), "extra", sorted(set(srows) - gen), "thin", thin)
+    assert set(srows) == gen | EXTRA_ROWS_STALLS[np_]
+    assert thin == THIN_ROWS_STALLS[np_]
 
 
 @pytest.mark.parametrize("np_", [4, 8])
