@@ -9,6 +9,8 @@
 #   oracle/_ref/ref_lockstep_np4_i32_dbg  the same with DEBUG_INSTR (issue-order printf)
 #   oracle/_ref/ref_lockstep_np4       NUM_PROCS=4, MAX_INSTR_NUM=4096
 #   oracle/_ref/ref_lockstep_np8       NUM_PROCS=8, MAX_INSTR_NUM=4096
+#   oracle/_ref/ref_lockstep_np{4,8}_dbg  the two above with DEBUG_INSTR (`packed` leaves the
+#                                      issue lines on stdout)
 set -euo pipefail
 HERE="$(cd "$(dirname "$0")" && pwd)"
 REF="${REF:-/root/reference}"
@@ -39,5 +41,7 @@ gcc $CFLAGS -DNUM_PROCS=4 -DMAX_INSTR_NUM=32   "$HERE/ref_lockstep.c" -o "$OUT/r
 gcc $CFLAGS -DNUM_PROCS=4 -DMAX_INSTR_NUM=32 -DDEBUG_INSTR "$HERE/ref_lockstep.c" -o "$OUT/ref_lockstep_np4_i32_dbg"
 gcc $CFLAGS -DNUM_PROCS=4 -DMAX_INSTR_NUM=4096 "$HERE/ref_lockstep.c" -o "$OUT/ref_lockstep_np4"
 gcc $CFLAGS -DNUM_PROCS=8 -DMAX_INSTR_NUM=4096 "$HERE/ref_lockstep.c" -o "$OUT/ref_lockstep_np8"
+gcc $CFLAGS -DNUM_PROCS=4 -DMAX_INSTR_NUM=4096 -DDEBUG_INSTR "$HERE/ref_lockstep.c" -o "$OUT/ref_lockstep_np4_dbg"
+gcc $CFLAGS -DNUM_PROCS=8 -DMAX_INSTR_NUM=4096 -DDEBUG_INSTR "$HERE/ref_lockstep.c" -o "$OUT/ref_lockstep_np8_dbg"
 gcc -O2 -fopenmp "$SRC" -o "$OUT/cache_simulator_ref"
 echo "build_ref: built $(ls "$OUT" | tr '\n' ' ')"

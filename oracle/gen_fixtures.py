@@ -47,6 +47,28 @@ outputs.  Nothing written here is reference source text.
   tests/golden/dumps/random_md5.json           md5 + length of the reference's OWN
                                                printProcessorState text of each of them
                                                (oracle/_ref/ref_lockstep_np8 fmt)
+  tests/golden/adversarial/<variant>.npy       (python oracle/gen_fixtures.py adversarial)
+                                               per-system result digests (u64 [n],
+                                               dsm_common.h dsm_result_digest, idx = the
+                                               system's index) of the adversarial inputs --
+                                               the contention ensemble, the tiled scenarios,
+                                               the crafted lone-node inputs, the generated
+                                               ensemble (tests/adversarial.py,
+                                               tests/solo_inputs.py; the table of variants is
+                                               tests/reference_pins.py's) -- under the
+                                               lock-step schedule, seeded stalls, inbox and
+                                               round limits, from oracle/_ref/
+                                               ref_lockstep_np{4,8} packed
+  tests/golden/adversarial/<variant>_issue.npy per-system issue digests (u64 [n]: the first 8
+                                               bytes of the md5 of the system's DEBUG_INSTR
+                                               lines, oracle/_ref/ref_lockstep_np{4,8}_dbg)
+  tests/golden/adversarial/np8_uniform_2p40.npy  per-system results [1024, 6] of generated
+                                               systems (1 << 40) + 12345 .. (ref_lockstep gen)
+  tests/golden/adversarial/index.json          per variant: the input's sha256, producer,
+                                               schedule, limits, status counts, sums, hash
+                                               sums, the 13 per-type totals; the three one-home
+                                               storms' results and per-type counts; the far
+                                               fixture's parameters and reference aggregate
 """
 import concurrent.futures as cf
 import hashlib
@@ -379,6 +401,73 @@ def dumps():
     with open(os.path.join(d, "random_md5.json"), "w") as f:
         json.dump({"producer": "oracle/_ref/ref_lockstep_np8 fmt (assignment.c:824-876)",
                    "np": 8, "texts": out}, f, indent=0)
+
+
+def adversarial():
+    """tests/golden/adversarial: the adversarial inputs of tests/adversarial.py and
+    tests/solo_inputs.py through the reference's own handler text (ref_lockstep `packed`); the
+    table of variants and the digests are tests/reference_pins.py's."""
+    for p in (os.path.join(REPO, "tests"), HERE):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    import adversarial as adv
+    import pyoracle
+    import reference_pins as pins
+    d = pins.DIR
+    os.makedirs(d, exist_ok=True)
+    for np_ in pins.NPS:       # before anything runs: this numpy builds the certified ensemble
+        tr, cn, _ = adv.contention(np_, adv.SEED, adv.N_CONTENTION)
+        assert adv.digest(tr, cn) == adv.CONTENTION_SHA256[np_], np_
+    index = {"variants": {}, "storms": {}}
+    with tempfile.TemporaryDirectory() as tmp:
+        for v in pins.variants():
+            np_ = v["np"]
+            tr, cn = pins.inputs(v["kind"], np_, pyoracle)
+            seed, thresh = pins.sched(v)
+            kw = dict(seed=seed, thresh=thresh, cap=v["cap"], limit=v["limit"])
+            res, _, _, types = pins.run_ref_packed(pins.ref_exe(np_), np_, tr, cn, tmp, **kw)
+            assert (types.sum(axis=1) == res["msgs"]).all()
+            np.save(os.path.join(d, v["name"] + ".npy"), pins.digests(res))
+            if v["issue"]:
+                dres, _, _, _, lines = pins.run_ref_packed(pins.ref_exe(np_, True), np_, tr, cn, tmp,
+                                                           lines=True, **kw)
+                assert dres.tobytes() == res.tobytes()
+                np.save(os.path.join(d, v["name"] + "_issue.npy"),
+                        np.array([pins.text_digest(t) for t in lines], dtype=np.uint64))
+            e = dict(input_sha256=adv.digest(tr, cn), np=np_, kind=v["kind"], stride=int(tr.shape[2]),
+                     schedule=dict(seed=seed, thresh=thresh), cap=v["cap"], limit=v["limit"],
+                     producer=f"oracle/_ref/ref_lockstep_np{np_} packed (assignment.c handler/issue "
+                              f"text; the system's index is its schedule id)")
+            e.update(pins.summary(res, types))
+            index["variants"][v["name"]] = e
+            print("  ", v["name"], e["status"], flush=True)
+        for np_ in pins.NPS:
+            for name in adv.STORMS:
+                tr, cn = adv.storm(name, np_)
+                for stalls in (False, True):
+                    seed, thresh = pins.sched(dict(stalls=stalls))
+                    res, _, _, types = pins.run_ref_packed(pins.ref_exe(np_), np_, tr, cn, tmp,
+                                                           seed=seed, thresh=thresh)
+                    r = res[0]
+                    index["storms"][f"{name}_np{np_}_" + ("stalls" if stalls else "lockstep")] = dict(
+                        input_sha256=adv.digest(tr, cn), np=np_, schedule=dict(seed=seed, thresh=thresh),
+                        status=int(r["status"]), rounds=int(r["rounds"]), msgs=int(r["msgs"]),
+                        instrs=int(r["instrs"]), dump_hash="0x%016x" % int(r["dump_hash"]),
+                        final_hash="0x%016x" % int(r["final_hash"]), types=[int(x) for x in types[0]])
+        f = pins.FAR
+        out = os.path.join(tmp, "far.bin")
+        exe = os.path.join(REFBIN, f"ref_lockstep_np{f['np']}")
+        gen = [str(pyoracle.DIST[f["dist"]]), str(f["seed"]), str(f["n_instr"]), str(f["first_sys"]),
+               str(f["n_sys"])]
+        subprocess.run([exe, "gen"] + gen + [out], check=True)
+        res, _ = read_ref_bin(out, f["np"])
+        np.save(os.path.join(d, f["name"] + ".npy"), res_to_u64(res))
+        r = subprocess.run([exe, "agg"] + gen + ["4"], check=True, capture_output=True, text=True)
+        index["far"] = dict(f, aggregate=json.loads(r.stdout.strip().splitlines()[-1]),
+                            producer=f"oracle/_ref/ref_lockstep_np{f['np']} gen / agg (the digest takes "
+                                     f"the absolute system id)")
+    with open(os.path.join(d, "index.json"), "w") as fh:
+        json.dump(index, fh, indent=1, sort_keys=True)
 
 
 if __name__ == "__main__":

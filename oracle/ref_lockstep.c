@@ -23,6 +23,19 @@
  *   ref_lockstep tests <name> <out.bin> <seed> <thresh> <first> <n>
  *                                            (n seeded schedule-exploration variants; no files)
  *   ref_lockstep gen <dist> <seed> <n_instr> <first_sys> <n_sys> <out.bin>
+ *   ref_lockstep packed <stride> <n> <traces.bin> <counts.bin> <out.bin> [<seed> <thresh>]
+ *                                            (n systems of packed u16 instructions, installed
+ *                                            as gen installs its own; system k has schedule
+ *                                            id k; the schedule from the two arguments or
+ *                                            DSM_REF_SCHED_SEED / DSM_REF_SCHED_THRESH; per
+ *                                            system 13 u64 handled-message counts by type
+ *                                            follow the records; a DEBUG_INSTR build leaves
+ *                                            the issue lines on stdout.  Refuses a stride above
+ *                                            MAX_INSTR_NUM and any instruction whose home is
+ *                                            >= NUM_PROCS: the reference indexes out of bounds
+ *                                            there, and ST_ASSERT_FAILED for such an input is
+ *                                            this project's convention, not the reference's,
+ *                                            so those inputs stay with the oracle alone)
  *   ref_lockstep fmt <recs.bin> <out.bin>   (printProcessorState of 64-byte records)
  *   ref_lockstep bench <dist> <seed> <n_instr> <first> <n> <nproc>
  *                                            (CPU baseline: timed run_system, forked slices)
@@ -344,6 +357,82 @@ int main(int argc, char **argv) {
         rmdir("tests/empty"); rmdir("tests"); if (chdir("/")) {} rmdir(tmpl);
         return 0;
     }
+    if ((argc == 7 || argc == 9) && !strcmp(argv[1], "packed")) {
+        /* n systems of packed u16 instructions (traces [n, NUM_PROCS, stride], bit 15 WR,
+         * bits 8..14 address, bits 0..7 value; counts u32 [n, NUM_PROCS]), installed as `gen`
+         * installs the generator's.  System k runs under the schedule with id k. */
+        const int stride = atoi(argv[2]);
+        const uint64_t n = strtoull(argv[3], 0, 0);
+        if (stride < 1 || stride > MAX_INSTR_NUM) { fprintf(stderr, "packed: stride > MAX_INSTR_NUM\n"); return 1; }
+        if (argc == 9) {
+            g_sched_seed = strtoull(argv[7], 0, 0);
+            g_sched_thresh = (uint32_t)strtoul(argv[8], 0, 0);
+        } else {
+            const char *e = getenv("DSM_REF_SCHED_SEED");
+            if (e && *e) g_sched_seed = strtoull(e, 0, 0);
+            e = getenv("DSM_REF_SCHED_THRESH");
+            if (e && *e) g_sched_thresh = (uint32_t)strtoul(e, 0, 0);
+        }
+        const size_t per = (size_t)NUM_PROCS * (size_t)stride;
+        uint16_t *tr = malloc(n * per * sizeof *tr + 1);
+        uint32_t *cn = malloc(n * NUM_PROCS * sizeof *cn + 1);
+        FILE *ft = fopen(argv[4], "rb"), *fc = fopen(argv[5], "rb");
+        if (!tr || !cn || !ft || !fc || fread(tr, sizeof *tr, n * per, ft) != n * per ||
+            fread(cn, sizeof *cn, n * NUM_PROCS, fc) != n * NUM_PROCS) {
+            fprintf(stderr, "packed: cannot read %llu systems\n", (unsigned long long)n);
+            return 1;
+        }
+        fclose(ft); fclose(fc);
+        for (uint64_t s = 0; s < n; ++s)
+            for (int t = 0; t < NUM_PROCS; ++t) {
+                const uint32_t c = cn[s * NUM_PROCS + t];
+                if (c > (uint32_t)stride) { fprintf(stderr, "packed: count > stride (system %llu)\n", (unsigned long long)s); return 1; }
+                for (uint32_t i = 0; i < c; ++i)
+                    if (((tr[s * per + (size_t)t * stride + i] >> 12) & 7) >= NUM_PROCS) {
+                        fprintf(stderr, "packed: system %llu node %d instruction %u: home >= NUM_PROCS\n",
+                                (unsigned long long)s, t, i);
+                        return 1;
+                    }
+            }
+        FILE *f = fopen(argv[6], "wb");
+        if (!f) { perror("open out"); return 1; }
+        char tmpl[] = "/tmp/reflsXXXXXX";
+        if (!mkdtemp(tmpl) || chdir(tmpl)) { perror("scratch"); return 1; }
+        mkdir("tests", 0700); mkdir("tests/empty", 0700);
+        for (int t = 0; t < NUM_PROCS; ++t) {
+            char p[64]; snprintf(p, sizeof p, "tests/empty/core_%d.txt", t);
+            FILE *e = fopen(p, "w"); if (e) fclose(e);
+        }
+#ifndef DEBUG_INSTR
+        if (!freopen("/dev/null", "w", stdout)) return 1;
+#endif
+        for (uint64_t s = 0; s < n; ++s) {
+            g_sys = s;
+            for (int t = 0; t < NUM_PROCS; ++t) {
+                reset_ctx(t);
+                initializeProcessor(t, &C[t].node, "empty");
+                const uint16_t *w = tr + s * per + (size_t)t * stride;
+                const int c = (int)cn[s * NUM_PROCS + t];
+                for (int i = 0; i < c; ++i) {
+                    C[t].node.instructions[i].type = (w[i] >> 15) ? 'W' : 'R';
+                    C[t].node.instructions[i].address = (byte)((w[i] >> 8) & 0x7F);
+                    C[t].node.instructions[i].value = (byte)(w[i] & 0xFF);
+                }
+                C[t].node.instructionCount = c;
+            }
+            run_system(&res, dump, fin);
+            write_sys(f, &res, dump, fin);
+            fwrite(g_sys_types, sizeof g_sys_types[0], 13, f);
+        }
+        fclose(f);
+        fflush(stdout);
+        for (int t = 0; t < NUM_PROCS; ++t) {
+            char p[64]; snprintf(p, sizeof p, "tests/empty/core_%d.txt", t); unlink(p);
+        }
+        rmdir("tests/empty"); rmdir("tests"); if (chdir("/")) {} rmdir(tmpl);
+        free(tr); free(cn);
+        return 0;
+    }
     if (argc == 8 && (!strcmp(argv[1], "bench") || !strcmp(argv[1], "agg"))) {
         /* bench: CPU baseline -- the reference's own handler text under the lock-step
          * schedule over systems first .. first+n-1 of the generator, in nproc forked
@@ -483,6 +572,6 @@ int main(int argc, char **argv) {
         rmdir(tmpl);
         return 0;
     }
-    fprintf(stderr, "usage: %s tests <name> <out.bin> | gen <dist> <seed> <n_instr> <first> <n> <out.bin> | fmt <recs.bin> <out.bin>\n", argv[0]);
+    fprintf(stderr, "usage: %s tests <name> <out.bin> | gen <dist> <seed> <n_instr> <first> <n> <out.bin> | packed <stride> <n> <traces.bin> <counts.bin> <out.bin> [<seed> <thresh>] | fmt <recs.bin> <out.bin>\n", argv[0]);
     return 2;
 }

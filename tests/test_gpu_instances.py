@@ -31,6 +31,7 @@ import numpy as np
 import pytest
 
 import adversarial as adv
+import reference_pins as pins
 from test_gpu_routes import _apply, _check_records, _check_results, _open
 from test_instances_model import ensemble
 
@@ -90,7 +91,9 @@ def ensembles():
 def reference(orc, ensembles):
     """The oracle's run of an ensemble under a schedule and limits at an inbox depth, once per
     (entry, np, stalls, round limit in rounds, inbox): results, dump and final records, every
-    system's issue events and their number (the generated ensemble only), per-type message counts."""
+    system's issue events and their number (the generated ensemble only), per-type message counts.
+    Where tests/golden/adversarial holds the reference's run of it (tests/reference_pins.py), the
+    oracle's is that run."""
     cache = {}
 
     def get(entry, np_, sx=False, limit=0, inbox=256):
@@ -100,6 +103,7 @@ def reference(orc, ensembles):
             sched = dict(sched_seed=adv.STALL_SEED, sched_thresh=adv.STALL_THRESH) if sx else {}
             out = orc.run_packed_ex_types(np_, tr, cn, first_sys=0, ring_cap=inbox, round_limit=limit,
                                           issue=entry == "generated", nthreads=16, **sched)
+            pins.pinned(entry, np_, sx, inbox, limit, out[0])
             for a in out:
                 if a is not None:
                     a.setflags(write=False)

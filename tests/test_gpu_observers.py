@@ -25,6 +25,7 @@ import numpy as np
 import pytest
 
 import adversarial as adv
+import reference_pins as pins
 import test_gpu_routes as R
 from conftest import res_to_u64
 from test_gpu_routes import dsm, ensembles, orc  # noqa: F401  (fixtures)
@@ -38,7 +39,8 @@ SCHED = dict(sched_seed=adv.STALL_SEED, sched_thresh=adv.STALL_THRESH)
 def observed(orc, ensembles):
     """The oracle's run of an ensemble under a schedule and limits, once per (kind, np, stalls,
     round limit, inbox limit): results, dump and final records, every system's issue events and
-    per-type message counts."""
+    per-type message counts.  Where tests/golden/adversarial holds the reference's run under that
+    schedule and those limits (tests/reference_pins.py), the oracle's is that run."""
     cache = {}
 
     def get(kind, np_, sx=False, limit=0, inbox=256):
@@ -47,6 +49,7 @@ def observed(orc, ensembles):
             tr, cn, _ = ensembles(kind, np_)
             out = orc.run_packed_ex_types(np_, tr, cn, first_sys=0, ring_cap=inbox, round_limit=limit,
                                           issue=True, nthreads=16, **(SCHED if sx else {}))
+            pins.pinned(kind, np_, sx, inbox, limit, out[0])
             for a in out:
                 a.setflags(write=False)
             cache[key] = out

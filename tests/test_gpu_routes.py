@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 import adversarial as adv
+import reference_pins as pins
 import scenarios
 from conftest import res_to_u64
 
@@ -68,7 +69,8 @@ def ensembles():
 @pytest.fixture(scope="module")
 def reference(orc, ensembles):
     """The oracle's run of an ensemble, once per (kind, np, compare, inbox limit):
-    results, dump and final records, issue events (compare "issue")."""
+    results, dump and final records, issue events (compare "issue").  Where tests/golden/adversarial
+    holds the reference's run of it (tests/reference_pins.py), the oracle's is that run."""
     cache = {}
 
     def get(kind, np_, compare="lockstep", cap=256):
@@ -84,6 +86,7 @@ def reference(orc, ensembles):
                 res, dump, fin, ev, evn = orc.run_packed_ex(
                     np_, tr, cn, sched_seed=adv.STALL_SEED, sched_thresh=adv.STALL_THRESH,
                     first_sys=0, nthreads=16)
+            pins.pinned(kind, np_, compare == "stalls", cap, 0, res)
             for a in (res, dump, fin):
                 a.setflags(write=False)
             cache[key] = (res, dump, fin, ev, evn)

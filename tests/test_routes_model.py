@@ -36,6 +36,7 @@ import pytest
 
 import adversarial as adv
 import pyoracle
+import reference_pins as pins
 import scenarios
 from conftest import REPO
 
@@ -448,7 +449,9 @@ def test_observer_limits_bite(observer_oracle, np_):
 
 def test_storm_counts():
     """(i): the largest count of one message type at one node, for the 16-bit fields of the
-    kernel's per-lane type counters (dsm_engine.hip, tc[7])."""
+    kernel's per-lane type counters (dsm_engine.hip, tc[7]).  The counts are the oracle's and, from
+    tests/golden/adversarial, those of the reference's own handler text."""
+    stored = pins.index()["storms"]
     top = {}
     for name in adv.STORMS:
         tr, cn = adv.storm(name)
@@ -457,6 +460,9 @@ def test_storm_counts():
             sched = dict(sched_seed=adv.STALL_SEED, sched_thresh=adv.STALL_THRESH) if sx else {}
             res, _, _, _, _, bt = pyoracle.run_packed_ex_types(8, tr, cn, **sched)
             assert int(bt[0].sum()) == int(res[0]["msgs"])
+            ref = stored[f"{name}_np8_" + ("stalls" if sx else "lockstep")]
+            assert ref["input_sha256"] == adv.digest(tr, cn)
+            assert bt[0].tolist() == ref["types"] and pins.storm_fields(res[0]) == {k: ref[k] for k in pins.STORM_KEYS}
             print(name, "stalls" if sx else "lockstep", "instrs", int(res[0]["instrs"]),
                   "status", int(res[0]["status"]) & 0xFF, dict(zip(range(13), bt[0].tolist())))
             top[(name, sx)] = (int(res[0]["instrs"]), bt[0])
