@@ -240,7 +240,8 @@ int dsm_run_packed_device(dsm_ctx *ctx, const uint16_t *d_traces, const uint32_t
                           dsm_counters *d_counters, void *stream);
 
 /* GPU trace generator: writes d_traces [n_sys][np][max_instr] and d_counts [n_sys][np]
- * for systems first_sys .. first_sys+n_sys-1 (requires gen->n_instr <= max_instr). */
+ * for systems first_sys .. first_sys+n_sys-1 (requires gen->n_instr <= max_instr).  Every
+ * slot is written whole: the instructions past n_instr are zero. */
 int dsm_generate_device(dsm_ctx *ctx, const dsm_gen *gen, uint64_t first_sys, uint64_t n_sys,
                         uint16_t *d_traces, uint32_t *d_counts, void *stream);
 
@@ -331,7 +332,8 @@ int dsm_parse_traces(dsm_ctx *ctx, const char *text, const uint64_t *offsets, ui
 /* Synthetic core files in the shipped tests' format ("RD 0x%02x\n", "WR 0x%02x %u\n") for
  * the generator's instructions of systems first_sys .. first_sys+n_sys-1.  Always writes
  * d_offsets (n_sys*np + 1 entries; the last one is the total size); writes the text too
- * unless d_text is NULL (size query). */
+ * unless d_text is NULL (size query).  It writes no trace slots, so gen->n_instr is bounded
+ * by DSM_MAX_INSTR alone, not by the ctx's max_instr. */
 int dsm_generate_text_device(dsm_ctx *ctx, const dsm_gen *gen, uint64_t first_sys, uint64_t n_sys,
                              char *d_text, uint64_t *d_offsets, void *stream);
 
