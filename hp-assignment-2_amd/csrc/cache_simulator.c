@@ -23,16 +23,133 @@
  *                    (:595-598), as the schedule issued the instructions
  *   --schedule S:T   seeded schedule exploration (dsm_set_schedule): seed S, act threshold T
  *                    (0..65536; 65536 = lock-step); samples the reference's interleavings
+ *   --explore N      outcome census instead of one run: N (1..1048576) seeded interleavings of
+ *                    the system in one launch (variant i is system i of the run, so its stall
+ *                    pattern is schedule S's for index i), grouped on the GPU by outcome
+ *                    (dsm_census_device) and per core by dump (dsm_census_run_nodes_device).
+ *                    Without --schedule the seed is 0 and the threshold 32768.  Not valid with
+ *                    --issue-order.  Prints
+ *                        explored N schedules (seed S, threshold T): K outcomes
+ *                        outcome k: count C first F status <name> dumped 0xM dump_hash 0x<16 hex>
+ *                        core c: Kc outcomes, M missing
+ *                        core c outcome k: count C first F
+ *                    by count descending, then first variant ascending; Kc counts the distinct
+ *                    dumps of core c, M the variants in which it wrote none.  Writes nothing
+ *                    into the CWD; exits 0 when no census table dropped a system, else 3.
+ *   --explore-dir D  write the dumps of each outcome's first variant to
+ *                    D/outcome_<k>/core_<n>_output.txt
+ *   --explore-kind dumps|final|full   what tells two outcomes apart (DSM_CENSUS_*; default
+ *                    dumps: what the reference's output files can)
  */
+#include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <sys/stat.h>
+
+#include <hip/hip_runtime_api.h>
 
 #include "dsm.h"
 
 static void usage(const char *argv0) {
     fprintf(stderr, "Usage: %s [--np 4|8] [--max-instr N] [--device D] [--quiet] [--issue-order FILE]\n"
-                    "          [--schedule SEED:THRESH] <test_directory>\n", argv0);
+                    "          [--schedule SEED:THRESH] [--explore N [--explore-dir DIR]\n"
+                    "          [--explore-kind dumps|final|full]] <test_directory>\n", argv0);
+}
+
+static const char *const status_names[5] = {"COMPLETED", "DEADLOCKED", "RING_OVERFLOW", "ASSERT_FAILED",
+                                            "ROUND_LIMIT"};
+
+/* --explore: n copies of the parsed system under schedule (seed, thresh), one run with
+ * snapshots, both censuses on the device.  Returns the process exit code. */
+static int explore(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces, const uint32_t *counts,
+                   uint32_t n, unsigned long long seed, unsigned thresh, int kind, const char *out_dir) {
+    uint32_t cap = DSM_CENSUS_MIN_CAP;
+    while (cap < n) cap <<= 1;
+    const size_t words = DSM_CENSUS_WORDS(cap), slot = (size_t)np * stride;
+    const size_t tr_bytes = (size_t)n * slot * sizeof(uint16_t), cn_bytes = (size_t)n * np * sizeof(uint32_t);
+    const size_t cen_bytes = (size_t)(1 + np) * words * sizeof(uint64_t);
+    uint16_t *h_tr = (uint16_t *)malloc(tr_bytes), *d_tr = NULL;
+    uint32_t *h_cn = (uint32_t *)malloc(cn_bytes), *d_cn = NULL;
+    uint64_t *cen = (uint64_t *)malloc(cen_bytes), *d_cen = NULL;
+    dsm_outcome *outc = (dsm_outcome *)malloc((size_t)cap * sizeof(dsm_outcome));
+    dsm_sys_result *d_res = NULL;
+    dsm_counters *d_cnt = NULL;
+    int rc = DSM_OK, code = EXIT_FAILURE;
+    const char *what = "out of memory";
+    if (!h_tr || !h_cn || !cen || !outc) goto fail;
+    for (uint32_t i = 0; i < n; ++i) {
+        memcpy(h_tr + (size_t)i * slot, traces, slot * sizeof(uint16_t));
+        memcpy(h_cn + (size_t)i * np, counts, (size_t)np * sizeof(uint32_t));
+    }
+    what = "device memory";
+    if (hipMalloc((void **)&d_tr, tr_bytes + 16) != hipSuccess || hipMalloc((void **)&d_cn, cn_bytes + 4) != hipSuccess ||
+        hipMalloc((void **)&d_res, (size_t)n * sizeof(dsm_sys_result)) != hipSuccess ||
+        hipMalloc((void **)&d_cnt, sizeof(dsm_counters)) != hipSuccess ||
+        hipMalloc((void **)&d_cen, cen_bytes) != hipSuccess ||
+        hipMemcpy(d_tr, h_tr, tr_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_cn, h_cn, cn_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(d_cnt, 0, sizeof(dsm_counters)) != hipSuccess || hipMemset(d_cen, 0, cen_bytes) != hipSuccess)
+        goto fail;
+    what = "dsm_set_schedule";
+    if ((rc = dsm_set_schedule(ctx, seed, thresh))) goto fail;
+    what = "dsm_run_packed_device";
+    if ((rc = dsm_run_packed_device(ctx, d_tr, d_cn, n, d_res, d_cnt, NULL))) goto fail;
+    what = "dsm_census_device";
+    if ((rc = dsm_census_device(ctx, d_res, n, 0, kind, d_cen, cap, NULL))) goto fail;
+    what = "dsm_census_run_nodes_device";
+    if ((rc = dsm_census_run_nodes_device(ctx, 0, n, d_cen + words, cap, NULL))) goto fail;
+    what = "census read-back";          /* a blocking copy: the run and both censuses are done */
+    if (hipMemcpy(cen, d_cen, cen_bytes, hipMemcpyDeviceToHost) != hipSuccess) goto fail;
+
+    uint64_t k = 0, dropped = cen[2];
+    what = "dsm_census_sorted";
+    if ((rc = dsm_census_sorted(cen, cap, outc, cap, &k))) goto fail;
+    printf("explored %u schedules (seed %llu, threshold %u): %llu outcomes\n", n, seed, thresh,
+           (unsigned long long)k);
+    if (out_dir && mkdir(out_dir, 0777) != 0 && errno != EEXIST) { what = out_dir; rc = DSM_E_IO; goto fail; }
+    for (uint64_t o = 0; o < k; ++o) {
+        dsm_sys_result r;
+        what = "result read-back";
+        if (hipMemcpy(&r, d_res + outc[o].first_sys, sizeof r, hipMemcpyDeviceToHost) != hipSuccess) goto fail;
+        const uint32_t st = r.status & 0xFFu, dumped = r.status >> 8;
+        printf("outcome %llu: count %llu first %llu status %s dumped 0x%x dump_hash 0x%016llx\n",
+               (unsigned long long)o, (unsigned long long)outc[o].count, (unsigned long long)outc[o].first_sys,
+               st < 5 ? status_names[st] : "?", dumped, (unsigned long long)r.dump_hash);
+        if (out_dir) {
+            char path[512];
+            what = "dumps";
+            if (snprintf(path, sizeof path, "%s/outcome_%llu", out_dir, (unsigned long long)o) >= (int)sizeof path ||
+                (mkdir(path, 0777) != 0 && errno != EEXIST)) { rc = DSM_E_IO; goto fail; }
+            if ((rc = dsm_write_run_dumps(ctx, outc[o].first_sys, dumped, path))) goto fail;
+        }
+    }
+    for (int c = 0; c < np; ++c) {
+        const uint64_t *t = cen + (size_t)(1 + c) * words;
+        uint64_t kc = 0, missing = 0;
+        dropped += t[2];
+        what = "dsm_census_sorted";
+        if ((rc = dsm_census_sorted(t, cap, outc, cap, &kc))) goto fail;
+        for (uint64_t o = 0; o < kc; ++o) if (outc[o].key == DSM_OUTCOME_MISSING) missing = outc[o].count;
+        printf("core %d: %llu outcomes, %llu missing\n", c, (unsigned long long)(kc - (missing ? 1 : 0)),
+               (unsigned long long)missing);
+        for (uint64_t o = 0, j = 0; o < kc; ++o) {
+            if (outc[o].key == DSM_OUTCOME_MISSING) continue;
+            printf("core %d outcome %llu: count %llu first %llu\n", c, (unsigned long long)j++,
+                   (unsigned long long)outc[o].count, (unsigned long long)outc[o].first_sys);
+        }
+    }
+    code = dropped ? 3 : 0;
+    what = NULL;
+fail:
+    if (what) fprintf(stderr, "Error: explore: %s%s%s\n", what, rc ? ": " : "", rc ? dsm_strerror(rc) : "");
+    if (d_tr) (void)hipFree(d_tr);
+    if (d_cn) (void)hipFree(d_cn);
+    if (d_res) (void)hipFree(d_res);
+    if (d_cnt) (void)hipFree(d_cnt);
+    if (d_cen) (void)hipFree(d_cen);
+    free(h_tr); free(h_cn); free(cen); free(outc);
+    return code;
 }
 
 int main(int argc, char **argv) {
@@ -41,6 +158,9 @@ int main(int argc, char **argv) {
     const char *dir = NULL, *issue_file = NULL;
     unsigned long long sched_seed = 0;
     unsigned sched_thresh = DSM_SCHED_LOCKSTEP;
+    int have_sched = 0, explore_kind = DSM_CENSUS_DUMPS, explore_opts = 0;
+    long long explore_n = 0;
+    const char *explore_dir = NULL;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--np") && i + 1 < argc) np = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--max-instr") && i + 1 < argc) max_instr = (uint32_t)atoi(argv[++i]);
@@ -49,6 +169,20 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--issue-order") && i + 1 < argc) issue_file = argv[++i];
         else if (!strcmp(argv[i], "--schedule") && i + 1 < argc) {
             if (sscanf(argv[++i], "%llu:%u", &sched_seed, &sched_thresh) != 2) { usage(argv[0]); return EXIT_FAILURE; }
+            have_sched = 1;
+        }
+        else if (!strcmp(argv[i], "--explore") && i + 1 < argc) {
+            explore_n = atoll(argv[++i]);
+            if (explore_n < 1 || explore_n > (long long)DSM_CENSUS_MAX_CAP) { usage(argv[0]); return EXIT_FAILURE; }
+        }
+        else if (!strcmp(argv[i], "--explore-dir") && i + 1 < argc) { explore_dir = argv[++i]; explore_opts = 1; }
+        else if (!strcmp(argv[i], "--explore-kind") && i + 1 < argc) {
+            const char *v = argv[++i];
+            explore_opts = 1;
+            if (!strcmp(v, "dumps")) explore_kind = DSM_CENSUS_DUMPS;
+            else if (!strcmp(v, "final")) explore_kind = DSM_CENSUS_FINAL;
+            else if (!strcmp(v, "full")) explore_kind = DSM_CENSUS_FULL;
+            else { usage(argv[0]); return EXIT_FAILURE; }
         }
         else if (argv[i][0] == '-' && argv[i][1] == '-') { usage(argv[0]); return EXIT_FAILURE; }
         else dir = argv[i];
@@ -58,6 +192,8 @@ int main(int argc, char **argv) {
         usage(argv[0]);
         return EXIT_FAILURE;
     }
+    if ((explore_n && issue_file) || (!explore_n && explore_opts)) { usage(argv[0]); return EXIT_FAILURE; }
+    if (explore_n && !have_sched) { sched_seed = 0; sched_thresh = 0x8000u; }
     const uint32_t stride = (max_instr + 7u) & ~7u;
     /* initializeProcessor (:776-822): the core files are read from disk here and scanned on
      * the GPU with the reference's fgets/sscanf semantics (dsm_parse_traces) */
@@ -117,6 +253,13 @@ int main(int argc, char **argv) {
     fflush(stdout);
     free(text);
 
+    if (explore_n) {
+        const int code = explore(ctx, np, stride, traces, counts, (uint32_t)explore_n, sched_seed, sched_thresh,
+                                 explore_kind, explore_dir);
+        dsm_close(ctx);
+        free(traces);
+        return code;
+    }
     if ((rc = dsm_set_schedule(ctx, sched_seed, sched_thresh))) {
         fprintf(stderr, "Error: dsm_set_schedule: %s\n", dsm_strerror(rc));
         return EXIT_FAILURE;

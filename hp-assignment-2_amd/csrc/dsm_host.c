@@ -6,11 +6,14 @@
  *   dsm_format_dump / dsm_write_dump          replace printProcessorState (:824-876),
  *                                             byte-for-byte
  *   dsm_node_hash                             canonical 64-bit hash of a node record
+ *   dsm_outcome_key / dsm_census_results / _merge / _sorted
+ *                                             the outcome census on the host
  */
 #include "dsm.h"
 
 #include <errno.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 const char *dsm_strerror(int code) {
@@ -183,5 +186,99 @@ int dsm_aggregate_results(const dsm_sys_result *res, uint64_t n_sys, uint64_t fi
         agg->sum_final_hash += r->final_hash;
         agg->result_digest += dsm_result_digest(first_sys + i, r);
     }
+    return DSM_OK;
+}
+
+/* ---- outcome census (include/dsm.h): the plain reference of csrc/dsm_census.hip ---------- */
+
+/* A fmix64 chain in the style of dsm_result_digest, seeded by the kind instead of the system
+ * id.  fmix64 is a bijection with fmix64(0) == 0, so the chain ends in 0 exactly when its last
+ * input equals the chain so far; that one value is mapped to 1 (0 marks an empty slot). */
+uint64_t dsm_outcome_key(int kind, const dsm_sys_result *r) {
+    uint64_t h = fmix64((uint64_t)(kind + 1) * 0x9E3779B97F4A7C15ULL + 1u);
+    if (kind == DSM_CENSUS_FULL) {
+        h = fmix64(h ^ ((uint64_t)r->status | ((uint64_t)r->rounds << 32)));
+        h = fmix64(h ^ ((uint64_t)r->msgs | ((uint64_t)r->instrs << 32)));
+    } else {
+        h = fmix64(h ^ (uint64_t)r->status);
+    }
+    h = fmix64(h ^ r->dump_hash);
+    if (kind != DSM_CENSUS_DUMPS) h = fmix64(h ^ r->final_hash);
+    return h ? h : 1u;
+}
+
+static int census_cap_ok(uint32_t cap) {
+    return cap >= DSM_CENSUS_MIN_CAP && cap <= DSM_CENSUS_MAX_CAP && (cap & (cap - 1u)) == 0u;
+}
+
+/* count systems of `key`, the lowest of them ~inv_first, into the table; 0 when the key found
+ * neither its slot nor a free one within cap probes */
+static int census_add(uint64_t *census, uint32_t cap, uint64_t key, uint64_t count, uint64_t inv_first) {
+    uint64_t s = key & (cap - 1u);
+    for (uint32_t p = 0; p < cap; ++p, s = (s + 1u) & (cap - 1u)) {
+        uint64_t *slot = census + 4 + 4 * s;
+        if (slot[0] == 0) {
+            slot[0] = key;
+            census[1]++;
+        }
+        if (slot[0] == key) {
+            slot[1] += count;
+            if (inv_first > slot[2]) slot[2] = inv_first;
+            return 1;
+        }
+    }
+    return 0;
+}
+
+int dsm_census_results(const dsm_sys_result *res, uint64_t n_sys, uint64_t first_sys, int kind,
+                       uint64_t *census, uint32_t cap) {
+    if (!census || (n_sys && !res) || !census_cap_ok(cap)) return DSM_E_INVAL;
+    if (kind != DSM_CENSUS_DUMPS && kind != DSM_CENSUS_FINAL && kind != DSM_CENSUS_FULL) return DSM_E_INVAL;
+    memset(census, 0, DSM_CENSUS_WORDS(cap) * sizeof(uint64_t));
+    for (uint64_t i = 0; i < n_sys; ++i) {
+        census[0]++;
+        if (!census_add(census, cap, dsm_outcome_key(kind, &res[i]), 1, ~(first_sys + i))) census[2]++;
+    }
+    return DSM_OK;
+}
+
+int dsm_census_merge(uint64_t *dst, const uint64_t *src, uint32_t cap) {
+    if (!dst || !src || dst == src || !census_cap_ok(cap)) return DSM_E_INVAL;
+    dst[0] += src[0];
+    dst[2] += src[2];
+    for (uint32_t s = 0; s < cap; ++s) {
+        const uint64_t *slot = src + 4 + 4 * (uint64_t)s;
+        if (slot[0] && !census_add(dst, cap, slot[0], slot[1], slot[2])) dst[2] += slot[1];
+    }
+    return DSM_OK;
+}
+
+static int outcome_cmp(const void *pa, const void *pb) {
+    const dsm_outcome *a = (const dsm_outcome *)pa, *b = (const dsm_outcome *)pb;
+    if (a->count != b->count) return a->count > b->count ? -1 : 1;
+    return a->first_sys < b->first_sys ? -1 : (a->first_sys > b->first_sys ? 1 : 0);
+}
+
+int dsm_census_sorted(const uint64_t *census, uint32_t cap, dsm_outcome *out, uint64_t out_cap,
+                      uint64_t *n) {
+    if (!census || !n || (out_cap && !out) || !census_cap_ok(cap)) return DSM_E_INVAL;
+    uint64_t k = 0;
+    for (uint32_t s = 0; s < cap; ++s) k += census[4 + 4 * (uint64_t)s] != 0;
+    *n = k;
+    if (k == 0 || out_cap == 0) return DSM_OK;
+    dsm_outcome *all = (dsm_outcome *)malloc((size_t)k * sizeof *all);
+    if (!all) return DSM_E_NOMEM;
+    k = 0;
+    for (uint32_t s = 0; s < cap; ++s) {
+        const uint64_t *slot = census + 4 + 4 * (uint64_t)s;
+        if (!slot[0]) continue;
+        all[k].key = slot[0];
+        all[k].count = slot[1];
+        all[k].first_sys = ~slot[2];
+        ++k;
+    }
+    qsort(all, (size_t)k, sizeof *all, outcome_cmp);
+    memcpy(out, all, (size_t)(k < out_cap ? k : out_cap) * sizeof *all);
+    free(all);
     return DSM_OK;
 }

@@ -1,6 +1,7 @@
 /*
  * dsm_internal.h -- the engine context shared by the kernel translation units of libdsm.so
- * (dsm_engine.hip: transition engine; dsm_text.hip: trace parser and dump formatter).
+ * (dsm_engine.hip: transition engine; dsm_text.hip: trace parser and dump formatter;
+ * dsm_census.hip: outcome census).
  * Not part of the ABI.
  */
 #ifndef DSM_INTERNAL_H

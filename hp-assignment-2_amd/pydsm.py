@@ -141,6 +141,13 @@ def lib():
             "dsm_group_allreduce_counters": (i32, [vp, vp, vp]),
             "dsm_group_allreduce_aggregate": (i32, [vp, vp, vp]),
             "dsm_group_barrier": (i32, [vp, vp]),
+            # ABI 5 (+census): the outcome census
+            "dsm_outcome_key": (u64, [i32, vp]),
+            "dsm_census_device": (i32, [vp, vp, u64, u64, i32, vp, u32, vp]),
+            "dsm_census_run_nodes_device": (i32, [vp, u64, u64, vp, u32, vp]),
+            "dsm_census_results": (i32, [vp, u64, u64, i32, vp, u32]),
+            "dsm_census_merge": (i32, [vp, vp, u32]),
+            "dsm_census_sorted": (i32, [vp, u32, vp, u64, ctypes.POINTER(u64)]),
             # test-only (csrc/dsm_internal.h, not in include/dsm.h)
             "dsm_debug_order_state": (i32, [vp, vp, vp, vp, u64, u64, vp, u32, ctypes.POINTER(u32),
                                             ctypes.POINTER(i32)]),
@@ -209,6 +216,68 @@ def aggregate_results_c(res, first_idx=0):
     _check(lib().dsm_aggregate_results(_ptr(res), len(res), first_idx, _ptr(out)),
            "dsm_aggregate_results")
     return agg_vec_to_dict(out)
+
+
+# -- outcome census (ABI 5 +census) -----------------------------------------------------------
+CENSUS_DUMPS, CENSUS_FINAL, CENSUS_FULL = 0, 1, 2
+CENSUS_KINDS = {"dumps": CENSUS_DUMPS, "final": CENSUS_FINAL, "full": CENSUS_FULL}
+CENSUS_MIN_CAP, CENSUS_MAX_CAP = 16, 1 << 20
+OUTCOME_MISSING = 1
+OUTCOME_DTYPE = np.dtype([("key", "<u8"), ("count", "<u8"), ("first_sys", "<u8")])
+
+
+def _census_cap_ok(cap):
+    return CENSUS_MIN_CAP <= cap <= CENSUS_MAX_CAP and cap & (cap - 1) == 0
+
+
+def CENSUS_WORDS(cap):
+    """DSM_CENSUS_WORDS: uint64 words of a census table of `cap` slots."""
+    return 4 + 4 * cap
+
+
+def outcome_key(kind, res):
+    """dsm_outcome_key of one RESULT_DTYPE record."""
+    rec = np.ascontiguousarray(res).view(RESULT_DTYPE).reshape(-1)[:1].copy()
+    return int(lib().dsm_outcome_key(CENSUS_KINDS.get(kind, kind), _ptr(rec)))
+
+
+def census_results(res, kind=CENSUS_DUMPS, cap=256, first_sys=0):
+    """dsm_census_results (the host census) of per-system results -> the table, uint64
+    [CENSUS_WORDS(cap)]."""
+    res = np.ascontiguousarray(res).view(RESULT_DTYPE).reshape(-1)
+    out = np.zeros(CENSUS_WORDS(cap) if _census_cap_ok(cap) else 4, dtype=np.uint64)
+    _check(lib().dsm_census_results(_ptr(res), len(res), first_sys, CENSUS_KINDS.get(kind, kind),
+                                    _ptr(out), cap), "dsm_census_results")
+    return out
+
+
+def census_merge(dst, src, cap):
+    """dsm_census_merge: dst += src (both tables of `cap` slots); returns dst."""
+    assert dst.dtype == np.uint64 and dst.flags.c_contiguous and dst.size >= 4
+    src = np.ascontiguousarray(src, dtype=np.uint64)
+    if _census_cap_ok(cap):         # else the library refuses before it touches a table
+        assert dst.size == src.size == CENSUS_WORDS(cap)
+    _check(lib().dsm_census_merge(_ptr(dst), _ptr(src), cap), "dsm_census_merge")
+    return dst
+
+
+def census_header(census):
+    c = np.asarray(census, dtype=np.uint64).reshape(-1)
+    return {"systems": int(c[0]), "distinct": int(c[1]), "dropped": int(c[2])}
+
+
+def census_sorted(census, cap):
+    """dsm_census_sorted: the outcomes of a table as an OUTCOME_DTYPE array, by count
+    descending, then first_sys ascending."""
+    census = np.ascontiguousarray(census, dtype=np.uint64).reshape(-1)
+    if _census_cap_ok(cap):
+        assert census.size == CENSUS_WORDS(cap)
+    n = ctypes.c_uint64(0)
+    _check(lib().dsm_census_sorted(_ptr(census), cap, None, 0, ctypes.byref(n)), "dsm_census_sorted")
+    out = np.zeros(n.value, dtype=OUTCOME_DTYPE)
+    _check(lib().dsm_census_sorted(_ptr(census), cap, _ptr(out), n.value, ctypes.byref(n)),
+           "dsm_census_sorted")
+    return out
 
 
 class Group:
@@ -281,6 +350,8 @@ class Engine:
                  type_counts=False, issue_trace=False):
         self.np = np_
         self.max_instr = max_instr
+        self.device = device
+        self._sched = (0, SCHED_LOCKSTEP)      # what set_schedule last set (explore restores it)
         self.cfg = Config(np_, max_instr, ring_cap,
                           (F_SNAPSHOTS if snapshots else 0) | (F_TIMING if timing else 0) |
                           (F_TYPE_COUNTS if type_counts else 0) |
@@ -352,6 +423,53 @@ class Engine:
                                           _dptr(d_agg, NAGG * 8), ctypes.c_void_p(stream)),
                "dsm_aggregate_device")
 
+    def census_device(self, d_results, n_sys, first_sys, kind, d_census, cap, stream=0):
+        """dsm_census_device: per-system results -> d_census (CENSUS_WORDS(cap) uint64,
+        accumulated; zero it first for one run)."""
+        nb = 8 * CENSUS_WORDS(cap) if _census_cap_ok(cap) else 0
+        _check(lib().dsm_census_device(self.ctx, _dptr(d_results, 32 * n_sys), n_sys, first_sys,
+                                       CENSUS_KINDS.get(kind, kind), _dptr(d_census, nb), cap,
+                                       ctypes.c_void_p(stream)), "dsm_census_device")
+
+    def census_run_nodes_device(self, first_sys, n_sys, d_census, cap, stream=0):
+        """dsm_census_run_nodes_device: the per-core census of the last run -> np tables back to
+        back in d_census (np * CENSUS_WORDS(cap) uint64, accumulated)."""
+        nb = 8 * self.np * CENSUS_WORDS(cap) if _census_cap_ok(cap) else 0
+        _check(lib().dsm_census_run_nodes_device(self.ctx, first_sys, n_sys, _dptr(d_census, nb),
+                                                 cap, ctypes.c_void_p(stream)),
+               "dsm_census_run_nodes_device")
+
+    def explore(self, traces, counts, k, seed, thresh=0x8000, kind=CENSUS_DUMPS):
+        """k seeded interleavings of ONE system (traces [np, max_instr] u16, counts [np]) in
+        one run, censused on the device: the sorted census (OUTCOME_DTYPE; first_sys is the
+        variant's index in the run, whose snapshots stay readable if the engine keeps them).
+        The schedule that was set before is restored."""
+        import torch
+        if not 1 <= k <= CENSUS_MAX_CAP:
+            raise DsmError(E_INVAL, "explore: k")
+        tr = np.ascontiguousarray(traces, dtype=np.uint16).reshape(1, self.np, self.max_instr)
+        cn = np.ascontiguousarray(counts, dtype=np.uint32).reshape(1, self.np)
+        cap = max(CENSUS_MIN_CAP, 1 << (k - 1).bit_length())
+        dev = torch.device("cuda", self.device)
+        # the library's own staging keeps 16 bytes of slack behind the traces and one count
+        d_tr = torch.zeros(k * tr.size + 8, dtype=torch.int16, device=dev)
+        d_tr[:k * tr.size].view(k, tr.size)[:] = torch.from_numpy(tr.view(np.int16).reshape(-1)).to(dev)
+        d_cn = torch.zeros(k * self.np + 1, dtype=torch.int32, device=dev)
+        d_cn[:k * self.np].view(k, self.np)[:] = torch.from_numpy(cn.view(np.int32).reshape(-1)).to(dev)
+        d_res = torch.zeros(4 * k, dtype=torch.int64, device=dev)
+        d_cnt = torch.zeros(NCOUNTERS, dtype=torch.int64, device=dev)
+        d_cen = torch.zeros(CENSUS_WORDS(cap), dtype=torch.int64, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        prev = self._sched
+        self.set_schedule(seed, thresh)
+        try:
+            self.run_packed_device(d_tr, d_cn, k, d_res, d_cnt, st)
+            self.census_device(d_res, k, 0, kind, d_cen, cap, st)
+            table = d_cen.cpu().numpy().view(np.uint64)
+        finally:
+            self.set_schedule(*prev)
+        return census_sorted(table, cap)
+
     def node_state(self, sys, node):
         d = np.zeros(64, dtype=np.uint8)
         f = np.zeros(64, dtype=np.uint8)
@@ -410,6 +528,7 @@ class Engine:
     # -- schedule exploration / issue order --------------------------------------------------
     def set_schedule(self, seed, act_thresh=SCHED_LOCKSTEP):
         _check(lib().dsm_set_schedule(self.ctx, seed, act_thresh), "dsm_set_schedule")
+        self._sched = (seed, act_thresh)
 
     def issue_trace(self, sys):
         cap = self.np * self.max_instr

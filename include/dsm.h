@@ -42,7 +42,9 @@ extern "C" {
                              4: dsm_counters grew to DSM_NCOUNTERS (ser_macro_steps), dsm_launch_info
                                 names the kernels that ran (dsm_launch_kernel_names);
                              5: per-system aggregates (dsm_aggregate_*) and the multi-GPU group
-                                over RCCL (dsm_group_*) */
+                                over RCCL (dsm_group_*);
+                             5 (+census): additive -- the outcome census (dsm_outcome_key,
+                                dsm_census_*) is new symbols only, no struct or call changed */
 
 #define DSM_MAX_NP 8             /* bitVector is one byte (README.md:51)                  */
 #define DSM_CACHE_SIZE 4         /* CACHE_SIZE      assignment.c:10                        */
@@ -380,6 +382,70 @@ int dsm_aggregate_results(const dsm_sys_result *res, uint64_t n_sys, uint64_t fi
                           dsm_aggregate *agg);
 /* one system's term of result_digest */
 uint64_t dsm_result_digest(uint64_t sys_id, const dsm_sys_result *r);
+
+/* ---- outcome census: the distinct outcomes of a run, how often, and who first ---------- *
+ * The reference is nondeterministic; what its users ask of a test directory is which dumps it
+ * can produce and how often.  A census groups the systems of a run (typically the seeded
+ * interleavings of dsm_set_schedule) by an outcome key and keeps, per key, the number of
+ * systems and the lowest system id that produced it -- the representative whose dumps
+ * dsm_write_run_dumps prints.
+ *
+ * The table is one flat uint64 buffer the caller owns (device or host) of
+ * DSM_CENSUS_WORDS(cap) words: the header {systems, distinct, dropped, reserved}, then cap
+ * slots {key, count, inv_first, reserved}.  cap is a power of two, DSM_CENSUS_MIN_CAP <= cap
+ * <= DSM_CENSUS_MAX_CAP (else DSM_E_INVAL).  Key 0 marks an empty slot, and inv_first is the
+ * bitwise NOT of the lowest absolute system id, so an all-zero buffer is the empty census
+ * and every update is a commutative atomic: compare-and-swap on the key, add on the count,
+ * max on inv_first.  Open addressing: home slot key & (cap - 1), linear probing by +1 with
+ * wrap-around; slots are never freed.  A system whose key finds neither its slot nor a free
+ * one within cap probes is counted in `dropped`, so a key is in the table with its exact
+ * count or not at all, and sum(count) + dropped == systems always.  Which keys an overfull
+ * table keeps depends on the order of insertion; nothing else does.  Slot placement may
+ * differ between two censuses of the same systems: they are equal when their headers and
+ * their sorted views (dsm_census_sorted) are. */
+enum { DSM_CENSUS_DUMPS = 0,   /* status (dumped-node mask included) and dump_hash: what the
+                                * reference's output files can tell apart                     */
+       DSM_CENSUS_FINAL = 1,   /* ... and final_hash                                          */
+       DSM_CENSUS_FULL = 2     /* all six result fields: timing differences count too         */ };
+#define DSM_CENSUS_MIN_CAP 16u
+#define DSM_CENSUS_MAX_CAP (1u << 20)
+#define DSM_CENSUS_WORDS(cap) (4u + 4u * (size_t)(cap))
+#define DSM_OUTCOME_MISSING 1u   /* per-core census: the key of a core that wrote no dump      */
+typedef struct dsm_outcome {
+    uint64_t key;
+    uint64_t count;            /* systems that produced the key                              */
+    uint64_t first_sys;        /* the lowest system id among them                            */
+} dsm_outcome;
+/* A system's outcome key (host only): a fmix64 chain over the fields `kind` names, without
+ * the system id.  Never 0 (the empty-slot mark): a chain that ends in 0 is mapped to 1. */
+uint64_t dsm_outcome_key(int kind, const dsm_sys_result *r);
+/* Census of d_results[0 .. n_sys) with ids first_sys, first_sys + 1, .. (64-bit) ACCUMULATED
+ * into d_census (device; zero it first for one run).  Asynchronous on `stream`, conventions
+ * as dsm_aggregate_device; n_sys == 0 is a no-op. */
+int dsm_census_device(dsm_ctx *ctx, const dsm_sys_result *d_results, uint64_t n_sys,
+                      uint64_t first_sys, int kind, uint64_t *d_census, uint32_t cap, void *stream);
+/* Per-core census of systems first_sys .. first_sys+n_sys-1 of the last run (needs
+ * DSM_F_SNAPSHOTS; argument and state errors as dsm_format_run_dumps_device), ACCUMULATED
+ * into np tables laid back to back in d_census (np * DSM_CENSUS_WORDS(cap) words), table c
+ * for core c.  The key of core c of a system is dsm_node_hash(c, its dump record, 15) where
+ * the core dumped (hash values 0 and 1 are mapped to 2) and DSM_OUTCOME_MISSING where it
+ * did not, as the run's final record of the core says (dsm_node_state.flags bit 1).  Ids
+ * are the systems' indices in the run. */
+int dsm_census_run_nodes_device(dsm_ctx *ctx, uint64_t first_sys, uint64_t n_sys,
+                                uint64_t *d_census, uint32_t cap, void *stream);
+/* dsm_census_device on the host (no GPU needed): the plain reference.  census is overwritten. */
+int dsm_census_results(const dsm_sys_result *res, uint64_t n_sys, uint64_t first_sys, int kind,
+                       uint64_t *census, uint32_t cap);
+/* dst += src, key by key with the same drop rule (host only): the shards of a multi-GPU
+ * ensemble, or the batches of a long one, combine with it.  Both tables have `cap` slots.
+ * Where a shard's own table had dropped systems, a key's merged count covers the shards that
+ * kept it; with dropped == 0 everywhere the result is the census of the whole. */
+int dsm_census_merge(uint64_t *dst, const uint64_t *src, uint32_t cap);
+/* The compact, deterministic view (host only): the outcomes sorted by count descending, then
+ * first_sys ascending (first ids are unique, so the order is total).  *n = the number of
+ * outcomes (may exceed out_cap; min(out_cap, *n) are written; out may be NULL if out_cap is 0). */
+int dsm_census_sorted(const uint64_t *census, uint32_t cap, dsm_outcome *out, uint64_t out_cap,
+                      uint64_t *n);
 
 /* ---- multi-GPU group: RCCL over xGMI --------------------------------------- *
  * Systems are independent, so an ensemble shards over GPUs with no data-path exchange; the
