@@ -40,6 +40,20 @@
  *                    D/outcome_<k>/core_<n>_output.txt
  *   --explore-kind dumps|final|full   what tells two outcomes apart (DSM_CENSUS_*; default
  *                    dumps: what the reference's output files can)
+ *   --audit          coherence audit of the final states on the GPU (dsm_audit_run_device): which
+ *                    invariants they break.  On a plain run one more line after the dumps,
+ *                        audit: coherent
+ *                    or, for example,
+ *                        audit: 0x0c DIR_EM,DIR_S lines 3 first 0x15 bad 0
+ *                    (class bits, class names, violating addresses, the lowest of them, bad lines
+ *                    plus bad directory entries).  With --explore every `outcome k:` line is
+ *                    followed by `outcome k audit: ...` in the same format for the outcome's first
+ *                    variant (with kind dumps the variants of one outcome may end in different
+ *                    final states), and the core lines by
+ *                        audit: V of N schedules incoherent
+ *                        audit class <NAME>: C schedules, first F
+ *                    over all N variants, one class line per class that occurred.  Exit codes do
+ *                    not change.
  */
 #include <errno.h>
 #include <stdio.h>
@@ -54,16 +68,25 @@
 static void usage(const char *argv0) {
     fprintf(stderr, "Usage: %s [--np 4|8] [--max-instr N] [--device D] [--quiet] [--issue-order FILE]\n"
                     "          [--schedule SEED:THRESH] [--explore N [--explore-dir DIR]\n"
-                    "          [--explore-kind dumps|final|full]] <test_directory>\n", argv0);
+                    "          [--explore-kind dumps|final|full]] [--audit] <test_directory>\n", argv0);
 }
 
 static const char *const status_names[5] = {"COMPLETED", "DEADLOCKED", "RING_OVERFLOW", "ASSERT_FAILED",
                                             "ROUND_LIMIT"};
 
+/* "coherent", or "0x0c DIR_EM,DIR_S lines 3 first 0x15 bad 0" */
+static void print_audit_word(const char *prefix, uint32_t w) {
+    if (w == DSM_AUDIT_COHERENT) { printf("%s: coherent\n", prefix); return; }
+    printf("%s: 0x%02x ", prefix, w & 0xFFu);
+    for (int b = 0, k = 0; b < DSM_AUDIT_NCLASS; ++b)
+        if ((w >> b) & 1u) printf("%s%s", k++ ? "," : "", dsm_audit_class_name(b));
+    printf(" lines %u first 0x%02x bad %u\n", (w >> 8) & 0xFFu, (w >> 16) & 0xFFu, w >> 24);
+}
+
 /* --explore: n copies of the parsed system under schedule (seed, thresh), one run with
  * snapshots, both censuses on the device.  Returns the process exit code. */
 static int explore(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces, const uint32_t *counts,
-                   uint32_t n, unsigned long long seed, unsigned thresh, int kind, const char *out_dir) {
+                   uint32_t n, unsigned long long seed, unsigned thresh, int kind, const char *out_dir, int audit) {
     uint32_t cap = DSM_CENSUS_MIN_CAP;
     while (cap < n) cap <<= 1;
     const size_t words = DSM_CENSUS_WORDS(cap), slot = (size_t)np * stride;
@@ -75,6 +98,8 @@ static int explore(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces
     dsm_outcome *outc = (dsm_outcome *)malloc((size_t)cap * sizeof(dsm_outcome));
     dsm_sys_result *d_res = NULL;
     dsm_counters *d_cnt = NULL;
+    uint32_t *d_words = NULL;
+    dsm_audit *d_aud = NULL, aud;
     int rc = DSM_OK, code = EXIT_FAILURE;
     const char *what = "out of memory";
     if (!h_tr || !h_cn || !cen || !outc) goto fail;
@@ -99,6 +124,14 @@ static int explore(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces
     if ((rc = dsm_census_device(ctx, d_res, n, 0, kind, d_cen, cap, NULL))) goto fail;
     what = "dsm_census_run_nodes_device";
     if ((rc = dsm_census_run_nodes_device(ctx, 0, n, d_cen + words, cap, NULL))) goto fail;
+    if (audit) {
+        what = "device memory";
+        if (hipMalloc((void **)&d_words, (size_t)n * sizeof(uint32_t)) != hipSuccess ||
+            hipMalloc((void **)&d_aud, sizeof aud) != hipSuccess || hipMemset(d_aud, 0, sizeof aud) != hipSuccess)
+            goto fail;
+        what = "dsm_audit_run_device";
+        if ((rc = dsm_audit_run_device(ctx, 0, n, d_words, d_aud, NULL))) goto fail;
+    }
     what = "census read-back";          /* a blocking copy: the run and both censuses are done */
     if (hipMemcpy(cen, d_cen, cen_bytes, hipMemcpyDeviceToHost) != hipSuccess) goto fail;
 
@@ -116,6 +149,14 @@ static int explore(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces
         printf("outcome %llu: count %llu first %llu status %s dumped 0x%x dump_hash 0x%016llx\n",
                (unsigned long long)o, (unsigned long long)outc[o].count, (unsigned long long)outc[o].first_sys,
                st < 5 ? status_names[st] : "?", dumped, (unsigned long long)r.dump_hash);
+        if (audit) {
+            uint32_t w;
+            char prefix[48];
+            what = "audit read-back";
+            if (hipMemcpy(&w, d_words + outc[o].first_sys, sizeof w, hipMemcpyDeviceToHost) != hipSuccess) goto fail;
+            snprintf(prefix, sizeof prefix, "outcome %llu audit", (unsigned long long)o);
+            print_audit_word(prefix, w);
+        }
         if (out_dir) {
             char path[512];
             what = "dumps";
@@ -139,6 +180,16 @@ static int explore(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces
                    (unsigned long long)outc[o].count, (unsigned long long)outc[o].first_sys);
         }
     }
+    if (audit) {
+        what = "audit read-back";
+        if (hipMemcpy(&aud, d_aud, sizeof aud, hipMemcpyDeviceToHost) != hipSuccess) goto fail;
+        printf("audit: %llu of %llu schedules incoherent\n", (unsigned long long)aud.violating,
+               (unsigned long long)aud.systems);
+        for (int b = 0; b < DSM_AUDIT_NCLASS; ++b)
+            if (aud.by_class[b])
+                printf("audit class %s: %llu schedules, first %llu\n", dsm_audit_class_name(b),
+                       (unsigned long long)aud.by_class[b], (unsigned long long)~aud.inv_first[b]);
+    }
     code = dropped ? 3 : 0;
     what = NULL;
 fail:
@@ -148,12 +199,14 @@ fail:
     if (d_res) (void)hipFree(d_res);
     if (d_cnt) (void)hipFree(d_cnt);
     if (d_cen) (void)hipFree(d_cen);
+    if (d_words) (void)hipFree(d_words);
+    if (d_aud) (void)hipFree(d_aud);
     free(h_tr); free(h_cn); free(cen); free(outc);
     return code;
 }
 
 int main(int argc, char **argv) {
-    int np = 4, device = 0, quiet = 0;
+    int np = 4, device = 0, quiet = 0, audit = 0;
     uint32_t max_instr = DSM_REF_MAX_INSTR;
     const char *dir = NULL, *issue_file = NULL;
     unsigned long long sched_seed = 0;
@@ -166,6 +219,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--max-instr") && i + 1 < argc) max_instr = (uint32_t)atoi(argv[++i]);
         else if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--quiet")) quiet = 1;
+        else if (!strcmp(argv[i], "--audit")) audit = 1;
         else if (!strcmp(argv[i], "--issue-order") && i + 1 < argc) issue_file = argv[++i];
         else if (!strcmp(argv[i], "--schedule") && i + 1 < argc) {
             if (sscanf(argv[++i], "%llu:%u", &sched_seed, &sched_thresh) != 2) { usage(argv[0]); return EXIT_FAILURE; }
@@ -255,7 +309,7 @@ int main(int argc, char **argv) {
 
     if (explore_n) {
         const int code = explore(ctx, np, stride, traces, counts, (uint32_t)explore_n, sched_seed, sched_thresh,
-                                 explore_kind, explore_dir);
+                                 explore_kind, explore_dir, audit);
         dsm_close(ctx);
         free(traces);
         return code;
@@ -293,6 +347,19 @@ int main(int argc, char **argv) {
         fprintf(stderr, "Error: dumps: %s\n", dsm_strerror(rc));
         dsm_close(ctx);
         return EXIT_FAILURE;
+    }
+    if (audit) {                                        /* the final states, audited on the GPU */
+        uint32_t *d_word = NULL, w = 0;
+        if (hipMalloc((void **)&d_word, sizeof w) != hipSuccess) rc = DSM_E_NOMEM;
+        else if (!(rc = dsm_audit_run_device(ctx, 0, 1, d_word, NULL, NULL)) &&
+                 hipMemcpy(&w, d_word, sizeof w, hipMemcpyDeviceToHost) != hipSuccess) rc = DSM_E_DEVICE;
+        if (d_word) (void)hipFree(d_word);
+        if (rc) {
+            fprintf(stderr, "Error: audit: %s\n", dsm_strerror(rc));
+            dsm_close(ctx);
+            return EXIT_FAILURE;
+        }
+        print_audit_word("audit", w);
     }
     dsm_close(ctx);
     free(traces);

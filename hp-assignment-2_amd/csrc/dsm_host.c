@@ -8,6 +8,7 @@
  *   dsm_node_hash                             canonical 64-bit hash of a node record
  *   dsm_outcome_key / dsm_census_results / _merge / _sorted
  *                                             the outcome census on the host
+ *   dsm_audit_states / _merge / _class_name   the coherence audit on the host
  */
 #include "dsm.h"
 
@@ -280,5 +281,96 @@ int dsm_census_sorted(const uint64_t *census, uint32_t cap, dsm_outcome *out, ui
     qsort(all, (size_t)k, sizeof *all, outcome_cmp);
     memcpy(out, all, (size_t)(k < out_cap ? k : out_cap) * sizeof *all);
     free(all);
+    return DSM_OK;
+}
+
+/* ---- coherence audit (include/dsm.h): the plain reference of csrc/dsm_audit.hip ---------- */
+
+static const char *const audit_names[DSM_AUDIT_NCLASS] = {"MULTI_OWNER", "OWNER_AND_SHARER", "DIR_EM", "DIR_S",
+                                                          "DIR_U", "STALE_VALUE", "BAD_RECORD"};
+
+const char *dsm_audit_class_name(int bit) {
+    return bit >= 0 && bit < DSM_AUDIT_NCLASS ? audit_names[bit] : NULL;
+}
+
+static int popcount8(uint32_t x) {
+    int n = 0;
+    for (; x; x &= x - 1u) ++n;
+    return n;
+}
+
+/* one system: the np final records st[c * stride] -> its audit word */
+static uint32_t audit_system(int np, const dsm_node_state *st, uint32_t stride) {
+    const int na = DSM_MEM_SIZE * np;
+    uint8_t me[DSM_MEM_SIZE * DSM_MAX_NP] = {0}, sh[DSM_MEM_SIZE * DSM_MAX_NP] = {0};
+    uint8_t stale[DSM_MEM_SIZE * DSM_MAX_NP] = {0};
+    uint32_t bad = 0, classes = 0, lines = 0, first = 0xFFu;
+    for (int c = 0; c < np; ++c) {
+        const dsm_node_state *r = st + (size_t)c * stride;
+        for (int s = 0; s < DSM_CACHE_SIZE; ++s) {
+            const int a = r->cache_addr[s], cs = r->cache_state[s];
+            if (cs == 3 || a == 0xFF) continue;                       /* not held */
+            if (cs > 3 || a >= na || (a & 3) != s) { ++bad; continue; }
+            if (cs <= 1) me[a] |= (uint8_t)(1u << c);
+            else sh[a] |= (uint8_t)(1u << c);
+            if (cs != 0 && r->cache_value[s] != st[(size_t)(a >> 4) * stride].memory[a & 15]) stale[a] = 1;
+        }
+    }
+    for (int a = 0; a < na; ++a) {
+        const dsm_node_state *h = st + (size_t)(a >> 4) * stride;
+        const uint32_t bv = h->dir_bv[a & 15], d = h->dir_state[a & 15], m = me[a], s = sh[a];
+        uint32_t v = 0;
+        if (popcount8(m) > 1) v |= 1u << DSM_AUDIT_MULTI_OWNER;
+        if (m && s) v |= 1u << DSM_AUDIT_OWNER_AND_SHARER;
+        if (d > 2) ++bad;
+        else if (d == 0 && (bv != m || popcount8(m) != 1)) v |= 1u << DSM_AUDIT_DIR_EM;
+        else if (d == 1 && (bv != s || s == 0 || m != 0)) v |= 1u << DSM_AUDIT_DIR_S;
+        else if (d == 2 && (m | s)) v |= 1u << DSM_AUDIT_DIR_U;
+        if (stale[a]) v |= 1u << DSM_AUDIT_STALE_VALUE;
+        if (v) {
+            classes |= v;
+            if (lines++ == 0) first = (uint32_t)a;
+        }
+    }
+    if (bad) classes |= 1u << DSM_AUDIT_BAD_RECORD;
+    return classes | lines << 8 | first << 16 | bad << 24;
+}
+
+int dsm_audit_states(int np, const dsm_node_state *states, uint32_t state_stride, uint64_t n_sys,
+                     uint64_t first_sys, uint32_t *words, dsm_audit *audit) {
+    if ((np != 4 && np != 8) || state_stride == 0) return DSM_E_INVAL;
+    if (n_sys && (!states || (!words && !audit))) return DSM_E_INVAL;
+    if (audit) memset(audit, 0, sizeof *audit);
+    for (uint64_t k = 0; k < n_sys; ++k) {
+        const uint32_t w = audit_system(np, states + (size_t)k * (size_t)np * state_stride, state_stride);
+        if (words) words[k] = w;
+        if (!audit) continue;
+        const uint64_t inv = ~(first_sys + k);
+        audit->systems++;
+        audit->lines += (w >> 8) & 0xFFu;
+        audit->bad_items += w >> 24;
+        if (!(w & 0x7Fu)) continue;
+        audit->violating++;
+        if (inv > audit->inv_first[7]) audit->inv_first[7] = inv;
+        for (int b = 0; b < DSM_AUDIT_NCLASS; ++b) {
+            if (!((w >> b) & 1u)) continue;
+            audit->by_class[b]++;
+            if (inv > audit->inv_first[b]) audit->inv_first[b] = inv;
+        }
+    }
+    return DSM_OK;
+}
+
+int dsm_audit_merge(dsm_audit *dst, const dsm_audit *src) {
+    if (!dst || !src || dst == src) return DSM_E_INVAL;
+    dst->systems += src->systems;
+    dst->violating += src->violating;
+    dst->lines += src->lines;
+    dst->bad_items += src->bad_items;
+    for (int b = 0; b < 8; ++b) {
+        dst->by_class[b] += src->by_class[b];
+        if (src->inv_first[b] > dst->inv_first[b]) dst->inv_first[b] = src->inv_first[b];
+    }
+    for (int b = 0; b < 12; ++b) dst->reserved[b] += src->reserved[b];
     return DSM_OK;
 }

@@ -148,6 +148,12 @@ def lib():
             "dsm_census_results": (i32, [vp, u64, u64, i32, vp, u32]),
             "dsm_census_merge": (i32, [vp, vp, u32]),
             "dsm_census_sorted": (i32, [vp, u32, vp, u64, ctypes.POINTER(u64)]),
+            # ABI 5 (+audit): the coherence audit
+            "dsm_audit_states_device": (i32, [vp, vp, u32, u64, u64, vp, vp, vp]),
+            "dsm_audit_run_device": (i32, [vp, u64, u64, vp, vp, vp]),
+            "dsm_audit_states": (i32, [i32, vp, u32, u64, u64, vp, vp]),
+            "dsm_audit_merge": (i32, [vp, vp]),
+            "dsm_audit_class_name": (ctypes.c_char_p, [i32]),
             # test-only (csrc/dsm_internal.h, not in include/dsm.h)
             "dsm_debug_order_state": (i32, [vp, vp, vp, vp, u64, u64, vp, u32, ctypes.POINTER(u32),
                                             ctypes.POINTER(i32)]),
@@ -278,6 +284,67 @@ def census_sorted(census, cap):
     _check(lib().dsm_census_sorted(_ptr(census), cap, _ptr(out), n.value, ctypes.byref(n)),
            "dsm_census_sorted")
     return out
+
+
+# -- coherence audit (ABI 5 +audit) -----------------------------------------------------------
+(AUDIT_MULTI_OWNER, AUDIT_OWNER_AND_SHARER, AUDIT_DIR_EM, AUDIT_DIR_S, AUDIT_DIR_U,
+ AUDIT_STALE_VALUE, AUDIT_BAD_RECORD) = range(7)
+AUDIT_NCLASS = 7
+AUDIT_CLASS_NAMES = ["MULTI_OWNER", "OWNER_AND_SHARER", "DIR_EM", "DIR_S", "DIR_U", "STALE_VALUE",
+                     "BAD_RECORD"]
+AUDIT_COHERENT = 0x00FF0000                  # DSM_AUDIT_COHERENT: the word of a coherent system
+NAUDIT = 32                                  # DSM_NAUDIT
+AUDIT_DTYPE = np.dtype([("systems", "<u8"), ("violating", "<u8"), ("lines", "<u8"),
+                        ("bad_items", "<u8"), ("by_class", "<u8", (8,)), ("inv_first", "<u8", (8,)),
+                        ("reserved", "<u8", (12,))])
+assert AUDIT_DTYPE.itemsize == 8 * NAUDIT
+
+
+def audit_class_name(bit):
+    """dsm_audit_class_name: the class name of a bit of the audit word, or None."""
+    s = lib().dsm_audit_class_name(bit)
+    return s.decode() if s is not None else None
+
+
+def audit_word_fields(word):
+    """An audit word -> (classes, lines, first_addr, bad): the class bits 0..6, the number of
+    violating addresses, the lowest of them (0xFF: none) and bad lines plus bad entries."""
+    w = int(word)
+    return w & 0xFF, (w >> 8) & 0xFF, (w >> 16) & 0xFF, w >> 24
+
+
+def audit_states(np_, states, state_stride=1, first_sys=0, n_sys=None, words=True, summary=True):
+    """dsm_audit_states (the host audit): states is the records' bytes, record k * np + c at
+    byte 64 * (k * np + c) * state_stride -> (words uint32 [n_sys] or None, summary AUDIT_DTYPE
+    scalar or None)."""
+    st = np.ascontiguousarray(states).view(np.uint8).reshape(-1)
+    if n_sys is None:
+        n_sys = st.size // (64 * np_ * state_stride) if np_ > 0 and state_stride > 0 else 0
+    w = np.zeros(n_sys, dtype=np.uint32) if words else None
+    a = np.zeros(1, dtype=AUDIT_DTYPE) if summary else None
+    _check(lib().dsm_audit_states(np_, _ptr(st) if st.size else None, state_stride, n_sys, first_sys,
+                                  _ptr(w), _ptr(a)), "dsm_audit_states")
+    return w, (a[0] if summary else None)
+
+
+def audit_merge(dst, src):
+    """dsm_audit_merge: dst += src (AUDIT_DTYPE arrays of one element); returns dst."""
+    assert dst.dtype == AUDIT_DTYPE and dst.size == 1 and dst.flags.c_contiguous
+    src = np.ascontiguousarray(src, dtype=AUDIT_DTYPE).reshape(1)
+    _check(lib().dsm_audit_merge(_ptr(dst), _ptr(src)), "dsm_audit_merge")
+    return dst
+
+
+def audit_to_dict(a):
+    """A dsm_audit (AUDIT_DTYPE record or NAUDIT uint64) as a dict: the sums, and per class
+    that occurred {name: (systems, first id)}; "first" is the lowest violating id or None."""
+    v = [int(x) for x in np.ascontiguousarray(a).view(np.uint64).reshape(-1)]
+    assert len(v) == NAUDIT
+    inv = lambda x: (~x) & 0xFFFFFFFFFFFFFFFF
+    return {"systems": v[0], "violating": v[1], "lines": v[2], "bad_items": v[3],
+            "first": inv(v[19]) if v[19] else None,
+            "classes": {AUDIT_CLASS_NAMES[b]: (v[4 + b], inv(v[12 + b]))
+                        for b in range(AUDIT_NCLASS) if v[4 + b]}}
 
 
 class Group:
@@ -439,14 +506,41 @@ class Engine:
                                                  cap, ctypes.c_void_p(stream)),
                "dsm_census_run_nodes_device")
 
-    def explore(self, traces, counts, k, seed, thresh=0x8000, kind=CENSUS_DUMPS):
+    def audit_states_device(self, d_states, n_sys, first_sys, d_words, d_audit, state_stride=1,
+                            stream=0):
+        """dsm_audit_states_device: the coherence audit of n_sys systems' records in d_states
+        (record k * np + c at 64 * (k * np + c) * state_stride bytes) -> d_words (n_sys uint32,
+        may be None) and d_audit (NAUDIT uint64, accumulated, may be None)."""
+        _check(lib().dsm_audit_states_device(self.ctx, _dptr(d_states), state_stride, n_sys,
+                                             first_sys, _dptr(d_words, 4 * n_sys),
+                                             _dptr(d_audit, 8 * NAUDIT), ctypes.c_void_p(stream)),
+               "dsm_audit_states_device")
+
+    def audit_run_device(self, first_sys, n_sys, d_words, d_audit, stream=0):
+        """dsm_audit_run_device: the same over the final records of systems first_sys ..
+        first_sys + n_sys - 1 of the last run (needs snapshots)."""
+        _check(lib().dsm_audit_run_device(self.ctx, first_sys, n_sys, _dptr(d_words, 4 * n_sys),
+                                          _dptr(d_audit, 8 * NAUDIT), ctypes.c_void_p(stream)),
+               "dsm_audit_run_device")
+
+    def explore(self, traces, counts, k, seed, thresh=0x8000, kind=CENSUS_DUMPS, audit=False):
         """k seeded interleavings of ONE system (traces [np, max_instr] u16, counts [np]) in
         one run, censused on the device: the sorted census (OUTCOME_DTYPE; first_sys is the
         variant's index in the run, whose snapshots stay readable if the engine keeps them).
-        The schedule that was set before is restored."""
+        The schedule that was set before is restored.
+
+        With audit=True (the engine must keep snapshots) the run's final records are audited on
+        the device too and the call returns (outcomes, words, summary): words[j] is the audit
+        word of outcome j's representative, first_sys, and summary the dsm_audit (AUDIT_DTYPE
+        record) over all k variants, exact for every kind.  With kind FINAL or FULL every variant
+        of an outcome has the same final records (up to a hash collision), so the
+        representative's word is the outcome's; with DUMPS variants of one outcome may differ in
+        their final states, and the word is the representative's only."""
         import torch
         if not 1 <= k <= CENSUS_MAX_CAP:
             raise DsmError(E_INVAL, "explore: k")
+        if audit and not self.cfg.flags & F_SNAPSHOTS:
+            raise DsmError(E_STATE, "explore: audit needs an engine with snapshots")
         tr = np.ascontiguousarray(traces, dtype=np.uint16).reshape(1, self.np, self.max_instr)
         cn = np.ascontiguousarray(counts, dtype=np.uint32).reshape(1, self.np)
         cap = max(CENSUS_MIN_CAP, 1 << (k - 1).bit_length())
@@ -465,10 +559,18 @@ class Engine:
         try:
             self.run_packed_device(d_tr, d_cn, k, d_res, d_cnt, st)
             self.census_device(d_res, k, 0, kind, d_cen, cap, st)
+            if audit:
+                d_words = torch.zeros(k, dtype=torch.int32, device=dev)
+                d_aud = torch.zeros(NAUDIT, dtype=torch.int64, device=dev)
+                self.audit_run_device(0, k, d_words, d_aud, st)
             table = d_cen.cpu().numpy().view(np.uint64)
         finally:
             self.set_schedule(*prev)
-        return census_sorted(table, cap)
+        outcomes = census_sorted(table, cap)
+        if not audit:
+            return outcomes
+        words = d_words.cpu().numpy().view(np.uint32)[outcomes["first_sys"].astype(np.int64)]
+        return outcomes, words, d_aud.cpu().numpy().view(AUDIT_DTYPE)[0]
 
     def node_state(self, sys, node):
         d = np.zeros(64, dtype=np.uint8)

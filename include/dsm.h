@@ -44,7 +44,8 @@ extern "C" {
                              5: per-system aggregates (dsm_aggregate_*) and the multi-GPU group
                                 over RCCL (dsm_group_*);
                              5 (+census): additive -- the outcome census (dsm_outcome_key,
-                                dsm_census_*) is new symbols only, no struct or call changed */
+                                dsm_census_*) is new symbols only, no struct or call changed;
+                             5 (+audit): additive -- the coherence audit (dsm_audit_*) likewise */
 
 #define DSM_MAX_NP 8             /* bitVector is one byte (README.md:51)                  */
 #define DSM_CACHE_SIZE 4         /* CACHE_SIZE      assignment.c:10                        */
@@ -446,6 +447,76 @@ int dsm_census_merge(uint64_t *dst, const uint64_t *src, uint32_t cap);
  * outcomes (may exceed out_cap; min(out_cap, *n) are written; out may be NULL if out_cap is 0). */
 int dsm_census_sorted(const uint64_t *census, uint32_t cap, dsm_outcome *out, uint64_t out_cap,
                       uint64_t *n);
+
+/* ---- coherence audit: which invariants the final states of a system break --------------- *
+ * The census says which outcomes a run has; the audit says whether an outcome is coherent.  It
+ * reads the FINAL records of the np nodes of one system (dsm_node_state).  For address a in
+ * [0, 16 * np): home h = a >> 4, entry i = a & 15, cache slot s = a & 3.
+ *
+ *   held       node c holds slot s when cache_state[s] != INVALID (3) and cache_addr[s] != 0xFF.
+ *   bad line   a held line with cache_state[s] > 3, cache_addr[s] >= 16 * np or
+ *              (cache_addr[s] & 3) != s.  It is counted and takes part in nothing else, so
+ *              arbitrary bytes never index out of range.
+ *   bad entry  a directory entry with dir_state[i] > 2.  It is counted, and its address is left
+ *              out of the three DIR classes only.
+ *   ME(a)      the bitmask of nodes that hold a in MODIFIED or EXCLUSIVE; SH(a) in SHARED.
+ *   bv, d, m   dir_bv[i] (the whole byte), dir_state[i] and memory[i] of the home node.
+ *
+ * An address violates
+ *   DSM_AUDIT_MULTI_OWNER       popcount(ME) > 1
+ *   DSM_AUDIT_OWNER_AND_SHARER  ME != 0 && SH != 0
+ *   DSM_AUDIT_DIR_EM            d == EM && (bv != ME || popcount(ME) != 1)
+ *   DSM_AUDIT_DIR_S             d == S && (bv != SH || SH == 0 || ME != 0)
+ *   DSM_AUDIT_DIR_U             d == U && (ME | SH) != 0
+ *   DSM_AUDIT_STALE_VALUE       some node holds a in EXCLUSIVE or SHARED with cache_value != m
+ *                               (MODIFIED is exempt)
+ * and a system has DSM_AUDIT_BAD_RECORD with at least one bad line or bad entry.  bv is compared
+ * as the whole byte, so at np 4 a set bit 4..7 is a mismatch.
+ *
+ * A system's audit word: bits 0..6 the classes that some address violates (bit 7 zero), bits
+ * 8..15 the number of addresses that violate any of classes 0..5 (0..128), bits 16..23 the lowest
+ * such address or 0xFF when there is none, bits 24..31 bad lines plus bad entries (at most 160).
+ * A coherent system's word is DSM_AUDIT_COHERENT.
+ *
+ * The summary is DSM_NAUDIT x uint64: everything a sum except inv_first, a max (the bitwise NOT
+ * of the lowest ABSOLUTE system id, 0 = none, as in the census), so the summaries of shards and
+ * batches merge (dsm_audit_merge) and every device update is a commutative atomic. */
+enum { DSM_AUDIT_MULTI_OWNER = 0, DSM_AUDIT_OWNER_AND_SHARER = 1, DSM_AUDIT_DIR_EM = 2,
+       DSM_AUDIT_DIR_S = 3, DSM_AUDIT_DIR_U = 4, DSM_AUDIT_STALE_VALUE = 5, DSM_AUDIT_BAD_RECORD = 6 };
+#define DSM_AUDIT_NCLASS 7
+#define DSM_AUDIT_COHERENT 0x00FF0000u
+#define DSM_NAUDIT 32
+typedef struct dsm_audit {
+    uint64_t systems;
+    uint64_t violating;        /* systems with any of bits 0..6                              */
+    uint64_t lines;            /* sum over systems of the word's bits 8..15                  */
+    uint64_t bad_items;        /* sum of bits 24..31                                         */
+    uint64_t by_class[8];      /* systems per class; slot 7 is zero                          */
+    uint64_t inv_first[8];     /* max, not sum: ~(lowest system id with the class); slot 7:
+                                * with any class; 0 = none                                   */
+    uint64_t reserved[12];     /* zero                                                       */
+} dsm_audit;
+/* Audit of n_sys systems whose record k * np + c (system k, node c) is
+ * d_states[(k * np + c) * state_stride] (16-byte aligned device buffer, the convention of
+ * dsm_format_dumps_device), with ids first_sys + k (64-bit).  d_words (may be NULL) receives
+ * n_sys words; d_audit (may be NULL) is ACCUMULATED into (zero it first for one run).  Both NULL
+ * with n_sys > 0 is DSM_E_INVAL; n_sys == 0 is a no-op.  Asynchronous on `stream`. */
+int dsm_audit_states_device(dsm_ctx *ctx, const dsm_node_state *d_states, uint32_t state_stride,
+                            uint64_t n_sys, uint64_t first_sys, uint32_t *d_words,
+                            dsm_audit *d_audit, void *stream);
+/* the same over the final records of systems first_sys .. first_sys+n_sys-1 of the last run
+ * (needs DSM_F_SNAPSHOTS; state and argument errors as dsm_census_run_nodes_device).  Ids are
+ * the systems' indices in the run. */
+int dsm_audit_run_device(dsm_ctx *ctx, uint64_t first_sys, uint64_t n_sys, uint32_t *d_words,
+                         dsm_audit *d_audit, void *stream);
+/* dsm_audit_states_device on the host (no GPU needed): the plain reference.  np is 4 or 8;
+ * words and audit (either may be NULL, not both when n_sys > 0) are overwritten. */
+int dsm_audit_states(int np, const dsm_node_state *states, uint32_t state_stride, uint64_t n_sys,
+                     uint64_t first_sys, uint32_t *words, dsm_audit *audit);
+/* dst += src: sums, and the max for inv_first (host only) */
+int dsm_audit_merge(dsm_audit *dst, const dsm_audit *src);
+/* "MULTI_OWNER" .. "BAD_RECORD" for bits 0..6, NULL for any other bit (host only) */
+const char *dsm_audit_class_name(int bit);
 
 /* ---- multi-GPU group: RCCL over xGMI --------------------------------------- *
  * Systems are independent, so an ensemble shards over GPUs with no data-path exchange; the
