@@ -54,6 +54,20 @@
  *                        audit class <NAME>: C schedules, first F
  *                    over all N variants, one class line per class that occurred.  Exit codes do
  *                    not change.
+ *   --check DIR      only with --explore: can the system produce the output files in DIR, and
+ *                    how often?  DIR/core_<n>_output.txt is read back into a record
+ *                    (dsm_read_dump; a core without a file is one that wrote none) and looked up
+ *                    in the per-core census, and the np records together are compared with the
+ *                    dumps of every outcome's first variant (outcomes by dumps, whatever
+ *                    --explore-kind says).  After the explore output:
+ *                        check core c: count C of N first F
+ *                        check core c: never produced
+ *                        check core c: no file; C of N schedules write none
+ *                        check joint: count C of N first F
+ *                        check joint: never produced; closest agrees on A of NP cores (count C first F)
+ *                    Exits 0 when the joint outcome was produced, 4 when it was not, 3 when it
+ *                    was not found and a census table dropped a system, 1 when a file in DIR is
+ *                    not what printProcessorState prints (it is named on stderr).
  */
 #include <errno.h>
 #include <stdio.h>
@@ -68,7 +82,7 @@
 static void usage(const char *argv0) {
     fprintf(stderr, "Usage: %s [--np 4|8] [--max-instr N] [--device D] [--quiet] [--issue-order FILE]\n"
                     "          [--schedule SEED:THRESH] [--explore N [--explore-dir DIR]\n"
-                    "          [--explore-kind dumps|final|full]] [--audit] <test_directory>\n", argv0);
+                    "          [--explore-kind dumps|final|full] [--check DIR]] [--audit] <test_directory>\n", argv0);
 }
 
 static const char *const status_names[5] = {"COMPLETED", "DEADLOCKED", "RING_OVERFLOW", "ASSERT_FAILED",
@@ -86,12 +100,14 @@ static void print_audit_word(const char *prefix, uint32_t w) {
 /* --explore: n copies of the parsed system under schedule (seed, thresh), one run with
  * snapshots, both censuses on the device.  Returns the process exit code. */
 static int explore(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces, const uint32_t *counts,
-                   uint32_t n, unsigned long long seed, unsigned thresh, int kind, const char *out_dir, int audit) {
+                   uint32_t n, unsigned long long seed, unsigned thresh, int kind, const char *out_dir, int audit,
+                   const char *check_dir) {
     uint32_t cap = DSM_CENSUS_MIN_CAP;
     while (cap < n) cap <<= 1;
     const size_t words = DSM_CENSUS_WORDS(cap), slot = (size_t)np * stride;
     const size_t tr_bytes = (size_t)n * slot * sizeof(uint16_t), cn_bytes = (size_t)n * np * sizeof(uint32_t);
-    const size_t cen_bytes = (size_t)(1 + np) * words * sizeof(uint64_t);
+    /* tables: the outcomes, one per core, and with --check the outcomes by dumps */
+    const size_t cen_bytes = (size_t)(1 + np + (check_dir ? 1 : 0)) * words * sizeof(uint64_t);
     uint16_t *h_tr = (uint16_t *)malloc(tr_bytes), *d_tr = NULL;
     uint32_t *h_cn = (uint32_t *)malloc(cn_bytes), *d_cn = NULL;
     uint64_t *cen = (uint64_t *)malloc(cen_bytes), *d_cen = NULL;
@@ -102,7 +118,21 @@ static int explore(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces
     dsm_audit *d_aud = NULL, aud;
     int rc = DSM_OK, code = EXIT_FAILURE;
     const char *what = "out of memory";
+    dsm_node_state want[DSM_MAX_NP];                /* --check: the records of DIR's files ... */
+    int have[DSM_MAX_NP] = {0};                     /* ... and which cores have one */
     if (!h_tr || !h_cn || !cen || !outc) goto fail;
+    for (int c = 0; check_dir && c < np; ++c) {
+        rc = dsm_read_dump(c, check_dir, &want[c]);
+        have[c] = rc == DSM_OK;
+        if (rc == DSM_E_FORMAT) {
+            fprintf(stderr, "Error: %s/core_%d_output.txt is not a dump of core %d as printProcessorState prints it\n",
+                    check_dir, c, c);
+            what = NULL;
+            goto fail;
+        }
+        if (rc != DSM_OK && rc != DSM_E_IO) { what = "dsm_read_dump"; goto fail; }
+        rc = DSM_OK;
+    }
     for (uint32_t i = 0; i < n; ++i) {
         memcpy(h_tr + (size_t)i * slot, traces, slot * sizeof(uint16_t));
         memcpy(h_cn + (size_t)i * np, counts, (size_t)np * sizeof(uint32_t));
@@ -124,6 +154,11 @@ static int explore(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces
     if ((rc = dsm_census_device(ctx, d_res, n, 0, kind, d_cen, cap, NULL))) goto fail;
     what = "dsm_census_run_nodes_device";
     if ((rc = dsm_census_run_nodes_device(ctx, 0, n, d_cen + words, cap, NULL))) goto fail;
+    if (check_dir) {
+        what = "dsm_census_device";
+        if ((rc = dsm_census_device(ctx, d_res, n, 0, DSM_CENSUS_DUMPS, d_cen + (size_t)(1 + np) * words, cap, NULL)))
+            goto fail;
+    }
     if (audit) {
         what = "device memory";
         if (hipMalloc((void **)&d_words, (size_t)n * sizeof(uint32_t)) != hipSuccess ||
@@ -191,6 +226,59 @@ static int explore(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces
                        (unsigned long long)aud.by_class[b], (unsigned long long)~aud.inv_first[b]);
     }
     code = dropped ? 3 : 0;
+    if (check_dir) {
+        for (int c = 0; c < np; ++c) {
+            const uint64_t *t = cen + (size_t)(1 + c) * words;
+            uint64_t key = DSM_OUTCOME_MISSING;
+            if (have[c]) {
+                key = dsm_node_hash(c, &want[c], 15);
+                if (key < 2) key = 2;                   /* as the per-core census maps them */
+            }
+            dsm_outcome hit;
+            what = "dsm_census_find";
+            if ((rc = dsm_census_find(t, cap, key, &hit)) < 0) goto fail;
+            if (!have[c])
+                printf("check core %d: no file; %llu of %u schedules write none\n", c,
+                       (unsigned long long)(rc ? hit.count : 0), n);
+            else if (rc)
+                printf("check core %d: count %llu of %u first %llu\n", c, (unsigned long long)hit.count, n,
+                       (unsigned long long)hit.first_sys);
+            else
+                printf("check core %d: never produced\n", c);
+            rc = DSM_OK;
+        }
+        /* jointly: every outcome by dumps, judged by its first variant's dump records */
+        const uint64_t *t = cen + (size_t)(1 + np) * words;
+        uint64_t kd = 0, cnt[DSM_MAX_NP + 1] = {0}, first[DSM_MAX_NP + 1];
+        dropped += t[2];
+        what = "dsm_census_sorted";
+        if ((rc = dsm_census_sorted(t, cap, outc, cap, &kd))) goto fail;
+        for (uint64_t o = 0; o < kd; ++o) {
+            int agree = 0;
+            for (int c = 0; c < np; ++c) {
+                dsm_node_state dump, fin;
+                what = "dsm_get_node_state";
+                if ((rc = dsm_get_node_state(ctx, outc[o].first_sys, c, &dump, &fin))) goto fail;
+                const int wrote = (fin.flags >> 1) & 1;
+                agree += wrote == have[c] && (!wrote || !memcmp(&dump, &want[c], 60));
+            }
+            if (!cnt[agree] || outc[o].first_sys < first[agree]) first[agree] = outc[o].first_sys;
+            cnt[agree] += outc[o].count;
+        }
+        if (cnt[np]) {
+            printf("check joint: count %llu of %u first %llu\n", (unsigned long long)cnt[np], n,
+                   (unsigned long long)first[np]);
+        } else {
+            int a = np - 1;
+            while (a >= 0 && !cnt[a]) --a;
+            if (a >= 0)
+                printf("check joint: never produced; closest agrees on %d of %d cores (count %llu first %llu)\n", a,
+                       np, (unsigned long long)cnt[a], (unsigned long long)first[a]);
+            else
+                printf("check joint: never produced\n");
+        }
+        code = cnt[np] ? 0 : dropped ? 3 : 4;
+    }
     what = NULL;
 fail:
     if (what) fprintf(stderr, "Error: explore: %s%s%s\n", what, rc ? ": " : "", rc ? dsm_strerror(rc) : "");
@@ -213,7 +301,7 @@ int main(int argc, char **argv) {
     unsigned sched_thresh = DSM_SCHED_LOCKSTEP;
     int have_sched = 0, explore_kind = DSM_CENSUS_DUMPS, explore_opts = 0;
     long long explore_n = 0;
-    const char *explore_dir = NULL;
+    const char *explore_dir = NULL, *check_dir = NULL;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--np") && i + 1 < argc) np = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--max-instr") && i + 1 < argc) max_instr = (uint32_t)atoi(argv[++i]);
@@ -230,6 +318,7 @@ int main(int argc, char **argv) {
             if (explore_n < 1 || explore_n > (long long)DSM_CENSUS_MAX_CAP) { usage(argv[0]); return EXIT_FAILURE; }
         }
         else if (!strcmp(argv[i], "--explore-dir") && i + 1 < argc) { explore_dir = argv[++i]; explore_opts = 1; }
+        else if (!strcmp(argv[i], "--check") && i + 1 < argc) { check_dir = argv[++i]; explore_opts = 1; }
         else if (!strcmp(argv[i], "--explore-kind") && i + 1 < argc) {
             const char *v = argv[++i];
             explore_opts = 1;
@@ -309,7 +398,7 @@ int main(int argc, char **argv) {
 
     if (explore_n) {
         const int code = explore(ctx, np, stride, traces, counts, (uint32_t)explore_n, sched_seed, sched_thresh,
-                                 explore_kind, explore_dir, audit);
+                                 explore_kind, explore_dir, audit, check_dir);
         dsm_close(ctx);
         free(traces);
         return code;

@@ -5,8 +5,9 @@
  *                                             (assignment.c:792-818)
  *   dsm_format_dump / dsm_write_dump          replace printProcessorState (:824-876),
  *                                             byte-for-byte
+ *   dsm_parse_dump / dsm_read_dump            their inverse: an output file back into a record
  *   dsm_node_hash                             canonical 64-bit hash of a node record
- *   dsm_outcome_key / dsm_census_results / _merge / _sorted
+ *   dsm_outcome_key / dsm_census_results / _merge / _sorted / _find
  *                                             the outcome census on the host
  *   dsm_audit_states / _merge / _class_name   the coherence audit on the host
  */
@@ -128,6 +129,105 @@ int dsm_write_dump(int node, const dsm_node_state *st, const char *dir) {
     size_t w = fwrite(buf, 1, (size_t)len, f);
     int rc = fclose(f);
     return (w == (size_t)len && rc == 0) ? DSM_OK : DSM_E_IO;
+}
+
+/* ---- the dump reader (include/dsm.h): the plain reference of unfmt_kernel (dsm_text.hip) ----
+ * Acceptance is the formatter's: the 55 lines are scanned loosely with sscanf, the record that
+ * scan yields is formatted again, and only a text equal to that byte for byte is accepted. */
+
+/* index of `s` among names[0 .. n), or -1 */
+static int name_index(const char *s, const char *const *names, int n) {
+    for (int i = 0; i < n; ++i)
+        if (!strcmp(s, names[i])) return i;
+    return -1;
+}
+
+/* z is cut into its lines in place (sscanf measures its whole input on every call) */
+static int parse_dump_loose(char *z, int *node, dsm_node_state *st) {
+    static const char *const cst[] = {"MODIFIED", "EXCLUSIVE", "SHARED", "INVALID"};
+    static const char *const dst[] = {"EM", "S", "U"};
+    const char *line[55];
+    int nl = 0;
+    for (char *p = z; *p && nl < 55; ++nl) {            /* line starts */
+        line[nl] = p;
+        char *e = strchr(p, '\n');
+        if (!e) return DSM_E_FORMAT;
+        *e = 0;
+        p = e + 1;
+    }
+    if (nl != 55) return DSM_E_FORMAT;
+    int idx, nd;
+    unsigned a, b;
+    char s[16];
+    if (sscanf(line[1], " Processor Node: %9d", &nd) != 1 || nd < 0 || nd >= DSM_MAX_NP) return DSM_E_FORMAT;
+    for (int i = 0; i < DSM_MEM_SIZE; ++i) {            /* lines 7 .. 22 */
+        int v;
+        if (sscanf(line[7 + i], "| %9d | %8x | %9d |", &idx, &a, &v) != 3) return DSM_E_FORMAT;
+        st->memory[i] = (uint8_t)v;
+    }
+    for (int i = 0; i < DSM_MEM_SIZE; ++i) {            /* lines 28 .. 43 */
+        if (sscanf(line[28 + i], "| %9d | %8x | %2s | %10x |", &idx, &a, s, &b) != 4) return DSM_E_FORMAT;
+        const int d = name_index(s, dst, 3);
+        if (d < 0) return DSM_E_FORMAT;
+        st->dir_state[i] = (uint8_t)d;
+        st->dir_bv[i] = (uint8_t)b;
+    }
+    for (int i = 0; i < DSM_CACHE_SIZE; ++i) {          /* lines 49 .. 52 */
+        int v;
+        if (sscanf(line[49 + i], "| %9d | %8x | %9d | %9s", &idx, &a, &v, s) != 4) return DSM_E_FORMAT;
+        const int c = name_index(s, cst, 4);
+        if (c < 0) return DSM_E_FORMAT;
+        st->cache_addr[i] = (uint8_t)a;
+        st->cache_value[i] = (uint8_t)v;
+        st->cache_state[i] = (uint8_t)c;
+    }
+    *node = nd;
+    return DSM_OK;
+}
+
+int dsm_parse_dump(const char *text, size_t len, int *node, dsm_node_state *st) {
+    if (!node || !st || (len && !text)) return DSM_E_INVAL;
+    char z[DSM_DUMP_MAX + 1], again[DSM_DUMP_MAX + 2];
+    dsm_node_state r;
+    int nd = -1;
+    memset(&r, 0, sizeof r);
+    int rc = DSM_E_FORMAT;
+    if (len >= DSM_DUMP_BASE && len <= DSM_DUMP_MAX) {
+        memcpy(z, text, len);
+        z[len] = 0;
+        r.flags = 0x02;
+        if (strlen(z) == len && parse_dump_loose(z, &nd, &r) == DSM_OK &&
+            dsm_format_dump(nd, &r, again, sizeof again) == (int)len && !memcmp(again, text, len))
+            rc = DSM_OK;
+    }
+    if (rc != DSM_OK) {
+        nd = -1;
+        memset(&r, 0, sizeof r);
+    }
+    *node = nd;
+    *st = r;
+    return rc;
+}
+
+int dsm_read_dump(int node, const char *dir, dsm_node_state *st) {
+    if (!st || node < 0 || node >= DSM_MAX_NP) return DSM_E_INVAL;
+    char buf[DSM_DUMP_MAX + 2], path[512];
+    if (dir) snprintf(path, sizeof path, "%s/core_%d_output.txt", dir, node);
+    else snprintf(path, sizeof path, "core_%d_output.txt", node);         /* :831 */
+    memset(st, 0, sizeof *st);
+    FILE *f = fopen(path, "rb");
+    if (!f) return DSM_E_IO;
+    const size_t len = fread(buf, 1, sizeof buf, f);      /* one byte past the longest dump */
+    const int bad = ferror(f);
+    fclose(f);
+    if (bad) return DSM_E_IO;
+    int nd = -1;
+    const int rc = dsm_parse_dump(buf, len, &nd, st);
+    if (rc == DSM_OK && nd != node) {
+        memset(st, 0, sizeof *st);
+        return DSM_E_FORMAT;
+    }
+    return rc;
 }
 
 int dsm_format_issue_trace(const uint32_t *events, uint32_t n, char *buf, size_t cap) {
@@ -282,6 +382,23 @@ int dsm_census_sorted(const uint64_t *census, uint32_t cap, dsm_outcome *out, ui
     memcpy(out, all, (size_t)(k < out_cap ? k : out_cap) * sizeof *all);
     free(all);
     return DSM_OK;
+}
+
+int dsm_census_find(const uint64_t *census, uint32_t cap, uint64_t key, dsm_outcome *out) {
+    if (!census || !census_cap_ok(cap) || key == 0) return DSM_E_INVAL;
+    uint64_t s = key & (cap - 1u);
+    for (uint32_t p = 0; p < cap; ++p, s = (s + 1u) & (cap - 1u)) {
+        const uint64_t *slot = census + 4 + 4 * s;
+        if (slot[0] == 0) return 0;                 /* the chain ends: slots are never freed */
+        if (slot[0] != key) continue;
+        if (out) {
+            out->key = key;
+            out->count = slot[1];
+            out->first_sys = ~slot[2];
+        }
+        return 1;
+    }
+    return 0;
 }
 
 /* ---- coherence audit (include/dsm.h): the plain reference of csrc/dsm_audit.hip ---------- */

@@ -8,6 +8,8 @@
  *   fmt_kernel   printProcessorState (:824-876) for whole ensembles: the 55-line dump of every
  *                selected node record, byte-identical to the reference's fprintf output,
  *                written into fixed DSM_DUMP_SLOT-byte slots (HBM-write-bound).
+ *   unfmt_kernel fmt_kernel's inverse: dump slots back into node records, accepted exactly
+ *                when the formatter prints them (HBM-read-bound).
  *   textlen_kernel / textgen_kernel / scan_kernel
  *                synthetic core files in the shipped tests' text format, from the
  *                counter-based generator (bench and test inputs for parse_kernel).
@@ -181,6 +183,210 @@ __global__ void __launch_bounds__(NT) fmt_kernel(const uint8_t *recs, uint64_t r
     }
 }
 
+/* ---- dump reader: fmt_kernel turned round --------------------------------------------- *
+ * Acceptance is dsm_parse_dump's (dsm_host.c): a slot is read exactly when its d_len bytes are
+ * what the formatter prints for node k % np and some record.  A workgroup takes FR slots per
+ * iteration, NT / FR lanes to a slot, 16 bytes per lane and load (the next tile's loads are in
+ * flight while this one is worked on):
+ *   (a) on their way into LDS, the chunks below the cache section are compared with the node's
+ *       template under a mask that leaves out the bytes of the variable fields;
+ *   (b) one work item per variable field, as in fmt_kernel: it accepts the field's canonical
+ *       form only (%3d right-aligned without a leading zero and at most 255, upper-case hex,
+ *       "EM" / " S" / " U", the four cache state names) and writes its bytes of the record.  The
+ *       cache section moves with the EXCLUSIVE lines before it (a line is EXCLUSIVE when its state
+ *       field starts with 'E'; the state item then holds the field to the whole name), so its
+ *       items compare their own fixed bytes at the shifted position, and the first trailer item
+ *       holds d_len to DSM_DUMP_BASE + the number of EXCLUSIVE lines.
+ * With that length every byte that can decide lies below d_len: the tail of a slot never does
+ * (an absent or refused slot's bytes are compared too, and the result is not looked at). */
+constexpr uint32_t UNFMT_FR = 16, UNFMT_NT = 256;   /* records per iteration, threads */
+constexpr uint32_t UNFMT_GRID_PER_CU = 3;           /* grid cap: three tiles' LDS fit a CU */
+constexpr uint32_t CMP16 = CAC0 / 16;               /* whole 16-byte chunks below the cache section */
+static_assert(CAC0 - 16 * CMP16 == 4, "the last compared chunk holds four bytes of fixed text");
+
+/* %3d of 0..255 in canonical form, or 256 */
+DEVI uint32_t undec3(const char *p) {
+    const uint32_t a = (uint8_t)p[0], b = (uint8_t)p[1], dc = (uint32_t)(uint8_t)p[2] - '0';
+    if (dc > 9u) return 256u;
+    if (a == ' ' && b == ' ') return dc;
+    const uint32_t db = b - '0';
+    if (db > 9u) return 256u;
+    if (a == ' ') return db ? db * 10u + dc : 256u;
+    const uint32_t da = a - '0';
+    if (da - 1u > 8u) return 256u;
+    const uint32_t v = da * 100u + db * 10u + dc;
+    return v <= 255u ? v : 256u;
+}
+/* %02X: two upper-case hex digits, or >= 256 */
+DEVI uint32_t unhex2(const char *p) {
+    const uint32_t a = (uint8_t)p[0], b = (uint8_t)p[1];
+    const uint32_t ha = a - '0' < 10u ? a - '0' : (a - 'A' < 6u ? a - 'A' + 10u : 256u);
+    const uint32_t hb = b - '0' < 10u ? b - '0' : (b - 'A' < 6u ? b - 'A' + 10u : 256u);
+    return (ha << 4) | hb;
+}
+/* the bytes of s (NUL-terminated) at p */
+DEVI bool same(const char *p, const char *s) {
+    bool ok = true;
+    for (uint32_t j = 0; s[j]; ++j) ok &= p[j] == s[j];
+    return ok;
+}
+
+/* byte `pos` of the text below the cache section belongs to a variable field */
+DEVI bool field_byte(uint32_t pos) {
+    if (pos >= MEM0 && pos < MEM0 + 16 * MEML) {
+        const uint32_t o = (pos - MEM0) % MEML;
+        return o >= 23 && o <= 25;
+    }
+    if (pos >= DIR0 && pos < DIR0 + 16 * DIRL) {
+        const uint32_t o = (pos - DIR0) % DIRL;
+        return o == 21 || o == 22 || o == 38 || o == 39;
+    }
+    return false;
+}
+
+template <uint32_t FR, uint32_t NT>
+__global__ void __launch_bounds__(NT) unfmt_kernel(const v4u32 *text, const uint32_t *lens, uint64_t n,
+                                                   int np, const uint4 *tpl, uint8_t *recs,
+                                                   uint64_t rec_stride, int32_t *status) {
+    static_assert(FR * 4 <= 64, "the output step and the next tile's setup stay in wave 0");
+    static_assert(NT % FR == 0, "whole lanes per record");
+    constexpr uint32_t LPR = NT / FR;                          /* lanes per record */
+    constexpr uint32_t PER = (SLOT16 + LPR - 1) / LPR;         /* 16-byte loads per lane and tile */
+    __shared__ uint4 s_buf[FR * SLOT16];
+    __shared__ uint4 s_tpl[DSM_MAX_NP * SLOT16];
+    __shared__ uint4 s_mask[CMP16 + 1];                        /* 0xFF: fixed text below CAC0 */
+    __shared__ uint32_t s_rec[FR][16];
+    __shared__ uint32_t s_len[FR], s_bad[FR];
+    __shared__ uint32_t s_cmp[2][FR];                          /* (a)'s verdicts, by tile parity */
+    char *const sb = reinterpret_cast<char *>(s_buf);
+    const uint32_t tid = threadIdx.x, rr = tid / LPR, l = tid % LPR;
+    for (uint32_t i = tid; i < (uint32_t)np * SLOT16; i += NT) s_tpl[i] = tpl[i];
+    for (uint32_t c = tid; c <= CMP16; c += NT) {
+        uint32_t w[4] = {0, 0, 0, 0};
+        for (uint32_t b = 0; b < 16; ++b) {
+            const uint32_t pos = 16 * c + b;
+            if (pos < CAC0 && !field_byte(pos)) w[b >> 2] |= 0xFFu << (8 * (b & 3u));
+        }
+        s_mask[c] = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+    if (tid < 2 * FR) s_cmp[tid / FR][tid % FR] = 0u;
+    v4u32 pv[PER];
+    auto fetch = [&](uint64_t b) {
+        const uint32_t nr = (n - b) < FR ? (uint32_t)(n - b) : FR;
+#pragma unroll
+        for (uint32_t j = 0; j < PER; ++j) {
+            const uint32_t c = l + j * LPR;
+            if (rr < nr && c < SLOT16) pv[j] = __builtin_nontemporal_load(text + (b + rr) * SLOT16 + c);
+        }
+    };
+    if ((uint64_t)blockIdx.x * FR < n) fetch((uint64_t)blockIdx.x * FR);
+    __syncthreads();
+    uint32_t par = 0;
+    for (uint64_t base = (uint64_t)blockIdx.x * FR; base < n; base += (uint64_t)gridDim.x * FR, par ^= 1u) {
+        const uint32_t nr = (n - base) < FR ? (uint32_t)(n - base) : FR;
+        /* (a) the tile into LDS, its fixed text below the cache section held to the template on
+         * the way; lengths, verdicts and the unprinted word of each record */
+        const uint32_t node = ((uint32_t)(base % (uint64_t)np) + rr) % (uint32_t)np;
+        uint32_t diff = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < PER; ++j) {
+            const uint32_t c = l + j * LPR;
+            if (rr < nr && c < SLOT16) {
+                const uint4 x = make_uint4(pv[j].x, pv[j].y, pv[j].z, pv[j].w);
+                s_buf[rr * SLOT16 + c] = x;
+                if (c <= CMP16) {
+                    const uint4 y = s_tpl[node * SLOT16 + c], m = s_mask[c];
+                    diff |= ((x.x ^ y.x) & m.x) | ((x.y ^ y.y) & m.y) | ((x.z ^ y.z) & m.z) | ((x.w ^ y.w) & m.w);
+                }
+            }
+        }
+        if (diff) s_cmp[par][rr] = 1u;
+        if (tid < nr) {
+            const uint32_t len = lens[base + tid];
+            s_len[tid] = len;
+            s_bad[tid] = len != 0u && len - DSM_DUMP_BASE > (uint32_t)(DSM_DUMP_MAX - DSM_DUMP_BASE);
+            s_rec[tid][15] = 0x0200u;                  /* pending 0, flags 0x02 (dumped), issued 0 */
+        }
+        __syncthreads();
+        if (base + (uint64_t)gridDim.x * FR < n) fetch(base + (uint64_t)gridDim.x * FR);
+        /* (b) one work item per variable field group, type-major as in fmt_kernel */
+        for (uint32_t i = tid; i < FR * ITEMS; i += NT) {
+            uint32_t r, f;
+            if (i < 16 * FR) { r = i >> 4; f = i & 15u; }
+            else if (i < 32 * FR) { r = (i - 16 * FR) >> 4; f = 16 + ((i - 16 * FR) & 15u); }
+            else { r = (i - 32 * FR) / 15u; f = 32 + (i - 32 * FR) % 15u; }
+            if (r >= nr) continue;
+            const uint32_t len = s_len[r];
+            if (len - DSM_DUMP_BASE > (uint32_t)(DSM_DUMP_MAX - DSM_DUMP_BASE)) continue;   /* absent or refused */
+            uint8_t *rb = reinterpret_cast<uint8_t *>(s_rec[r]);
+            const char *t = sb + r * SLOT;
+            bool ok;
+            if (f < 16) {                                        /* node.memory[f], %5d */
+                const uint32_t v = undec3(t + MEM0 + MEML * f + 23);
+                ok = v < 256u;
+                rb[f] = (uint8_t)v;
+            } else if (f < 32) {                                 /* directory[f-16] */
+                const uint32_t k = f - 16;
+                const char *ln = t + DIR0 + DIRL * k;
+                const char c0 = ln[21], c1 = ln[22];
+                const uint32_t st = (c0 == 'E' && c1 == 'M') ? 0u : (c0 == ' ' && c1 == 'S') ? 1u
+                                  : (c0 == ' ' && c1 == 'U') ? 2u : 3u;
+                const uint32_t bv = unhex2(ln + 38);
+                ok = st < 3u && bv < 256u;
+                rb[32 + k] = (uint8_t)st;
+                rb[16 + k] = (uint8_t)bv;
+            } else {
+                /* cache section: 3 items per line + 3 for the trailer, each at its line's shift */
+                const uint32_t q = f - 32;
+                uint32_t em = 0, pop = 0;
+                for (uint32_t k = 0; k < 4; ++k)
+                    if (t[CAC0 + CACL * k + pop + 29] == 'E') { em |= 1u << k; ++pop; }
+                if (q < 12) {
+                    const uint32_t k = q / 3, part = q - 3 * k;
+                    const char *ln = t + CAC0 + CACL * k + __builtin_popcount(em & ((1u << k) - 1u));
+                    if (part == 0) {                          /* "|  %3d  |  0x%02X" */
+                        const uint32_t a = unhex2(ln + 13);
+                        ok = same(ln, "|    ") && ln[5] == (char)('0' + k) && same(ln + 6, "  |  0x") && a < 256u;
+                        rb[48 + k] = (uint8_t)a;
+                    } else if (part == 1) {                   /* "   |  %3d  |  " */
+                        const uint32_t v = undec3(ln + 21);
+                        ok = same(ln + 15, "   |  ") && same(ln + 24, "  |  ") && v < 256u;
+                        rb[52 + k] = (uint8_t)v;
+                    } else {                                  /* "%8s \t|\n" */
+                        const uint32_t st = same(ln + 29, "MODIFIED") ? 0u : same(ln + 29, "EXCLUSIVE") ? 1u
+                                          : same(ln + 29, "  SHARED") ? 2u : same(ln + 29, " INVALID") ? 3u : 4u;
+                        ok = st < 4u && same(ln + 29 + (st == 1u ? 9u : 8u), " \t|\n");
+                        rb[56 + k] = (uint8_t)st;
+                    }
+                } else {                                      /* trailer: 3 x 14 bytes, and the length */
+                    const char *e = t + CAC0 + 4 * CACL + pop;
+                    const uint32_t j0 = 14u * (q - 12);
+                    ok = q != 12 || len == DSM_DUMP_BASE + pop;
+                    for (uint32_t j = j0; j < j0 + 14u; ++j) ok &= e[j] == (j < 40u ? '-' : '\n');
+                }
+            }
+            if (!ok) s_bad[r] = 1u;
+        }
+        __syncthreads();
+        /* (c) records (four 16-byte stores each) and statuses; wave 0 alone, which also clears
+         * this parity's verdicts (used again two tiles on) and starts the next tile's lengths,
+         * so no barrier is needed before the loop turns */
+        if (tid < FR * 4) {
+            const uint32_t r = tid >> 2, q = tid & 3u;
+            const bool bad = (s_bad[r] | s_cmp[par][r]) != 0u;
+            if (r < nr) {
+                const bool ok = s_len[r] != 0u && !bad;
+                v4u32 v;
+                v.x = ok ? s_rec[r][4 * q + 0] : 0u; v.y = ok ? s_rec[r][4 * q + 1] : 0u;
+                v.z = ok ? s_rec[r][4 * q + 2] : 0u; v.w = ok ? s_rec[r][4 * q + 3] : 0u;
+                *reinterpret_cast<v4u32 *>(recs + (base + r) * rec_stride + q * 16) = v;
+                if (status && q == 0u)
+                    status[base + r] = s_len[r] == 0u ? DSM_DUMP_ABSENT : bad ? DSM_E_FORMAT : DSM_OK;
+            }
+            if (q == 0u) s_cmp[par][r] = 0u;
+        }
+    }
+}
 
 /* ---- trace parser ------------------------------------------------------------------- */
 constexpr uint32_t PHALO = 32;      /* halo bytes (a chunk is <= 19) */
@@ -714,6 +920,30 @@ extern "C" int dsm_format_run_dumps_device(dsm_ctx *c, int view, uint64_t first_
     HIPCK(hipSetDevice(c->device));
     const uint8_t *recs = (const uint8_t *)c->d_recs + first_sys * (uint64_t)c->cfg.np * 128 + view * 64;
     return launch_fmt(c, recs, 128, n_sys * (uint64_t)c->cfg.np, d_text, d_len, (hipStream_t)stream);
+}
+
+extern "C" int dsm_parse_dumps_device(dsm_ctx *c, const char *d_text, const uint32_t *d_len, uint64_t n,
+                                      dsm_node_state *d_states, uint32_t state_stride,
+                                      int32_t *d_status, void *stream) {
+    if (!c || state_stride == 0) return DSM_E_INVAL;
+    if (((uintptr_t)d_text & 15u) || ((uintptr_t)d_states & 15u) || ((uintptr_t)d_len & 3u) ||
+        ((uintptr_t)d_status & 3u))
+        return DSM_E_INVAL;
+    if (n == 0) return DSM_OK;
+    if (!d_text || !d_len || !d_states) return DSM_E_INVAL;
+    HIPCK(hipSetDevice(c->device));
+    int rc = ensure_templates(c);
+    if (rc) return rc;
+    /* the grid is capped at what the tiles' LDS lets a CU hold: a grid-stride loop over tiles */
+    uint64_t blocks = (n + UNFMT_FR - 1) / UNFMT_FR;
+    const uint64_t cap = (uint64_t)c->cus * UNFMT_GRID_PER_CU;
+    if (blocks > cap) blocks = cap;
+    hipLaunchKernelGGL((unfmt_kernel<UNFMT_FR, UNFMT_NT>), dim3((unsigned)blocks), dim3(UNFMT_NT), 0,
+                       (hipStream_t)stream, (const v4u32 *)d_text, d_len, n, c->cfg.np,
+                       (const uint4 *)c->d_dump_tpl, (uint8_t *)d_states,
+                       (uint64_t)state_stride * sizeof(dsm_node_state), d_status);
+    HIPCK(hipGetLastError());
+    return DSM_OK;
 }
 
 extern "C" int dsm_write_run_dumps(dsm_ctx *c, uint64_t sys, uint32_t node_mask, const char *dir) {

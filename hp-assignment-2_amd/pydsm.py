@@ -40,6 +40,7 @@ assert len(COUNTER_FIELDS) == NCOUNTERS
 MAX_SLOT = COUNTER_FIELDS.index("max_rounds")   # the one counter that is a max, not a sum
 
 DUMP_BASE, DUMP_MAX, DUMP_SLOT = 1954, 1958, 1968
+DUMP_ABSENT = 1                              # DSM_DUMP_ABSENT: status of a slot of length 0
 VIEW_DUMP, VIEW_FINAL = 0, 1
 E_INVAL, E_DEVICE, E_NOMEM, E_IO, E_FORMAT, E_STATE, E_RANGE = -1, -2, -3, -4, -5, -6, -7
 
@@ -154,6 +155,11 @@ def lib():
             "dsm_audit_states": (i32, [i32, vp, u32, u64, u64, vp, vp]),
             "dsm_audit_merge": (i32, [vp, vp]),
             "dsm_audit_class_name": (ctypes.c_char_p, [i32]),
+            # ABI 5 (+dump reader): output files back into records
+            "dsm_parse_dump": (i32, [vp, ctypes.c_size_t, ctypes.POINTER(i32), vp]),
+            "dsm_read_dump": (i32, [i32, ctypes.c_char_p, vp]),
+            "dsm_census_find": (i32, [vp, u32, u64, vp]),
+            "dsm_parse_dumps_device": (i32, [vp, vp, vp, u64, vp, u32, vp, vp]),
             # test-only (csrc/dsm_internal.h, not in include/dsm.h)
             "dsm_debug_order_state": (i32, [vp, vp, vp, vp, u64, u64, vp, u32, ctypes.POINTER(u32),
                                             ctypes.POINTER(i32)]),
@@ -284,6 +290,19 @@ def census_sorted(census, cap):
     _check(lib().dsm_census_sorted(_ptr(census), cap, _ptr(out), n.value, ctypes.byref(n)),
            "dsm_census_sorted")
     return out
+
+
+def census_find(census, cap, key):
+    """dsm_census_find: the outcome of `key` in a table as (count, first_sys), or None when the
+    table does not hold it."""
+    census = np.ascontiguousarray(census, dtype=np.uint64).reshape(-1)
+    if _census_cap_ok(cap):
+        assert census.size == CENSUS_WORDS(cap)
+    out = np.zeros(1, dtype=OUTCOME_DTYPE)
+    rc = lib().dsm_census_find(_ptr(census), cap, key, _ptr(out))
+    if rc < 0:
+        raise DsmError(rc, "dsm_census_find")
+    return (int(out[0]["count"]), int(out[0]["first_sys"])) if rc else None
 
 
 # -- coherence audit (ABI 5 +audit) -----------------------------------------------------------
@@ -541,19 +560,8 @@ class Engine:
             raise DsmError(E_INVAL, "explore: k")
         if audit and not self.cfg.flags & F_SNAPSHOTS:
             raise DsmError(E_STATE, "explore: audit needs an engine with snapshots")
-        tr = np.ascontiguousarray(traces, dtype=np.uint16).reshape(1, self.np, self.max_instr)
-        cn = np.ascontiguousarray(counts, dtype=np.uint32).reshape(1, self.np)
-        cap = max(CENSUS_MIN_CAP, 1 << (k - 1).bit_length())
-        dev = torch.device("cuda", self.device)
-        # the library's own staging keeps 16 bytes of slack behind the traces and one count
-        d_tr = torch.zeros(k * tr.size + 8, dtype=torch.int16, device=dev)
-        d_tr[:k * tr.size].view(k, tr.size)[:] = torch.from_numpy(tr.view(np.int16).reshape(-1)).to(dev)
-        d_cn = torch.zeros(k * self.np + 1, dtype=torch.int32, device=dev)
-        d_cn[:k * self.np].view(k, self.np)[:] = torch.from_numpy(cn.view(np.int32).reshape(-1)).to(dev)
-        d_res = torch.zeros(4 * k, dtype=torch.int64, device=dev)
-        d_cnt = torch.zeros(NCOUNTERS, dtype=torch.int64, device=dev)
+        cap, dev, d_tr, d_cn, d_res, d_cnt, st = self._stage_variants(traces, counts, k)
         d_cen = torch.zeros(CENSUS_WORDS(cap), dtype=torch.int64, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
         prev = self._sched
         self.set_schedule(seed, thresh)
         try:
@@ -571,6 +579,90 @@ class Engine:
             return outcomes
         words = d_words.cpu().numpy().view(np.uint32)[outcomes["first_sys"].astype(np.int64)]
         return outcomes, words, d_aud.cpu().numpy().view(AUDIT_DTYPE)[0]
+
+    def _stage_variants(self, traces, counts, k):
+        """k copies of one system in device buffers for an exploration run -> (census cap,
+        device, d_traces, d_counts, d_results, d_counters, stream)."""
+        import torch
+        tr = np.ascontiguousarray(traces, dtype=np.uint16).reshape(1, self.np, self.max_instr)
+        cn = np.ascontiguousarray(counts, dtype=np.uint32).reshape(1, self.np)
+        cap = max(CENSUS_MIN_CAP, 1 << (k - 1).bit_length())
+        dev = torch.device("cuda", self.device)
+        # the library's own staging keeps 16 bytes of slack behind the traces and one count
+        d_tr = torch.zeros(k * tr.size + 8, dtype=torch.int16, device=dev)
+        d_tr[:k * tr.size].view(k, tr.size)[:] = torch.from_numpy(tr.view(np.int16).reshape(-1)).to(dev)
+        d_cn = torch.zeros(k * self.np + 1, dtype=torch.int32, device=dev)
+        d_cn[:k * self.np].view(k, self.np)[:] = torch.from_numpy(cn.view(np.int32).reshape(-1)).to(dev)
+        d_res = torch.zeros(4 * k, dtype=torch.int64, device=dev)
+        d_cnt = torch.zeros(NCOUNTERS, dtype=torch.int64, device=dev)
+        return cap, dev, d_tr, d_cn, d_res, d_cnt, torch.cuda.current_stream(dev).cuda_stream
+
+    def check_dumps(self, traces, counts, k, seed, thresh, dumps):
+        """Can this system produce these output files, and how often?  `dumps` is a list of np
+        items, the text (str or bytes) of core c's core_c_output.txt or None for a core that
+        wrote none.  Runs the k seeded interleavings of Engine.explore (the engine must keep
+        snapshots) with the DUMPS census and the per-core census, and returns a dict:
+          cores    per core {"key", "count", "first"}: the target key (OUTCOME_MISSING for None,
+                   else the node hash of the parsed record over its 15 printed words, 0 and 1
+                   mapped to 2) looked up in that core's table; count 0 and first None: never
+          joint    {"count", "first"} over the DUMPS outcomes whose representative (the first
+                   variant; within one outcome every variant has the same dumps, up to a hash
+                   collision) agrees with the target on all np cores, by the dump records
+          closest  {"agree", "count", "first"} for the highest agreement below np, or None
+          dropped  the tables' dropped systems; when not zero a "never" is not proven
+          k        the number of schedules
+        A text that is not canonical, or prints another node, raises DsmError(E_FORMAT)."""
+        import torch
+        if not 1 <= k <= CENSUS_MAX_CAP:
+            raise DsmError(E_INVAL, "check_dumps: k")
+        if not self.cfg.flags & F_SNAPSHOTS:
+            raise DsmError(E_STATE, "check_dumps: needs an engine with snapshots")
+        if len(dumps) != self.np:
+            raise DsmError(E_INVAL, "check_dumps: one item per core")
+        target, keys = [], []
+        for c, text in enumerate(dumps):
+            if text is None:
+                target.append(None)
+                keys.append(OUTCOME_MISSING)
+                continue
+            node, rec = parse_dump(text)
+            if node != c:
+                raise DsmError(E_FORMAT, f"check_dumps: core {c}'s text prints node {node}")
+            target.append(rec[:60].tobytes())
+            keys.append(max(node_hash(c, rec, 15), 2))
+        cap, dev, d_tr, d_cn, d_res, d_cnt, st = self._stage_variants(traces, counts, k)
+        words = CENSUS_WORDS(cap)
+        d_cen = torch.zeros((1 + self.np) * words, dtype=torch.int64, device=dev)
+        prev = self._sched
+        self.set_schedule(seed, thresh)
+        try:
+            self.run_packed_device(d_tr, d_cn, k, d_res, d_cnt, st)
+            self.census_device(d_res, k, 0, CENSUS_DUMPS, d_cen[:words], cap, st)
+            self.census_run_nodes_device(0, k, d_cen[words:], cap, st)
+            tables = d_cen.cpu().numpy().view(np.uint64).reshape(1 + self.np, words)
+        finally:
+            self.set_schedule(*prev)
+        out = {"k": k, "cores": [], "dropped": int(tables[:, 2].sum())}
+        for c in range(self.np):
+            hit = census_find(tables[1 + c], cap, keys[c])
+            out["cores"].append({"key": keys[c], "count": hit[0] if hit else 0,
+                                 "first": hit[1] if hit else None})
+        by_agree = {}
+        for o in census_sorted(tables[0], cap):
+            rep, agree = int(o["first_sys"]), 0
+            for c in range(self.np):
+                d, f = self.node_state(rep, c)
+                mine = d[:60].tobytes() if f[61] & 2 else None
+                agree += mine == target[c]
+            cnt, first = by_agree.get(agree, (0, rep))
+            by_agree[agree] = (cnt + int(o["count"]), min(first, rep))
+        cnt, first = by_agree.pop(self.np, (0, None))
+        out["joint"] = {"count": cnt, "first": first}
+        out["closest"] = None
+        if by_agree:
+            a = max(by_agree)
+            out["closest"] = {"agree": a, "count": by_agree[a][0], "first": by_agree[a][1]}
+        return out
 
     def node_state(self, sys, node):
         d = np.zeros(64, dtype=np.uint8)
@@ -621,6 +713,15 @@ class Engine:
                                                  ctypes.c_void_p(d_text), ctypes.c_void_p(d_len),
                                                  ctypes.c_void_p(stream)),
                "dsm_format_run_dumps_device")
+
+    def parse_dumps_device(self, d_text, d_len, n, d_states, d_status=None, state_stride=1, stream=0):
+        """dsm_parse_dumps_device: the inverse of format_dumps_device.  Slot k (DUMP_SLOT bytes at
+        d_text, d_len[k] of them text) -> record k at d_states + 64 * k * state_stride and
+        d_status[k] (int32, may be None): 0, DUMP_ABSENT or E_FORMAT.  Pointers or tensors."""
+        _check(lib().dsm_parse_dumps_device(self.ctx, _dptr(d_text, DUMP_SLOT * n), _dptr(d_len, 4 * n), n,
+                                            _dptr(d_states, 64 * ((n - 1) * state_stride + 1) if n else 0),
+                                            state_stride, _dptr(d_status, 4 * n), ctypes.c_void_p(stream)),
+               "dsm_parse_dumps_device")
 
     def write_run_dumps(self, sys, node_mask, out_dir=None):
         _check(lib().dsm_write_run_dumps(self.ctx, sys, node_mask,
@@ -728,6 +829,36 @@ def format_dump(node, rec):
     if n < 0:
         raise DsmError(n, "dsm_format_dump")
     return buf.raw[:n].decode()
+
+
+def parse_dump_rc(text, length=None):
+    """dsm_parse_dump of the first `length` bytes of text (str or bytes; default all of it)
+    -> (return code, node, record uint8 [64]): DSM_OK, or E_FORMAT with node -1 and a zero
+    record."""
+    raw = text.encode("latin-1") if isinstance(text, str) else bytes(text)
+    length = len(raw) if length is None else length
+    assert 0 <= length <= len(raw)
+    buf = np.frombuffer(raw, dtype=np.uint8) if raw else np.zeros(1, dtype=np.uint8)
+    rec = np.full(64, 0xEE, dtype=np.uint8)
+    node = ctypes.c_int(-2)
+    rc = lib().dsm_parse_dump(_ptr(buf), length, ctypes.byref(node), _ptr(rec))
+    return rc, node.value, rec
+
+
+def parse_dump(text):
+    """dsm_parse_dump: printProcessorState text (str or bytes) -> (node, record uint8 [64]);
+    raises DsmError(E_FORMAT) for a text dsm_format_dump does not print."""
+    rc, node, rec = parse_dump_rc(text)
+    _check(rc, "dsm_parse_dump")
+    return node, rec
+
+
+def read_dump(node, dump_dir=None):
+    """dsm_read_dump: core_<node>_output.txt of a directory (None: the CWD) -> record uint8 [64]."""
+    rec = np.zeros(64, dtype=np.uint8)
+    _check(lib().dsm_read_dump(node, dump_dir.encode() if dump_dir else None, _ptr(rec)),
+           f"dsm_read_dump({node})")
+    return rec
 
 
 def split_dumps(text, lens):

@@ -12,6 +12,9 @@
  *   dsm_format_dumps_device / dsm_format_run_dumps_device / dsm_write_run_dumps
  *                                             <- printProcessorState, on the GPU, for whole
  *                                                ensembles (byte-identical text)
+ *   dsm_parse_dump / dsm_read_dump / dsm_parse_dumps_device
+ *                                             <- printProcessorState's output files read back
+ *                                                into records (no counterpart in the reference)
  *   dsm_run_* (lock-step ensemble engine)     <- the per-node loop of main (:135-699), the
  *                                                message switch (:177-566), instruction issue
  *                                                (:590-687), handleCacheReplacement
@@ -45,7 +48,9 @@ extern "C" {
                                 over RCCL (dsm_group_*);
                              5 (+census): additive -- the outcome census (dsm_outcome_key,
                                 dsm_census_*) is new symbols only, no struct or call changed;
-                             5 (+audit): additive -- the coherence audit (dsm_audit_*) likewise */
+                             5 (+audit): additive -- the coherence audit (dsm_audit_*) likewise;
+                             5 (+dump reader): additive -- dsm_parse_dump / dsm_read_dump /
+                                dsm_parse_dumps_device and dsm_census_find likewise */
 
 #define DSM_MAX_NP 8             /* bitVector is one byte (README.md:51)                  */
 #define DSM_CACHE_SIZE 4         /* CACHE_SIZE      assignment.c:10                        */
@@ -353,6 +358,20 @@ int dsm_format_run_dumps_device(dsm_ctx *ctx, int view, uint64_t first_sys, uint
  * write core_<n>_output.txt (:831) for every node n in node_mask into `dir` (NULL = CWD). */
 int dsm_write_run_dumps(dsm_ctx *ctx, uint64_t sys, uint32_t node_mask, const char *dir);
 
+/* ---- printProcessorState read back: output files into records ----------------------- *
+ * The inverse of dsm_format_dumps_device, pinned to dsm_parse_dump (boundary helpers below).
+ * The text of record k lies at d_text + k * DSM_DUMP_SLOT (16-byte aligned buffer), d_len[k]
+ * bytes of it; the node it must print is k % np.  Record k goes to d_states[k * state_stride]
+ * (16-byte aligned; 64 bytes, the bytes between records are not touched) and d_status[k] (may
+ * be NULL) is 0 (read), DSM_DUMP_ABSENT (d_len[k] == 0: record zero, flags 0) or DSM_E_FORMAT
+ * (record zero): a length outside {0, DSM_DUMP_BASE .. DSM_DUMP_MAX}, a text dsm_parse_dump
+ * refuses, or a node other than k % np.  Bytes of a slot at and after d_len[k] may be loaded
+ * but never decide anything.  n == 0 is a no-op.  Asynchronous on `stream`. */
+#define DSM_DUMP_ABSENT 1
+int dsm_parse_dumps_device(dsm_ctx *ctx, const char *d_text, const uint32_t *d_len, uint64_t n,
+                           dsm_node_state *d_states, uint32_t state_stride, int32_t *d_status,
+                           void *stream);
+
 /* ---- per-system aggregates (the shardable result of a run) ---------------------------- *
  * A run's per-system results folded into the reference's golden-aggregate view
  * (tests/golden/aggregates.json): sums over systems (mod 2^64), status counts, the max of
@@ -447,6 +466,9 @@ int dsm_census_merge(uint64_t *dst, const uint64_t *src, uint32_t cap);
  * outcomes (may exceed out_cap; min(out_cap, *n) are written; out may be NULL if out_cap is 0). */
 int dsm_census_sorted(const uint64_t *census, uint32_t cap, dsm_outcome *out, uint64_t out_cap,
                       uint64_t *n);
+/* One key looked up along its probe chain (host only): 1 and *out (may be NULL) when the table
+ * holds it, 0 when it does not, DSM_E_INVAL for key 0 or a bad cap. */
+int dsm_census_find(const uint64_t *census, uint32_t cap, uint64_t key, dsm_outcome *out);
 
 /* ---- coherence audit: which invariants the final states of a system break --------------- *
  * The census says which outcomes a run has; the audit says whether an outcome is coherent.  It
@@ -563,6 +585,17 @@ int dsm_load_test_dir(const char *dir_name, int np, uint32_t cap, uint16_t *trac
 int dsm_format_dump(int node, const dsm_node_state *st, char *buf, size_t cap);
 /* writes core_<node>_output.txt (:831) into directory `dir` (NULL = CWD) */
 int dsm_write_dump(int node, const dsm_node_state *st, const char *dir);
+/* The inverse of dsm_format_dump, defined by it: DSM_OK exactly when a node in 0 ..
+ * DSM_MAX_NP-1 and a record with every dir_state <= 2 and every cache_state <= 3 exist such
+ * that dsm_format_dump(node, record) is the len bytes of text; *node and *st are then that node
+ * and that record, its unprinted bytes 60..63 set to pending 0, flags 0x02 (dumped), issued 0.
+ * Anything else (a leading zero, a lower-case hex digit, a sign, 256, "??", one byte short or
+ * long, a NUL inside) is DSM_E_FORMAT with *node = -1 and the record zeroed.  text need not be
+ * NUL-terminated; nothing past len is read. */
+int dsm_parse_dump(const char *text, size_t len, int *node, dsm_node_state *st);
+/* reads core_<node>_output.txt in `dir` (NULL = CWD): DSM_E_IO when it is missing,
+ * DSM_E_FORMAT when it is not canonical or prints another node (the record is zeroed) */
+int dsm_read_dump(int node, const char *dir, dsm_node_state *st);
 /* 64-bit hash of the first nwords (15: dump view, 16: final view) u32 words of a record */
 uint64_t dsm_node_hash(int node, const dsm_node_state *st, int nwords);
 
