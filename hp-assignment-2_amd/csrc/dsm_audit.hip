@@ -284,8 +284,7 @@ extern "C" int dsm_audit_states_device(dsm_ctx *c, const dsm_node_state *d_state
 extern "C" int dsm_audit_run_device(dsm_ctx *c, uint64_t first_sys, uint64_t n_sys, uint32_t *d_words,
                                     dsm_audit *d_audit, void *stream) {
     if (!c) return DSM_E_INVAL;
-    if (!(c->cfg.flags & DSM_F_SNAPSHOTS) || !c->d_recs) return DSM_E_STATE;
-    if (first_sys > c->recs_n || n_sys > c->recs_n - first_sys) return DSM_E_INVAL;
+    if (int rc = dsm_recs_range(c, DSM_F_SNAPSHOTS, first_sys, n_sys)) return rc;
     if (n_sys == 0) return DSM_OK;
     if ((!d_words && !d_audit) || ((uintptr_t)d_words & 3u) || ((uintptr_t)d_audit & 7u)) return DSM_E_INVAL;
     /* [sys][node][dump, final] x 64 B: the final record is the second half of each 128 B */

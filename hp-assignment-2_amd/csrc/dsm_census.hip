@@ -39,6 +39,7 @@
 #include <stdint.h>
 
 #include "dsm_internal.h"
+#include "dsm_device.h"     /* fmix64, the node hash and the result chain */
 
 namespace {
 
@@ -49,13 +50,6 @@ constexpr int WG_TILE = TILES * CENSUS_THREADS;
 constexpr int WG_ITEMS = 4 * WG_TILE;
 
 typedef unsigned long long u64;
-
-__device__ __forceinline__ uint64_t fmix64(uint64_t z) {
-    z ^= z >> 33; z *= 0xff51afd7ed558ccdULL;
-    z ^= z >> 33; z *= 0xc4ceb9fe1a85ec53ULL;
-    z ^= z >> 33;
-    return z;
-}
 
 __device__ __forceinline__ uint64_t bcast64(uint64_t x, int src) {
     const uint32_t lo = __shfl((uint32_t)x, src, 64), hi = __shfl((uint32_t)(x >> 32), src, 64);
@@ -118,13 +112,12 @@ struct ResKeys {
         const uint64_t dh = b.x | ((uint64_t)b.y << 32), fh = b.z | ((uint64_t)b.w << 32);
         uint64_t h = fmix64((uint64_t)(kind + 1) * 0x9E3779B97F4A7C15ULL + 1u);     /* dsm_outcome_key */
         if (kind == DSM_CENSUS_FULL) {
-            h = fmix64(h ^ ((uint64_t)a.x | ((uint64_t)a.y << 32)));
-            h = fmix64(h ^ ((uint64_t)a.z | ((uint64_t)a.w << 32)));
+            h = res_hash_head(h, a);
         } else {
-            h = fmix64(h ^ (uint64_t)a.x);
+            h = res_hash_step(h, (uint64_t)a.x);
         }
-        h = fmix64(h ^ dh);
-        if (kind != DSM_CENSUS_DUMPS) h = fmix64(h ^ fh);
+        h = res_hash_step(h, dh);
+        if (kind != DSM_CENSUS_DUMPS) h = res_hash_step(h, fh);
         key = h ? h : 1u;
         id = first_sys + i;
         tab = 0;
@@ -142,7 +135,7 @@ struct NodeKeys {
         const uint4 *r = recs + i * 8;
         const uint32_t node = (uint32_t)(i % np);
         const uint32_t fl = r[7].w >> 8;              /* final record: dsm_node_state.flags */
-        uint64_t h = 0x9E3779B97F4A7C15ULL * (uint64_t)(node + 1);               /* dsm_node_hash(.., 15) */
+        uint64_t h = node_hash_seed(node);                                       /* dsm_node_hash(.., 15) */
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const uint4 d = r[q];
@@ -150,7 +143,7 @@ struct NodeKeys {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int wi = 4 * q + k;
-                if (wi < 15) h = fmix64(h ^ ((uint64_t)dw[k] | ((uint64_t)wi << 32)));
+                if (wi < 15) h = node_hash_step(h, dw[k], wi);
             }
         }
         key = (fl & 2u) ? (h < 2u ? 2u : h) : (u64)DSM_OUTCOME_MISSING;
@@ -262,8 +255,7 @@ extern "C" int dsm_census_device(dsm_ctx *c, const dsm_sys_result *d_results, ui
 extern "C" int dsm_census_run_nodes_device(dsm_ctx *c, uint64_t first_sys, uint64_t n_sys, uint64_t *d_census,
                                            uint32_t cap, void *stream) {
     if (!c || !cap_ok(cap)) return DSM_E_INVAL;
-    if (!(c->cfg.flags & DSM_F_SNAPSHOTS) || !c->d_recs) return DSM_E_STATE;
-    if (first_sys > c->recs_n || n_sys > c->recs_n - first_sys) return DSM_E_INVAL;
+    if (int rc = dsm_recs_range(c, DSM_F_SNAPSHOTS, first_sys, n_sys)) return rc;
     if (n_sys && (!d_census || ((uintptr_t)d_census & 7u))) return DSM_E_INVAL;
     if (n_sys == 0) return DSM_OK;
     HIPCK(hipSetDevice(c->device));

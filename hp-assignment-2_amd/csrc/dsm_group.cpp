@@ -7,7 +7,7 @@
  * ncclAllReduce of uint64 (mod 2^64 sums) plus one single-slot max.
  *
  * The reference (assignment.c) has no multi-GPU side: its only sharing is sendMessage's
- * per-node queues (:711-739), which here stay inside a wavefront (dsm_engine.hip).
+ * per-node queues (:711-739), which here stay inside a wavefront (dsm_sim.hip).
  */
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>

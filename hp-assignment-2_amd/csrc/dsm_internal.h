@@ -1,8 +1,14 @@
 /*
- * dsm_internal.h -- the engine context shared by the kernel translation units of libdsm.so
- * (dsm_engine.hip: transition engine; dsm_text.hip: trace parser and dump formatter;
- * dsm_census.hip: outcome census).
- * Not part of the ABI.
+ * dsm_internal.h -- the engine context shared by the translation units of libdsm.so, and the
+ * host functions that cross between them:
+ *   dsm_runtime.hip  the C ABI: contexts, settings, run_engine (no kernel of its own)
+ *   dsm_sim.hip      the lock-step transition kernel and its dispatch table
+ *   dsm_ser.hip      the serial resume pass and the kernel that orders its claims
+ *   dsm_kernels.hip  trace scan, digest, argument blocks; aggregate and generator entry points
+ *   dsm_text.hip     trace parser, dump formatter and reader, text generator
+ *   dsm_census.hip   outcome census
+ *   dsm_audit.hip    coherence audit
+ * Each kernel is launched from the unit that defines it.  Not part of the ABI.
  */
 #ifndef DSM_INTERNAL_H
 #define DSM_INTERNAL_H
@@ -11,8 +17,7 @@
 
 #include "dsm.h"
 #include "dsm_plan.h"
-
-struct SimArgs;   /* transition-kernel argument block (dsm_engine.hip) */
+#include "dsm_args.h"       /* SimArgs, CTRL_*, K_* */
 
 #define DSM_TIMING_RING 64
 
@@ -22,10 +27,7 @@ struct dsm_ctx {
     int ring;
     hipStream_t stream;
     int cus;
-    unsigned int *d_ctrl;            /* CTRL_WORDS, zeroed per run (dsm_engine.hip CTRL_*): claim
-                                      * shards of the fast, re-run and resume launches, the
-                                      * overflow and suspended counts, order_kernel's class
-                                      * counts, ffscan_kernel's sample counts               */
+    unsigned int *d_ctrl;            /* CTRL_WORDS, zeroed per run (dsm_args.h CTRL_*)        */
     SimArgs *d_args;                 /* the run's argument blocks (dsm_plan.h ARGS_*), written
                                       * in stream order by args_kernel                      */
     uint32_t *d_ovf_list;
@@ -111,6 +113,38 @@ extern "C" int dsm_debug_order_state(dsm_ctx *c, uint32_t *counts, uint32_t *lis
 
 /* dsm_text.hip: called by dsm_close */
 void dsm_text_release(dsm_ctx *c);
+
+/* dsm_sim.hip: the transition kernel of a launch -- the fast kernel of (ring, mode), nullptr
+ * where the dispatch has none, and the 256-deep re-run kernel; its resident workgroups per CU
+ * (0 on error), its launch, and the fast kernel's LDS bytes per workgroup.  DSM_LOCAL: these
+ * cross between the library's units only and are not exported */
+#define DSM_LOCAL __attribute__((visibility("hidden")))
+typedef void (*sim_fn)(const SimArgs *);
+DSM_LOCAL sim_fn dsm_sim_pick(int np, int ring, bool gen, int mode);
+DSM_LOCAL sim_fn dsm_sim_pick_rerun(int np, bool gen, int mode);
+DSM_LOCAL int dsm_sim_blocks_per_cu(sim_fn f, int threads);
+DSM_LOCAL void dsm_sim_launch(sim_fn f, unsigned grid, unsigned threads, hipStream_t st, const SimArgs *a);
+DSM_LOCAL int dsm_sim_lds_bytes(int ring, int waves);
+/* dsm_ser.hip: order_kernel and ser_kernel<np, cap> */
+DSM_LOCAL void dsm_order_launch(int np, unsigned blocks, hipStream_t st, const SimArgs *a);
+DSM_LOCAL void dsm_ser_launch(int np, bool cap, unsigned blocks, hipStream_t st, const SimArgs *a);
+/* dsm_kernels.hip: args_kernel (a run's argument blocks to device memory, in stream order),
+ * ffscan_kernel and digest_kernel */
+DSM_LOCAL void dsm_args_launch(const SimArgsPack &pk, SimArgs *dst, hipStream_t st);
+DSM_LOCAL void dsm_scan_launch(int np, unsigned blocks, hipStream_t st, const uint16_t *traces,
+                               const uint32_t *counts, uint32_t stride, uint64_t n_sys, uint32_t *scan,
+                               unsigned long long *counters);
+DSM_LOCAL void dsm_digest_launch(int np, unsigned blocks, hipStream_t st, uint64_t n_sys, const uint4 *recs,
+                                 dsm_sys_result *results, unsigned long long *counters);
+
+/* is [first_sys, first_sys + n_sys) inside the node records of the last run?  DSM_E_STATE where
+ * the context holds none, or was opened without the flags in `need` (DSM_F_SNAPSHOTS, or 0);
+ * DSM_E_INVAL where the range is not inside */
+static inline int dsm_recs_range(const dsm_ctx *c, uint32_t need, uint64_t first_sys, uint64_t n_sys) {
+    if ((c->cfg.flags & need) != need || !c->d_recs) return DSM_E_STATE;
+    if (first_sys > c->recs_n || n_sys > c->recs_n - first_sys) return DSM_E_INVAL;
+    return DSM_OK;
+}
 
 template <typename T>
 static inline int dsm_ensure(T **p, size_t *cap, size_t need) {

@@ -1,0 +1,62 @@
+/*
+ * dsm_knobs.h -- every compile-time knob and probe of libdsm.so's kernels, with its default and
+ * the measurement behind it.  Every kernel unit and the runtime include it, so a -D on the
+ * command line reaches all of them; dsm_launch_kernel_names reports the non-default ones
+ * (dsm_runtime.hip build_variant).  Plain preprocessor: dsm_serial.h's host model reads it too.
+ */
+#ifndef DSM_KNOBS_H
+#define DSM_KNOBS_H
+
+/* ---- probe builds (never the default) -------------------------------------------------- */
+#ifndef TRAFFIC_PROBE
+#define TRAFFIC_PROBE 0     /* traffic attribution builds (results invalid): 1 no serial pass, 2 and
+                               no serial-form suspend records (tools/traffic_streams.sh) */
+#endif
+#ifndef REC_PROBE
+#define REC_PROBE 0         /* probe build (hashes invalid): no node records and no digest pass, to
+                               time what the records cost the step */
+#endif
+#ifndef SIM_TAILPROBE
+#define SIM_TAILPROBE 0     /* budget-pass wave end-time histogram (probe build, results exact;
+                               tools/tail_probe.py) */
+#endif
+/* SER_PROBE builds (diagnostics; tools/ser_probe.py): per-wave event counts
+ * of the serial pass in the counter slots the pass leaves unused (msgs_by_type 0-4): iterations,
+ * iterations with a macro-step, with a one-action step, with a chunk miss, hand-overs */
+#ifndef SER_PROBE
+#define SER_PROBE 0
+#endif
+
+/* ---- the transition kernel (dsm_sim.hip) ----------------------------------------------- */
+#ifndef FF_LONG_U
+#define FF_LONG_U 8         /* trace chunks per step of the fast-forward scan past the 8-instruction
+                               window (hot, C4: 1 / 2 / 4 / 6 / 8 -> 49.6 / 39.3 / 34.1 / 32.6 / 32.1 ms) */
+#endif
+
+/* ---- the serial resume pass (dsm_ser.hip, dsm_serial.h) -------------------------------- */
+#ifndef SER_HB
+#define SER_HB 8            /* finished lanes that trigger a batched hand-over (1: at once) */
+#endif
+#ifndef SER_HT
+#define SER_HT 32           /* ... or iterations the oldest finished lane has waited */
+#endif
+/* the run phase (dsm_serial.h ser_solo) in front of each refill period's iterations: taken by a
+ * wave when at least SER_SOLO_MIN of 64 of its running lanes are eligible */
+#ifndef SER_SOLO_MIN
+#define SER_SOLO_MIN 48     /* C3 64 / 56 / 48 / 32: 32.45 / 31.97 / 32.30 / 32.29 ms; C5 21.98 / 21.86 / 21.80 / 21.81 */
+#endif
+#ifndef SER_SOLO_HW
+#define SER_SOLO_HW 4       /* a run's weight in SER_HT's iterations */
+#endif
+/* what ser_macro (a lone node's whole transaction in one step) covers besides hits and misses */
+#ifndef SER_DEAD_FWD
+#define SER_DEAD_FWD 1      /* a system's dead-end forward */
+#endif
+#ifndef SER_NOTICE_HOME
+#define SER_NOTICE_HOME 1   /* ... and an upgrade notice to either home */
+#endif
+#ifndef SER_DUMP
+#define SER_DUMP 0          /* ... and the lone node's dump (exact, but C5 33.4 vs 32.5 ms: off) */
+#endif
+
+#endif

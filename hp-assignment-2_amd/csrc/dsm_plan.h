@@ -1,7 +1,7 @@
 /*
  * dsm_plan.h -- which kernels a run launches, decided once.
  *
- * Shared by the gfx950 kernels and the runtime (dsm_engine.hip) and by the host
+ * Shared by the gfx950 kernels and the runtime (dsm_runtime.hip) and by the host
  * (tests/model/plan_model.cpp): pure integer logic, no HIP in it.
  *
  *   - the MODE bits of sim_kernel and the compile-time traits of an instantiation (sim_traits),

@@ -1,7 +1,7 @@
 /*
  * dsm_serial.h -- the lock-step round taken one node-action at a time: one lane (or one host
  * loop) simulates a whole system.  Used by the resume pass of the two-pass schedule
- * (dsm_engine.hip ser_kernel) and by a host model that checks it against the oracle
+ * (dsm_ser.hip ser_kernel) and by a host model that checks it against the oracle
  * (tests/model/serial_model.cpp).
  *
  * Why: after a few thousand rounds a C3 system is one surviving node issuing its trace while
@@ -50,15 +50,7 @@
 #ifndef DSM_SERIAL_H
 #define DSM_SERIAL_H
 
-#ifndef SER_NOTICE_HOME
-#define SER_NOTICE_HOME 1   /* ... and an upgrade notice to either home */
-#endif
-#ifndef SER_DUMP
-#define SER_DUMP 0          /* ... and the lone node's dump (exact, but C5 33.4 vs 32.5 ms: off) */
-#endif
-#ifndef SER_DEAD_FWD
-#define SER_DEAD_FWD 1      /* ser_macro also applies a system's dead-end forward */
-#endif
+#include "dsm_knobs.h"      /* SER_DEAD_FWD, SER_NOTICE_HOME, SER_DUMP: what ser_macro covers */
 
 /* Counting hooks of the host model (tests/model/serial_model.cpp defines them before this
  * header: ser_step's actions by type, ser_macro's cases and decline reasons).  Empty here, so in

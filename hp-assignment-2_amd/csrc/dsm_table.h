@@ -1,7 +1,7 @@
 /*
  * dsm_table.h -- table-driven transition of one node for one lock-step round.
  *
- * Shared by the gfx950 kernel (dsm_engine.hip) and the host (the table builder, and a CPU
+ * Shared by the gfx950 kernel (dsm_sim.hip) and the host (the table builder, and a CPU
  * model used by the tests).  The 13 message handlers of assignment.c (:177-566) and the
  * instruction issue (:590-687) are compiled into a 640-entry micro-op table:
  *
@@ -336,8 +336,10 @@ struct DtOut {
     bool asrt;
     uint32_t cset, cclr;               /* the same as a control-word update               */
 };
-/* node control word bits touched by cset / cclr (dsm_engine.hip's C_WAIT, C_ASSERT) */
+/* node control word bits touched by cset / cclr (the kernels' C_WAIT, C_ASSERT) */
 enum : uint32_t { DT_CTL_WAIT = 1u << 8, DT_CTL_ASSERT = 1u << 11 };
+/* ctl word: bits 0-7 pendingWriteValue, then flags */
+constexpr uint32_t C_WAIT = DT_CTL_WAIT, C_DUMPED = 1u << 9, C_OVF = 1u << 10, C_ASSERT = DT_CTL_ASSERT;
 static_assert((W1_WSET >> 12) == DT_CTL_WAIT && (W1_ASSERT >> 12) == DT_CTL_ASSERT &&
               (W1_WCLR >> 13) == DT_CTL_WAIT, "W1 control bits");
 

@@ -39,13 +39,10 @@
 #include "dsm.h"
 #include "dsm_gen.h"
 #include "dsm_internal.h"
+#include "dsm_device.h"     /* DEVI, v4u32 */
 #include "dsm_parse.h"
 
-#define DEVI __device__ __forceinline__
-
 namespace {
-
-typedef uint32_t v4u32 __attribute__((ext_vector_type(4)));
 
 /* ---- printProcessorState layout (byte offsets in the base 1954-byte text) ------------- */
 constexpr uint32_t SLOT = DSM_DUMP_SLOT, SLOT16 = DSM_DUMP_SLOT / 16;
@@ -914,8 +911,7 @@ extern "C" int dsm_format_run_dumps_device(dsm_ctx *c, int view, uint64_t first_
                                            uint64_t n_sys, char *d_text, uint32_t *d_len,
                                            void *stream) {
     if (!c || (view != DSM_VIEW_DUMP && view != DSM_VIEW_FINAL)) return DSM_E_INVAL;
-    if (!c->d_recs) return DSM_E_STATE;
-    if (first_sys > c->recs_n || n_sys > c->recs_n - first_sys) return DSM_E_INVAL;
+    if (int rc = dsm_recs_range(c, 0, first_sys, n_sys)) return rc;
     if (n_sys && (!d_text || !d_len || ((uintptr_t)d_text & 15u))) return DSM_E_INVAL;
     HIPCK(hipSetDevice(c->device));
     const uint8_t *recs = (const uint8_t *)c->d_recs + first_sys * (uint64_t)c->cfg.np * 128 + view * 64;
@@ -948,8 +944,7 @@ extern "C" int dsm_parse_dumps_device(dsm_ctx *c, const char *d_text, const uint
 
 extern "C" int dsm_write_run_dumps(dsm_ctx *c, uint64_t sys, uint32_t node_mask, const char *dir) {
     if (!c) return DSM_E_INVAL;
-    if (!(c->cfg.flags & DSM_F_SNAPSHOTS) || !c->d_recs) return DSM_E_STATE;
-    if (sys >= c->recs_n) return DSM_E_INVAL;
+    if (int rc = dsm_recs_range(c, DSM_F_SNAPSHOTS, sys, 1)) return rc;
     const int np = c->cfg.np;
     HIPCK(hipSetDevice(c->device));
     if (!c->d_text_tmp) HIPCK(hipMalloc((void **)&c->d_text_tmp, (size_t)DSM_MAX_NP * SLOT));

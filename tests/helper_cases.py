@@ -1,6 +1,6 @@
 """Cases and plain references for the helper kernels around the engine: the text generator
 (textlen_kernel / scan_kernel / textgen_kernel, dsm_text.hip), gen_kernel, ffscan_kernel and
-agg_kernel (dsm_engine.hip).  Shared by tests/test_helpers_model.py (the CPU certificate of the
+agg_kernel (dsm_kernels.hip).  Shared by tests/test_helpers_model.py (the CPU certificate of the
 references and of what the case lists cover) and tests/test_gpu_helpers.py (the kernels)."""
 from collections import namedtuple
 
@@ -18,15 +18,15 @@ TEXT_WRITE_FILES_PER_CU = 16 * 4    # dsm_text.hip dsm_generate_text_device: `wb
                                     # textgen_kernel: one file per wave, 4 waves per workgroup
 TEXT_LEN_FILES_PER_CU = 8 * 256     # dsm_text.hip dsm_generate_text_device: `blocks > cus * 8`,
                                     # textlen_kernel: one file per thread, 256 threads
-GEN_SLOTS_PER_CU = 512              # dsm_engine.hip dsm_generate_device: `cap = cus * 512`,
+GEN_SLOTS_PER_CU = 512              # dsm_kernels.hip dsm_generate_device: `cap = cus * 512`,
                                     # gen_kernel: one (system, node) slot per workgroup iteration
-AGG_SYSTEMS_PER_CU = 8 * 256        # dsm_engine.hip dsm_aggregate_device: `cap = cus * 8`,
+AGG_SYSTEMS_PER_CU = 8 * 256        # dsm_kernels.hip dsm_aggregate_device: `cap = cus * 8`,
                                     # agg_kernel: one system per thread, 256 threads
 SCAN_BLOCK = 1024                   # dsm_text.hip scan_kernel: one workgroup of 1024 threads,
                                     # ceil(n_files / 1024) offsets per thread
 SCAN_SYS = 4096                     # dsm_plan.h SCAN_SYS: systems ffscan_kernel samples
-SCAN_INSTR = 256                    # dsm_engine.hip SCAN_INSTR: instructions per sampled trace
-SCAN_RUN = 8                        # dsm_engine.hip ffscan_kernel: `run >= 8u`
+SCAN_INSTR = 256                    # dsm_kernels.hip SCAN_INSTR: instructions per sampled trace
+SCAN_RUN = 8                        # dsm_kernels.hip ffscan_kernel: `run >= 8u`
 
 
 def beyond(cap_per_cu, cus, np_=1):
@@ -135,7 +135,7 @@ def gen_large_case(cus):
 
 # ---- ffscan_kernel --------------------------------------------------------------------------
 def ref_scan(tr, cn, stride, n_sys, np_):
-    """ffscan_kernel's definition (dsm_plan.h "fast-forward verdict", dsm_engine.hip): of
+    """ffscan_kernel's definition (dsm_plan.h "fast-forward verdict", dsm_kernels.hip): of
     S = min(n_sys, 4096) systems j * n_sys // S, every node's first min(count, stride, 256)
     instructions go through a private table of four entries, indexed by address & 3, that
     holds the last address seen there (nothing at the start); `run` counts consecutive hits,

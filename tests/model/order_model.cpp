@@ -6,7 +6,7 @@
  * Every system is driven in lock-step through the oracle's one-action hook
  * (orc_step), as the budget pass runs it.  At the first round >= 160 that is a multiple of 8
  * and leaves the system quiet-lone (every inbox empty, exactly one node neither waiting nor
- * dumped, with instructions left: dsm_engine.hip lone_mask) the node records are packed into
+ * dumped, with instructions left: dsm_sim.hip lone_mask) the node records are packed into
  * the serial column and the header's classifier is compared with the same predicate computed
  * straight from the records: some home h, block b in EM whose owner o (the lowest bit) is not
  * the lone node and whose line b & 3 at o does not hold h << 4 | b in M or E.  They must agree

@@ -376,7 +376,7 @@ std::string ser_name(int np, bool cap) {
     return b;
 }
 
-/* the instantiation a launch of a plan is, as the dispatch picks it (dsm_engine.hip pick_fast,
+/* the instantiation a launch of a plan is, as the dispatch picks it (dsm_sim.hip pick_fast,
  * pick_fallback and run_engine's switch) */
 std::string launch_name(const Plan &p, const PlanLaunch &L) {
     const int np = p.in.np;

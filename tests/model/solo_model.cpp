@@ -1,6 +1,6 @@
 /*
  * tests/model/solo_model.cpp -- TEST INFRASTRUCTURE: the serial resume pass's loop with its run
- * phase (hp-assignment-2_amd/csrc/dsm_serial.h ser_solo, dsm_engine.hip ser_kernel) on the host,
+ * phase (hp-assignment-2_amd/csrc/dsm_serial.h ser_solo, dsm_ser.hip ser_kernel) on the host,
  * one lane, whole systems from their first round against the oracle (oracle/dsm_oracle.c):
  * status, rounds, messages, instructions, and every node's final and dump record.
  *

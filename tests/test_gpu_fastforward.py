@@ -1,4 +1,4 @@
-"""GPU: the hit-run fast-forward of the transition kernel (dsm_engine.hip step (4b)).
+"""GPU: the hit-run fast-forward of the transition kernel (dsm_sim.hip step (4b)).
 
 After a round in which a system sent nothing, every further round until some node issues a
 sending instruction is one local hit per non-waiting node (assignment.c:607-611 RD hit,
@@ -185,7 +185,7 @@ def test_one_pass_pair_reports_the_kernel_that_ran(dsm, orc, dist, picked):
 
 @pytest.mark.parametrize("ffb", [7, 100, 384, 1000])
 def test_long_runs_end_at_ragged_trace_ends_and_budgets(dsm, orc, monkeypatch, ffb):
-    """The fast-forward long run (dsm_engine.hip, the run past the 8-instruction window,
+    """The fast-forward long run (dsm_sim.hip, the run past the 8-instruction window,
     FF_LONG_U = 8 chunks per scan step) must stop exactly at the group's first miss, at a trace end that is not a chunk boundary
     (ragged counts) and at the budget (FF_ON: the fast-forward kernel runs the budget pass,
     thr_ff = DSM_FF_BUDGET_ROUNDS rounds, so runs are cut mid-scan): against the oracle."""

@@ -228,7 +228,7 @@ def test_observers_back_to_back_on_one_engine(dsm, orc, ensembles, observed, mon
 def test_type_counts_one_home_storm(dsm, orc, monkeypatch, name, ring):
     """One system of 8 nodes x 4,096 instructions, all on home 0: the most messages of one type
     one node handles (16,398 READ_REQUEST in the read storm), counted in 16-bit fields per lane
-    (dsm_engine.hip, tc[7]).  All 13 counts equal the oracle's."""
+    (dsm_sim.hip, tc[7]).  All 13 counts equal the oracle's."""
     tr_, cn = adv.storm(name)
     ores, odump, ofin, _, _, obt = orc.run_packed_ex_types(8, tr_, cn)
     route = dict(env={"DSM_SERIAL": "1"}, engine=dict(ring_cap=ring, type_counts=True))

@@ -1,4 +1,4 @@
-"""GPU: the claim order of the serial resume pass (dsm_engine.hip order_kernel, between the
+"""GPU: the claim order of the serial resume pass (dsm_ser.hip order_kernel, between the
 budget pass and ser_kernel; the classifier is dsm_serial.h ser_long_class).
 
 The ordering kernel splits the budget pass's list of suspended systems in a long class

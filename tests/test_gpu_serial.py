@@ -1,4 +1,4 @@
-"""GPU: the resume pass in serial form (dsm_engine.hip ser_kernel, csrc/dsm_serial.h).
+"""GPU: the resume pass in serial form (dsm_ser.hip ser_kernel, csrc/dsm_serial.h).
 
 The budget pass (lock-step, 8 lanes per system) suspends every system still running after
 2^budget rounds; ser_kernel continues each on ONE lane, one node-action per iteration, with

@@ -1,4 +1,4 @@
-"""GPU: the serial resume pass's run phase (dsm_engine.hip ser_kernel's gate and
+"""GPU: the serial resume pass's run phase (dsm_ser.hip ser_kernel's gate and
 dsm_serial.h ser_solo: up to 8 simple transactions of a quiet-lone node per call).
 
 Every comparison is per system against the oracle on the same inputs: crafted ensembles whose

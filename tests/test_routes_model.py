@@ -449,7 +449,7 @@ def test_observer_limits_bite(observer_oracle, np_):
 
 def test_storm_counts():
     """(i): the largest count of one message type at one node, for the 16-bit fields of the
-    kernel's per-lane type counters (dsm_engine.hip, tc[7]).  The counts are the oracle's and, from
+    kernel's per-lane type counters (dsm_sim.hip, tc[7]).  The counts are the oracle's and, from
     tests/golden/adversarial, those of the reference's own handler text."""
     stored = pins.index()["storms"]
     top = {}

@@ -2,7 +2,7 @@
 """tools/ser_probe.py <dist> [systems] -- the serial pass's diagnostic counters of a SER_PROBE
 build (DSM_LIB=ab/libdsm_serprobe*.so; results of such a build are exact, its timing is not):
 per-wave event counts and s_memtime cycle sums the probe build leaves in the counter slots
-msgs_by_type 0-16 (dsm_engine.hip ser_kernel, SER_PROBE)."""
+msgs_by_type 0-16 (dsm_ser.hip ser_kernel, SER_PROBE)."""
 import json
 import os
 import sys
