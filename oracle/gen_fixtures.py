@@ -53,8 +53,9 @@ outputs.  Nothing written here is reference source text.
                                                system's index) of the adversarial inputs --
                                                the contention ensemble, the tiled scenarios,
                                                the crafted lone-node inputs, the generated
-                                               ensemble (tests/adversarial.py,
-                                               tests/solo_inputs.py; the table of variants is
+                                               ensemble, the crafted hit runs at stride 2048
+                                               (tests/adversarial.py, tests/solo_inputs.py,
+                                               tests/hitrun_cases.py; the table of variants is
                                                tests/reference_pins.py's) -- under the
                                                lock-step schedule, seeded stalls, inbox and
                                                round limits, from oracle/_ref/
@@ -404,9 +405,9 @@ def dumps():
 
 
 def adversarial():
-    """tests/golden/adversarial: the adversarial inputs of tests/adversarial.py and
-    tests/solo_inputs.py through the reference's own handler text (ref_lockstep `packed`); the
-    table of variants and the digests are tests/reference_pins.py's."""
+    """tests/golden/adversarial: the adversarial inputs of tests/adversarial.py,
+    tests/solo_inputs.py and tests/hitrun_cases.py (hitruns_np{4,8}_lockstep) through the
+    reference's own handler text (ref_lockstep `packed`); the table of variants and the digests are tests/reference_pins.py's."""
     for p in (os.path.join(REPO, "tests"), HERE):
         if p not in sys.path:
             sys.path.insert(0, p)

@@ -4,7 +4,7 @@ tests/golden/adversarial.
 
 oracle/gen_fixtures.py `adversarial` runs every variant through oracle/_ref/ref_lockstep_np{4,8}
 `packed` (the reference's handler and issue text under the lock-step schedule, seeded stalls, an
-inbox limit and a round limit) and stores, per variant, one .npy of per-system result digests
+inbox limit and a round limit; the crafted hit runs of tests/hitrun_cases.py among them) and stores, per variant, one .npy of per-system result digests
 (dsm_common.h dsm_result_digest, idx = the system's index), where the issue order is compared a
 second .npy of per-system issue digests (the first 8 bytes of the md5 of the system's DEBUG_INSTR
 lines), and an index.json entry with the input's sha256, status counts, sums and the 13 per-type
@@ -20,6 +20,7 @@ import subprocess
 import numpy as np
 
 import adversarial as adv
+import hitrun_cases
 import solo_inputs
 
 DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "adversarial")
@@ -46,7 +47,8 @@ def _variant(kind, np_, stalls=False, cap=256, limit=0, issue=False):
 def variants():
     """Every stored variant: on the contention ensemble exactly the (schedule, inbox limit, round
     limit) combinations adversarial.ROUTES and OBSERVER_ROUTES compare with; the tiled scenarios,
-    the crafted lone-node inputs and the generated ensemble beside them."""
+    the crafted lone-node inputs, the generated ensemble and the crafted hit runs
+    (tests/hitrun_cases.py, stride 2048) beside them."""
     lock, stall = (1 << adv.OBS_ROUND_LOG2[k] for k in ("lockstep", "stalls"))
     out = []
     for np_ in NPS:
@@ -60,7 +62,8 @@ def variants():
                 _variant("tiled", np_, stalls=True, issue=True),
                 _variant("crafted", np_),
                 _variant("generated", np_),
-                _variant("generated", np_, stalls=True)]
+                _variant("generated", np_, stalls=True),
+                _variant("hitruns", np_)]
     return out
 
 
@@ -93,6 +96,8 @@ def inputs(kind, np_, orc=None):
             tr, cn, _, _ = adv.tiled_scenarios(np_)
         elif kind == "crafted":
             tr, cn, _ = solo_inputs.crafted(np_, CRAFTED["seed"], CRAFTED["n"], CRAFTED["stride"])
+        elif kind == "hitruns":
+            tr, cn, _ = hitrun_cases.hitruns(np_, hitrun_cases.STRIDE)
         elif kind == "generated":
             g = adv.GEN_ENSEMBLE
             t, cn = orc.generate(np_, g["dist"], g["seed"], g["n_instr"], g["first"], g["n"])

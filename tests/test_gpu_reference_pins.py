@@ -2,7 +2,7 @@
 
 tests/golden/adversarial (oracle/gen_fixtures.py adversarial; tests/reference_pins.py) holds what
 the reference's handler and issue text gave on the contention ensemble, the tiled scenarios, the
-crafted lone-node inputs, the generated ensemble and the one-home storms, under the lock-step
+crafted lone-node inputs, the generated ensemble, the crafted hit runs and the one-home storms, under the lock-step
 schedule, seeded stalls, an inbox limit and a round limit.  Every stored variant runs once on a
 default Engine with the variant's setters, type counts and, where stored, the issue trace; the
 per-system result digests, the counters' sums, maximum and status counts, the 13 per-type totals

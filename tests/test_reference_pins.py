@@ -3,7 +3,8 @@
 Every GPU parity test compares the kernels with oracle/dsm_oracle.c; this module is the other
 link, oracle against reference, on the inputs the generator does not reach: the contention
 ensemble, the tiled scenarios, the one-home storms, the crafted lone-node inputs and the generated
-ensemble (tests/adversarial.py, tests/solo_inputs.py), under the lock-step schedule, seeded stalls,
+ensemble (tests/adversarial.py, tests/solo_inputs.py) and the crafted hit runs
+(tests/hitrun_cases.py), under the lock-step schedule, seeded stalls,
 inbox limits and round limits.  tests/golden/adversarial holds what the reference's handler and
 issue text gave (oracle/_ref/ref_lockstep_np{4,8} packed; oracle/gen_fixtures.py adversarial; the
 table of variants is tests/reference_pins.py's).
@@ -13,6 +14,7 @@ table of variants is tests/reference_pins.py's).
   - a live differential where oracle/_ref is built (by the current recipe: reference_pins.ref_packed
     tells a runner without `packed` and the tests skip): 20,000 random ragged systems per case, crossed
     over stall thresholds, inbox limits and round limits: results, records and type counts;
+    and the crafted hit runs of tests/hitrun_cases.py, both strides, clean and poisoned tails;
   - one generated fixture with system ids beyond 2^40.
 Inputs with a home >= np stay with the oracle alone: the reference indexes out of bounds there
 (ref_lockstep packed refuses them)."""
@@ -21,6 +23,7 @@ import numpy as np
 import pytest
 
 import adversarial as adv
+import hitrun_cases
 import pydsm
 import pyoracle as orc
 import reference_pins as pins
@@ -219,3 +222,25 @@ def test_live_differential(ragged_inputs, tmp_path, np_, family, thresh, cap, li
     print(np_, family, hex(thresh), cap, limit, "status", st.tolist())
     # the case's limits end systems
     assert (cap != 2 or st[2] > 0) and (not limit or st[4] > 0)
+
+
+@pytest.mark.parametrize("stride", [hitrun_cases.STRIDE, hitrun_cases.SMALL_STRIDE])
+@pytest.mark.parametrize("poisoned", [False, True], ids=["clean", "poisoned"])
+@pytest.mark.parametrize("np_", pins.NPS)
+def test_live_differential_hit_runs(tmp_path, np_, poisoned, stride):
+    """The crafted hit runs (tests/hitrun_cases.py), both strides, clean and poisoned tails:
+    results, records and type counts of the reference's handler text against the oracle's."""
+    exe, why = pins.ref_packed(np_)
+    if exe is None:
+        pytest.skip(why)
+    tr, cn, _ = hitrun_cases.hitruns(np_, stride)
+    if poisoned:
+        tr = hitrun_cases.poison(tr, cn)
+    rres, rdump, rfin, rtypes = pins.run_ref_packed(exe, np_, tr, cn, tmp_path)
+    res, dump, fin, _, _, bt = orc.run_packed_ex_types(np_, tr, cn, nthreads=16)
+    bad = np.nonzero(res.view(np.uint8).reshape(len(res), -1) != rres.view(np.uint8).reshape(len(res), -1))[0]
+    assert bad.size == 0, f"first differing system {bad[0]}: oracle {res[bad[0]]} reference {rres[bad[0]]}"
+    mask = ((res["status"] >> 8)[:, None] >> np.arange(np_)[None, :]) & 1
+    assert np.array_equal(dump * mask[:, :, None].astype(np.uint8), rdump)
+    assert np.array_equal(fin, rfin)
+    assert np.array_equal(bt.astype(np.uint64), rtypes)
