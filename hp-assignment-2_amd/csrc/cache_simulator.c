@@ -54,6 +54,15 @@
  *                        audit class <NAME>: C schedules, first F
  *                    over all N variants, one class line per class that occurred.  Exit codes do
  *                    not change.
+ *   --events FILE    write the run's event trace to FILE as text: every line the reference's
+ *                    -DDEBUG_INSTR and -DDEBUG_MSG builds would print for this system under the
+ *                    schedule, in their order (dsm_trace_events_device: a replay of the system on
+ *                    the GPU; dsm_format_event_trace).  With --explore it needs --explore-dir D, and
+ *                    FILE (a plain name, e.g. events.txt) is written into every D/outcome_<k>/ for
+ *                    the outcome's first variant: one replay launch over the K first variants, on
+ *                    the device traces of the exploration.  Exit codes and the other output do not
+ *                    change.
+ *   --events-kind instr|msg|all   which build's lines (default all: both, interleaved)
  *   --check DIR      only with --explore: can the system produce the output files in DIR, and
  *                    how often?  DIR/core_<n>_output.txt is read back into a record
  *                    (dsm_read_dump; a core without a file is one that wrote none) and looked up
@@ -82,7 +91,8 @@
 static void usage(const char *argv0) {
     fprintf(stderr, "Usage: %s [--np 4|8] [--max-instr N] [--device D] [--quiet] [--issue-order FILE]\n"
                     "          [--schedule SEED:THRESH] [--explore N [--explore-dir DIR]\n"
-                    "          [--explore-kind dumps|final|full] [--check DIR]] [--audit] <test_directory>\n", argv0);
+                    "          [--explore-kind dumps|final|full] [--check DIR]] [--audit]\n"
+                    "          [--events FILE [--events-kind instr|msg|all]] <test_directory>\n", argv0);
 }
 
 static const char *const status_names[5] = {"COMPLETED", "DEADLOCKED", "RING_OVERFLOW", "ASSERT_FAILED",
@@ -97,11 +107,64 @@ static void print_audit_word(const char *prefix, uint32_t w) {
     printf(" lines %u first 0x%02x bad %u\n", (w >> 8) & 0xFFu, (w >> 16) & 0xFFu, w >> 24);
 }
 
+/* --events: systems ids[0 .. k) of the device ensemble replayed with a log under the ctx's
+ * schedule; the text of system j goes to file (k == 1, dir NULL) or to dir/outcome_<j>/file.  A
+ * first launch without event storage sizes the buffer, the second stores the events.  Returns
+ * DSM_OK or an error code (*what names the step). */
+static int write_event_logs(dsm_ctx *ctx, const uint16_t *d_tr, const uint32_t *d_cn, uint64_t n_sys,
+                            const uint64_t *ids, uint32_t k, int kind, const char *dir, const char *file,
+                            const char **what) {
+    uint64_t *d_ids = NULL, *d_ev = NULL, *ev = NULL;
+    uint32_t *d_n = NULL, *cnt = (uint32_t *)malloc((size_t)k * sizeof(uint32_t)), cap = 1;
+    char *txt = NULL;
+    int rc = DSM_E_NOMEM;
+    *what = "events: memory";
+    if (!cnt || hipMalloc((void **)&d_ids, (size_t)k * sizeof(uint64_t)) != hipSuccess ||
+        hipMalloc((void **)&d_n, (size_t)k * sizeof(uint32_t)) != hipSuccess ||
+        hipMemcpy(d_ids, ids, (size_t)k * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess)
+        goto done;
+    *what = "dsm_trace_events_device";
+    if ((rc = dsm_trace_events_device(ctx, d_tr, d_cn, n_sys, d_ids, k, NULL, 0, d_n, NULL, NULL, NULL))) goto done;
+    rc = DSM_E_DEVICE;
+    if (hipMemcpy(cnt, d_n, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) goto done;
+    for (uint32_t j = 0; j < k; ++j) if (cnt[j] > cap) cap = cnt[j];
+    *what = "events: memory";
+    rc = DSM_E_NOMEM;
+    ev = (uint64_t *)malloc((size_t)k * cap * sizeof(uint64_t));
+    txt = (char *)malloc((size_t)cap * 160 + 1);          /* the longest line has 67 characters; :648 doubles one */
+    if (!ev || !txt || hipMalloc((void **)&d_ev, (size_t)k * cap * sizeof(uint64_t)) != hipSuccess) goto done;
+    *what = "dsm_trace_events_device";
+    if ((rc = dsm_trace_events_device(ctx, d_tr, d_cn, n_sys, d_ids, k, d_ev, cap, NULL, NULL, NULL, NULL))) goto done;
+    rc = DSM_E_DEVICE;
+    if (hipMemcpy(ev, d_ev, (size_t)k * cap * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) goto done;
+    for (uint32_t j = 0; j < k; ++j) {
+        char path[600];
+        *what = "dsm_format_event_trace";
+        const int len = dsm_format_event_trace(ev + (size_t)j * cap, cnt[j], kind, txt, (size_t)cap * 160 + 1);
+        if (len < 0) { rc = len; goto done; }
+        *what = "events: write";
+        rc = DSM_E_IO;
+        if (dir ? snprintf(path, sizeof path, "%s/outcome_%u/%s", dir, j, file) >= (int)sizeof path
+                : snprintf(path, sizeof path, "%s", file) >= (int)sizeof path) goto done;
+        FILE *f = fopen(path, "w");
+        if (!f) goto done;
+        const int ok = fwrite(txt, 1, (size_t)len, f) == (size_t)len;
+        if (fclose(f) != 0 || !ok) goto done;
+    }
+    rc = DSM_OK;
+done:
+    if (d_ids) (void)hipFree(d_ids);
+    if (d_n) (void)hipFree(d_n);
+    if (d_ev) (void)hipFree(d_ev);
+    free(cnt); free(ev); free(txt);
+    return rc;
+}
+
 /* --explore: n copies of the parsed system under schedule (seed, thresh), one run with
  * snapshots, both censuses on the device.  Returns the process exit code. */
 static int explore(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces, const uint32_t *counts,
                    uint32_t n, unsigned long long seed, unsigned thresh, int kind, const char *out_dir, int audit,
-                   const char *check_dir) {
+                   const char *check_dir, const char *events_file, int events_kind) {
     uint32_t cap = DSM_CENSUS_MIN_CAP;
     while (cap < n) cap <<= 1;
     const size_t words = DSM_CENSUS_WORDS(cap), slot = (size_t)np * stride;
@@ -112,6 +175,7 @@ static int explore(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces
     uint32_t *h_cn = (uint32_t *)malloc(cn_bytes), *d_cn = NULL;
     uint64_t *cen = (uint64_t *)malloc(cen_bytes), *d_cen = NULL;
     dsm_outcome *outc = (dsm_outcome *)malloc((size_t)cap * sizeof(dsm_outcome));
+    uint64_t *firsts = NULL;                        /* --events: every outcome's first variant */
     dsm_sys_result *d_res = NULL;
     dsm_counters *d_cnt = NULL;
     uint32_t *d_words = NULL;
@@ -176,8 +240,13 @@ static int explore(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces
     printf("explored %u schedules (seed %llu, threshold %u): %llu outcomes\n", n, seed, thresh,
            (unsigned long long)k);
     if (out_dir && mkdir(out_dir, 0777) != 0 && errno != EEXIST) { what = out_dir; rc = DSM_E_IO; goto fail; }
+    if (events_file && !(firsts = (uint64_t *)malloc((size_t)(k ? k : 1) * sizeof(uint64_t)))) {
+        what = "out of memory";
+        goto fail;
+    }
     for (uint64_t o = 0; o < k; ++o) {
         dsm_sys_result r;
+        if (firsts) firsts[o] = outc[o].first_sys;
         what = "result read-back";
         if (hipMemcpy(&r, d_res + outc[o].first_sys, sizeof r, hipMemcpyDeviceToHost) != hipSuccess) goto fail;
         const uint32_t st = r.status & 0xFFu, dumped = r.status >> 8;
@@ -200,6 +269,9 @@ static int explore(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces
             if ((rc = dsm_write_run_dumps(ctx, outc[o].first_sys, dumped, path))) goto fail;
         }
     }
+    if (events_file && k &&
+        (rc = write_event_logs(ctx, d_tr, d_cn, n, firsts, (uint32_t)k, events_kind, out_dir, events_file, &what)))
+        goto fail;
     for (int c = 0; c < np; ++c) {
         const uint64_t *t = cen + (size_t)(1 + c) * words;
         uint64_t kc = 0, missing = 0;
@@ -289,7 +361,7 @@ fail:
     if (d_cen) (void)hipFree(d_cen);
     if (d_words) (void)hipFree(d_words);
     if (d_aud) (void)hipFree(d_aud);
-    free(h_tr); free(h_cn); free(cen); free(outc);
+    free(h_tr); free(h_cn); free(cen); free(outc); free(firsts);
     return code;
 }
 
@@ -301,7 +373,8 @@ int main(int argc, char **argv) {
     unsigned sched_thresh = DSM_SCHED_LOCKSTEP;
     int have_sched = 0, explore_kind = DSM_CENSUS_DUMPS, explore_opts = 0;
     long long explore_n = 0;
-    const char *explore_dir = NULL, *check_dir = NULL;
+    const char *explore_dir = NULL, *check_dir = NULL, *events_file = NULL;
+    int events_kind = DSM_EV_FMT_INSTR | DSM_EV_FMT_MSG, events_opts = 0;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--np") && i + 1 < argc) np = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--max-instr") && i + 1 < argc) max_instr = (uint32_t)atoi(argv[++i]);
@@ -319,6 +392,15 @@ int main(int argc, char **argv) {
         }
         else if (!strcmp(argv[i], "--explore-dir") && i + 1 < argc) { explore_dir = argv[++i]; explore_opts = 1; }
         else if (!strcmp(argv[i], "--check") && i + 1 < argc) { check_dir = argv[++i]; explore_opts = 1; }
+        else if (!strcmp(argv[i], "--events") && i + 1 < argc) events_file = argv[++i];
+        else if (!strcmp(argv[i], "--events-kind") && i + 1 < argc) {
+            const char *v = argv[++i];
+            events_opts = 1;
+            if (!strcmp(v, "instr")) events_kind = DSM_EV_FMT_INSTR;
+            else if (!strcmp(v, "msg")) events_kind = DSM_EV_FMT_MSG;
+            else if (!strcmp(v, "all")) events_kind = DSM_EV_FMT_INSTR | DSM_EV_FMT_MSG;
+            else { usage(argv[0]); return EXIT_FAILURE; }
+        }
         else if (!strcmp(argv[i], "--explore-kind") && i + 1 < argc) {
             const char *v = argv[++i];
             explore_opts = 1;
@@ -336,6 +418,8 @@ int main(int argc, char **argv) {
         return EXIT_FAILURE;
     }
     if ((explore_n && issue_file) || (!explore_n && explore_opts)) { usage(argv[0]); return EXIT_FAILURE; }
+    if ((events_opts && !events_file) || (events_file && !*events_file) ||
+        (explore_n && events_file && (!explore_dir || strchr(events_file, '/')))) { usage(argv[0]); return EXIT_FAILURE; }
     if (explore_n && !have_sched) { sched_seed = 0; sched_thresh = 0x8000u; }
     const uint32_t stride = (max_instr + 7u) & ~7u;
     /* initializeProcessor (:776-822): the core files are read from disk here and scanned on
@@ -398,7 +482,7 @@ int main(int argc, char **argv) {
 
     if (explore_n) {
         const int code = explore(ctx, np, stride, traces, counts, (uint32_t)explore_n, sched_seed, sched_thresh,
-                                 explore_kind, explore_dir, audit, check_dir);
+                                 explore_kind, explore_dir, audit, check_dir, events_file, events_kind);
         dsm_close(ctx);
         free(traces);
         return code;
@@ -430,6 +514,27 @@ int main(int argc, char **argv) {
         fclose(f);
         free(ev);
         free(txt);
+    }
+    if (events_file) {                                  /* the DEBUG_INSTR / DEBUG_MSG log: a replay */
+        uint16_t *d_tr = NULL;
+        uint32_t *d_cn = NULL;
+        const uint64_t id0 = 0;
+        const char *what = "events: memory";
+        const size_t tr_bytes = (size_t)np * stride * sizeof(uint16_t);
+        rc = DSM_E_NOMEM;
+        if (hipMalloc((void **)&d_tr, tr_bytes) == hipSuccess && hipMalloc((void **)&d_cn, sizeof counts) == hipSuccess) {
+            rc = DSM_E_DEVICE;
+            if (hipMemcpy(d_tr, traces, tr_bytes, hipMemcpyHostToDevice) == hipSuccess &&
+                hipMemcpy(d_cn, counts, (size_t)np * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess)
+                rc = write_event_logs(ctx, d_tr, d_cn, 1, &id0, 1, events_kind, NULL, events_file, &what);
+        }
+        if (d_tr) (void)hipFree(d_tr);
+        if (d_cn) (void)hipFree(d_cn);
+        if (rc) {
+            fprintf(stderr, "Error: %s: %s\n", what, dsm_strerror(rc));
+            dsm_close(ctx);
+            return EXIT_FAILURE;
+        }
     }
     /* printProcessorState of every node that finished issuing (:695), formatted on the GPU */
     if ((rc = dsm_write_run_dumps(ctx, 0, dumped, NULL))) {

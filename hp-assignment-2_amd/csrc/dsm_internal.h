@@ -8,6 +8,7 @@
  *   dsm_text.hip     trace parser, dump formatter and reader, text generator
  *   dsm_census.hip   outcome census
  *   dsm_audit.hip    coherence audit
+ *   dsm_events.hip   event trace: the replay kernel, its host twin and the formatter
  * Each kernel is launched from the unit that defines it.  Not part of the ABI.
  */
 #ifndef DSM_INTERNAL_H
@@ -90,6 +91,9 @@ struct dsm_ctx {
     size_t parse_off_cap;
     uint32_t *d_parse_list;          /* parse_kernel: [0] files for the EXACT pass, then ids  */
     size_t parse_list_cap;
+    /* dsm_events.hip */
+    uint32_t *d_ev_scratch;          /* replay_kernel: per-lane system state (dsm_events.h)   */
+    size_t ev_scratch_cap;
 };
 
 #define HIPCK(x) do { if ((x) != hipSuccess) return DSM_E_DEVICE; } while (0)
@@ -113,6 +117,8 @@ extern "C" int dsm_debug_order_state(dsm_ctx *c, uint32_t *counts, uint32_t *lis
 
 /* dsm_text.hip: called by dsm_close */
 void dsm_text_release(dsm_ctx *c);
+/* dsm_events.hip: called by dsm_close */
+void dsm_events_release(dsm_ctx *c);
 
 /* dsm_sim.hip: the transition kernel of a launch -- the fast kernel of (ring, mode), nullptr
  * where the dispatch has none, and the 256-deep re-run kernel; its resident workgroups per CU

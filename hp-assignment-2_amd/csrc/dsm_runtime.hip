@@ -133,6 +133,7 @@ extern "C" void dsm_close(dsm_ctx *c) {
                     c->d_res, c->d_cnt, c->d_recs, c->d_table, c->d_issue, c->d_issue_n};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     dsm_text_release(c);
+    dsm_events_release(c);
     for (int i = 0; i < DSM_TIMING_RING; ++i) {
         if (c->tev0[i]) (void)hipEventDestroy(c->tev0[i]);
         if (c->tev1[i]) (void)hipEventDestroy(c->tev1[i]);

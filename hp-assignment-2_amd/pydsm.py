@@ -73,6 +73,11 @@ class LaunchInfo(ctypes.Structure):
                 ("resume_mode", ctypes.c_int), ("ser_cap", ctypes.c_int)]
 
 
+class EventOpts(ctypes.Structure):
+    _fields_ = [("sched_seed", ctypes.c_uint64), ("sched_thresh", ctypes.c_uint32),
+                ("round_limit_log2", ctypes.c_uint32), ("inbox_limit", ctypes.c_uint32)]
+
+
 RESUME_FORMS = {0: "none", 1: "lock-step", 2: "serial", 3: "fast-forward lock-step"}
 
 
@@ -160,6 +165,12 @@ def lib():
             "dsm_read_dump": (i32, [i32, ctypes.c_char_p, vp]),
             "dsm_census_find": (i32, [vp, u32, u64, vp]),
             "dsm_parse_dumps_device": (i32, [vp, vp, vp, u64, vp, u32, vp, vp]),
+            # ABI 5 (+events): the event trace
+            "dsm_trace_events_device": (i32, [vp, vp, vp, u64, vp, u64, vp, u32, vp, vp, vp, vp]),
+            "dsm_trace_events": (i32, [i32, vp, vp, u32, u64, vp, u64, ctypes.POINTER(EventOpts), vp, u32,
+                                       vp, vp, vp]),
+            "dsm_event_trace_hash": (u64, [vp, u64]),
+            "dsm_format_event_trace": (i32, [vp, u64, i32, ctypes.c_char_p, ctypes.c_size_t]),
             # test-only (csrc/dsm_internal.h, not in include/dsm.h)
             "dsm_debug_order_state": (i32, [vp, vp, vp, vp, u64, u64, vp, u32, ctypes.POINTER(u32),
                                             ctypes.POINTER(i32)]),
@@ -366,6 +377,73 @@ def audit_to_dict(a):
                         for b in range(AUDIT_NCLASS) if v[4 + b]}}
 
 
+# -- event trace (ABI 5 +events) ----------------------------------------------------------------
+EV_RECV, EV_SEND, EV_ISSUE, EV_ACCESS, EV_REPLACE, EV_FINISHED = range(6)
+EV_KIND_NAMES = ["RECV", "SEND", "ISSUE", "ACCESS", "REPLACE", "FINISHED"]
+EV_FMT_INSTR, EV_FMT_MSG = 1, 2
+EV_FMT_ALL = EV_FMT_INSTR | EV_FMT_MSG
+EV_FMT = {"instr": EV_FMT_INSTR, "msg": EV_FMT_MSG, "all": EV_FMT_ALL}
+EVENTS_MAX_LANES = 65536                     # DSM_EVENTS_MAX_LANES
+
+
+def event_fields(events):
+    """Event words (uint64) -> a dict of arrays: addr, value, type, node, peer, aux, kind, round,
+    flag (the bit fields of include/dsm.h)."""
+    e = np.asarray(events, dtype=np.uint64)
+    f = lambda lo, w: ((e >> np.uint64(lo)) & np.uint64((1 << w) - 1)).astype(np.int64)
+    return {"addr": f(0, 8), "value": f(8, 8), "type": f(16, 4), "node": f(20, 3), "peer": f(23, 3),
+            "aux": f(26, 3), "kind": f(29, 3), "round": f(32, 23), "flag": f(55, 1)}
+
+
+def trace_events(np_, traces, counts, ids=None, cap=0, sched=(0, SCHED_LOCKSTEP), round_limit_log2=0,
+                 inbox_limit=0):
+    """dsm_trace_events (the host replay; no GPU): traces [n_sys, np, max_instr] u16, counts
+    [n_sys, np]; ids None: every system -> (events uint64 [n_ids, cap] or None when cap is 0,
+    counts uint32 [n_ids], hashes uint64 [n_ids], results RESULT_DTYPE [n_ids]).  A system's
+    first min(cap, count) events are stored."""
+    traces = np.ascontiguousarray(traces, dtype=np.uint16)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    n_sys, _, stride = traces.shape
+    assert traces.shape[1] == np_ and counts.shape == (n_sys, np_)
+    if ids is not None:
+        ids = np.ascontiguousarray(ids, dtype=np.uint64)
+    n = n_sys if ids is None else len(ids)
+    ev = np.zeros((n, cap), dtype=np.uint64) if cap else None
+    cnt = np.zeros(n, dtype=np.uint32)
+    hs = np.zeros(n, dtype=np.uint64)
+    res = np.zeros(n, dtype=RESULT_DTYPE)
+    opts = EventOpts(sched[0], sched[1], round_limit_log2, inbox_limit)
+    _check(lib().dsm_trace_events(np_, _ptr(traces), _ptr(counts), stride, n_sys, _ptr(ids), n,
+                                  ctypes.byref(opts), _ptr(ev), cap, _ptr(cnt), _ptr(hs), _ptr(res)),
+           "dsm_trace_events")
+    return ev, cnt, hs, res
+
+
+def event_trace_hash(events):
+    """dsm_event_trace_hash of a system's events."""
+    events = np.ascontiguousarray(events, dtype=np.uint64).reshape(-1)
+    return int(lib().dsm_event_trace_hash(_ptr(events) if events.size else None, events.size))
+
+
+def format_event_trace_rc(events, what=EV_FMT_ALL, cap=None):
+    """dsm_format_event_trace into a buffer of cap bytes (default: ample) -> (return code, bytes)."""
+    events = np.ascontiguousarray(events, dtype=np.uint64).reshape(-1)
+    if cap is None:
+        cap = 160 * max(events.size, 1) + 1
+    buf = ctypes.create_string_buffer(max(cap, 1))
+    n = lib().dsm_format_event_trace(_ptr(events) if events.size else None, events.size,
+                                     EV_FMT.get(what, what), buf, cap)
+    return n, (buf.raw[:n] if n >= 0 else b"")
+
+
+def format_event_trace(events, what=EV_FMT_ALL):
+    """The reference's DEBUG_INSTR / DEBUG_MSG lines of the events, as bytes."""
+    n, text = format_event_trace_rc(events, what)
+    if n < 0:
+        raise DsmError(n, "dsm_format_event_trace")
+    return text
+
+
 class Group:
     """dsm_group: one RCCL communicator per GPU for the end-of-run all-reduces (ABI 5).
     Rank 0 makes the id (Group.unique_id()) and hands it to every rank out of band."""
@@ -541,6 +619,45 @@ class Engine:
         _check(lib().dsm_audit_run_device(self.ctx, first_sys, n_sys, _dptr(d_words, 4 * n_sys),
                                           _dptr(d_audit, 8 * NAUDIT), ctypes.c_void_p(stream)),
                "dsm_audit_run_device")
+
+    def trace_events_device(self, d_traces, d_counts, n_sys, d_ids, n_ids, d_events, event_cap,
+                            d_n_events, d_hash, d_results, stream=0):
+        """dsm_trace_events_device: pointers or tensors; each output may be None."""
+        _check(lib().dsm_trace_events_device(self.ctx, _dptr(d_traces), _dptr(d_counts), n_sys,
+                                             _dptr(d_ids, 8 * n_ids), n_ids,
+                                             _dptr(d_events, 8 * n_ids * event_cap), event_cap,
+                                             _dptr(d_n_events, 4 * n_ids), _dptr(d_hash, 8 * n_ids),
+                                             _dptr(d_results, 32 * n_ids), ctypes.c_void_p(stream)),
+               "dsm_trace_events_device")
+
+    def event_trace(self, traces, counts, ids=None, cap=0):
+        """Replay systems `ids` (None: all) of a packed ensemble on the GPU under the engine's
+        schedule, round limit and inbox limit -> (events uint64 [n_ids, cap] or None when cap is
+        0, counts uint32 [n_ids], hashes uint64 [n_ids], results RESULT_DTYPE [n_ids])."""
+        import torch
+        traces = np.ascontiguousarray(traces, dtype=np.uint16)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        n_sys = counts.shape[0]
+        assert traces.shape == (n_sys, self.np, self.max_instr), traces.shape
+        assert counts.shape == (n_sys, self.np)
+        dev = torch.device("cuda", self.device)
+        d_tr = torch.from_numpy(traces.view(np.int16).reshape(-1)).to(dev)
+        d_cn = torch.from_numpy(counts.view(np.int32).reshape(-1)).to(dev)
+        d_ids = None
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, dtype=np.uint64)
+            d_ids = torch.from_numpy(ids.view(np.int64)).to(dev)
+        n = n_sys if ids is None else len(ids)
+        d_ev = torch.zeros(max(n * cap, 1), dtype=torch.int64, device=dev) if cap else None
+        d_n = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        d_h = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+        d_res = torch.zeros(4 * max(n, 1), dtype=torch.int64, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        self.trace_events_device(d_tr, d_cn, n_sys, d_ids, n, d_ev, cap, d_n, d_h, d_res, st)
+        torch.cuda.synchronize(dev)
+        ev = d_ev.cpu().numpy().view(np.uint64)[:n * cap].reshape(n, cap) if cap else None
+        return (ev, d_n.cpu().numpy().view(np.uint32)[:n], d_h.cpu().numpy().view(np.uint64)[:n],
+                d_res.cpu().numpy().view(RESULT_DTYPE)[:n])
 
     def explore(self, traces, counts, k, seed, thresh=0x8000, kind=CENSUS_DUMPS, audit=False):
         """k seeded interleavings of ONE system (traces [np, max_instr] u16, counts [np]) in

@@ -50,7 +50,9 @@ extern "C" {
                                 dsm_census_*) is new symbols only, no struct or call changed;
                              5 (+audit): additive -- the coherence audit (dsm_audit_*) likewise;
                              5 (+dump reader): additive -- dsm_parse_dump / dsm_read_dump /
-                                dsm_parse_dumps_device and dsm_census_find likewise */
+                                dsm_parse_dumps_device and dsm_census_find likewise;
+                             5 (+events): additive -- the event trace (dsm_trace_events*,
+                                dsm_event_trace_hash, dsm_format_event_trace) likewise */
 
 #define DSM_MAX_NP 8             /* bitVector is one byte (README.md:51)                  */
 #define DSM_CACHE_SIZE 4         /* CACHE_SIZE      assignment.c:10                        */
@@ -539,6 +541,76 @@ int dsm_audit_states(int np, const dsm_node_state *states, uint32_t state_stride
 int dsm_audit_merge(dsm_audit *dst, const dsm_audit *src);
 /* "MULTI_OWNER" .. "BAD_RECORD" for bits 0..6, NULL for any other bit (host only) */
 const char *dsm_audit_class_name(int bit);
+
+/* ---- event trace: a system's DEBUG_INSTR and DEBUG_MSG logs -------------------------------- *
+ * The census says which outcomes a run has, the audit whether one is coherent; the event trace
+ * says why: which messages crossed, in which order, and which access hit or evicted what.  A
+ * separate replay kernel (one system per lane) re-runs chosen systems of a packed ensemble under
+ * the ctx's schedule, round limit and inbox limit and emits one 64-bit event per line the
+ * reference's two debugging builds (-DDEBUG_INSTR, -DDEBUG_MSG) would print, in the order they
+ * would print them under the schedule: by round, then node ascending, then program order within
+ * the node's action.  The engine kernels are untouched; the replay's results are the engine's.
+ *
+ *   bits 0-7 address, 8-15 value, 16-19 type (transactionType; ISSUE / ACCESS: 0 RD, 1 WR),
+ *   20-22 node (the acting processor, threadId), 23-25 peer (RECV: msg.sender, SEND: receiver,
+ *   else 0), 26-28 aux (secondReceiver, or a line state), 29-31 kind, 32-54 round (1-based),
+ *   55 flag, 56-63 zero.
+ *
+ *   DSM_EV_RECV      a message popped and handled (assignment.c:172)
+ *   DSM_EV_SEND      one sendMessage call (:736), right after the RECV or ISSUE whose handler
+ *                    made it, in program order: an INV multicast in ascending receiver order
+ *                    (:352-362); FLUSH and FLUSH_INVACK to the home first, then to
+ *                    secondReceiver; on a miss the eviction before the request
+ *   DSM_EV_ISSUE     an instruction issued (:596); value is the low byte of the packed word
+ *   DSM_EV_ACCESS    its hit or miss (:610 / :614 / :637 + :648 / :668): flag 1 on a hit, aux the
+ *                    line's state before on a hit, value the line's value before on a read hit
+ *   DSM_EV_REPLACE   handleCacheReplacement (:751): address and aux are the victim line's address
+ *                    and state; it precedes the eviction's SEND
+ *   DSM_EV_FINISHED  the node finished issuing (:691)
+ * Every field not named for a kind is 0.  Message fields are canonical -- only what a receiver
+ * reads: value is msg.value for WRITE_REQUEST, EVICT_MODIFIED, REPLY_RD, FLUSH and FLUSH_INVACK
+ * and bitVector & ((1 << np) - 1) for REPLY_ID; aux is secondReceiver for WRITEBACK_INT,
+ * WRITEBACK_INV, FLUSH and FLUSH_INVACK; flag is 1 for a REPLY_RD that installs the line
+ * EXCLUSIVE.  A stalled node logs nothing; the quiescent last round logs nothing; an action whose
+ * handler asserts (an instruction whose home is >= np among them) logs only its RECV or ISSUE,
+ * and the other nodes of that round still act and log.  The log describes the regular build: the
+ * DEBUG_MSG-only recovery branch (:549-559) and the handler-internal DEBUG_MSG notes stay out. */
+enum { DSM_EV_RECV = 0, DSM_EV_SEND = 1, DSM_EV_ISSUE = 2, DSM_EV_ACCESS = 3, DSM_EV_REPLACE = 4,
+       DSM_EV_FINISHED = 5 };
+#define DSM_EV_FMT_INSTR 1       /* the DEBUG_INSTR lines: ISSUE, ACCESS, REPLACE, FINISHED       */
+#define DSM_EV_FMT_MSG 2         /* the DEBUG_MSG lines: RECV, SEND                               */
+#define DSM_EVENTS_MAX_LANES 65536u   /* upper bound on the systems the replay kernel has in flight */
+typedef struct dsm_event_opts {
+    uint64_t sched_seed;
+    uint32_t sched_thresh;       /* >= DSM_SCHED_LOCKSTEP: lock-step                             */
+    uint32_t round_limit_log2;   /* 0 = DSM_MAX_ROUNDS                                           */
+    uint32_t inbox_limit;        /* 1..256, 0 = 256                                              */
+} dsm_event_opts;
+/* Replay systems d_ids[0 .. n_ids) (NULL: 0 .. n_ids-1) of a packed ensemble of n_sys systems
+ * (layout of dsm_run_packed_device; id i uses trace block i and is its schedule id, as in a run)
+ * under the ctx's schedule, round limit and inbox limit.  d_events is [n_ids][event_cap] (NULL
+ * with event_cap 0: counts, hashes and results only); min(event_cap, n) events of a system are
+ * stored and d_n_events holds the exact n; d_hash the dsm_event_trace_hash of all n; d_results
+ * the engine's result of that system under the same settings, bit for bit.  Each output may be
+ * NULL.  An id >= n_sys is not run and nothing is read for it: result all ones, count 0, hash 0.
+ * The per-node inboxes live in a ctx-owned scratch sized by the lanes in flight, allocated at
+ * the first call and freed by dsm_close.  Asynchronous on `stream`; n_ids == 0 is a no-op. */
+int dsm_trace_events_device(dsm_ctx *ctx, const uint16_t *d_traces, const uint32_t *d_counts,
+                            uint64_t n_sys, const uint64_t *d_ids, uint64_t n_ids, uint64_t *d_events,
+                            uint32_t event_cap, uint32_t *d_n_events, uint64_t *d_hash,
+                            dsm_sys_result *d_results, void *stream);
+/* the same on the host (no GPU needed): the plain reference.  traces [n_sys][np][max_instr];
+ * opts NULL: lock-step, no limits.  An id >= n_sys is DSM_E_INVAL. */
+int dsm_trace_events(int np, const uint16_t *traces, const uint32_t *counts, uint32_t max_instr,
+                     uint64_t n_sys, const uint64_t *ids, uint64_t n_ids, const dsm_event_opts *opts,
+                     uint64_t *events, uint32_t event_cap, uint32_t *n_events, uint64_t *hash,
+                     dsm_sys_result *results);
+/* h0 = 0x9E3779B97F4A7C15, then h = fmix64(h ^ e) over the events (host only) */
+uint64_t dsm_event_trace_hash(const uint64_t *events, uint64_t n);
+/* The reference's own printf text of the events `what` selects (DSM_EV_FMT_INSTR, DSM_EV_FMT_MSG
+ * or both, interleaved in event order); an ACCESS write hit on SHARED prints :637 and then :648.
+ * Returns the length, or DSM_E_INVAL if cap is too small (host only). */
+int dsm_format_event_trace(const uint64_t *events, uint64_t n, int what, char *buf, size_t cap);
 
 /* ---- multi-GPU group: RCCL over xGMI --------------------------------------- *
  * Systems are independent, so an ensemble shards over GPUs with no data-path exchange; the
