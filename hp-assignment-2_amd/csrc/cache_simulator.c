@@ -77,6 +77,28 @@
  *                    Exits 0 when the joint outcome was produced, 4 when it was not, 3 when it
  *                    was not found and a census table dropped a system, 1 when a file in DIR is
  *                    not what printProcessorState prints (it is named on stderr).
+ *   --reach          exhaustive exploration instead of a sample: every state the system can reach
+ *                    when, in each round, any non-empty subset of the nodes that have an action
+ *                    takes it (dsm_reach_device) -- the closure of every --schedule.  Not valid
+ *                    with --explore, --schedule, --events, --issue-order or --audit.  Prints
+ *                        reached S states, T transitions, K outcomes (exhaustive)
+ *                    or, when a limit stopped the search,
+ *                        reached S states, T transitions, K outcomes (truncated at N states / depth D: not exhaustive)
+ *                    and then the `outcome k:` lines of --explore: count is the number of terminal
+ *                    states with the outcome, first the lowest terminal state id.  Exits 0.
+ *   --reach-states N   at most N states (default 4194304); a level that would pass N is dropped
+ *   --reach-depth D    no level deeper than D (default 0: none)
+ *   --reach-inbox L    inbox limit 1..16 (default 16)
+ *                    With --reach, --explore-kind takes dumps or final; --explore-dir D replays
+ *                    each outcome's first terminal state's witness on the host and writes
+ *                    D/outcome_<k>/core_<n>_output.txt for the dumped nodes and
+ *                    D/outcome_<k>/schedule.txt, one act mask per round in two hex digits, root
+ *                    first; --check DIR (with kind dumps only) forms the DUMPS key of DIR's
+ *                    output files and answers
+ *                        check: can occur (outcome k)
+ *                        check: cannot occur
+ *                        check: not found; the exploration was truncated
+ *                    with exit code 0, 4 or 3.
  */
 #include <errno.h>
 #include <stdio.h>
@@ -92,7 +114,9 @@ static void usage(const char *argv0) {
     fprintf(stderr, "Usage: %s [--np 4|8] [--max-instr N] [--device D] [--quiet] [--issue-order FILE]\n"
                     "          [--schedule SEED:THRESH] [--explore N [--explore-dir DIR]\n"
                     "          [--explore-kind dumps|final|full] [--check DIR]] [--audit]\n"
-                    "          [--events FILE [--events-kind instr|msg|all]] <test_directory>\n", argv0);
+                    "          [--events FILE [--events-kind instr|msg|all]]\n"
+                    "          [--reach [--reach-states N] [--reach-depth D] [--reach-inbox L] [--explore-dir DIR]\n"
+                    "          [--explore-kind dumps|final] [--check DIR]] <test_directory>\n", argv0);
 }
 
 static const char *const status_names[5] = {"COMPLETED", "DEADLOCKED", "RING_OVERFLOW", "ASSERT_FAILED",
@@ -365,8 +389,155 @@ fail:
     return code;
 }
 
+/* --reach: every state the system can reach under the schedule model (dsm_reach_device), the
+ * terminal states grouped by outcome on the host (dsm_census_insert).  Returns the process exit
+ * code. */
+static int reach(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces, const uint32_t *counts,
+                 unsigned long long max_states, uint32_t max_depth, uint32_t inbox, int kind, const char *out_dir,
+                 const char *check_dir) {
+    const size_t tr_bytes = (size_t)np * stride * sizeof(uint16_t);
+    const uint64_t term_cap = max_states < (DSM_CENSUS_MAX_CAP / 2) ? max_states : (DSM_CENSUS_MAX_CAP / 2);
+    uint32_t cap = DSM_CENSUS_MIN_CAP;
+    uint16_t *d_tr = NULL;
+    uint32_t *d_cn = NULL, *d_par = NULL, *par = NULL;
+    uint8_t *d_msk = NULL, *msk = NULL, *path = NULL;
+    dsm_reach_terminal *d_term = NULL, *term = NULL;
+    uint64_t *cen = NULL;
+    dsm_outcome *outc = NULL;
+    dsm_reach_info info;
+    dsm_reach_opts opts;
+    int rc = DSM_OK, code = EXIT_FAILURE;
+    const char *what = "device memory";
+    dsm_node_state want[DSM_MAX_NP];
+    int have[DSM_MAX_NP] = {0};
+    memset(&opts, 0, sizeof opts);
+    opts.inbox_limit = inbox; opts.kind = (uint32_t)kind; opts.max_states = max_states; opts.max_depth = max_depth;
+    for (int c = 0; check_dir && c < np; ++c) {
+        rc = dsm_read_dump(c, check_dir, &want[c]);
+        have[c] = rc == DSM_OK;
+        if (rc == DSM_E_FORMAT) {
+            fprintf(stderr, "Error: %s/core_%d_output.txt is not a dump of core %d as printProcessorState prints it\n",
+                    check_dir, c, c);
+            what = NULL;
+            goto fail;
+        }
+        if (rc != DSM_OK && rc != DSM_E_IO) { what = "dsm_read_dump"; goto fail; }
+        rc = DSM_OK;
+    }
+    if (hipMalloc((void **)&d_tr, tr_bytes) != hipSuccess || hipMalloc((void **)&d_cn, (size_t)np * sizeof(uint32_t)) != hipSuccess ||
+        hipMalloc((void **)&d_par, (size_t)max_states * sizeof(uint32_t)) != hipSuccess ||
+        hipMalloc((void **)&d_msk, (size_t)max_states) != hipSuccess ||
+        hipMalloc((void **)&d_term, (size_t)term_cap * sizeof(dsm_reach_terminal)) != hipSuccess ||
+        hipMemcpy(d_tr, traces, tr_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_cn, counts, (size_t)np * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
+        goto fail;
+    what = "dsm_reach_device";
+    if ((rc = dsm_reach_device(ctx, d_tr, d_cn, &opts, &info, d_par, d_msk, NULL, NULL, d_term, term_cap, NULL))) goto fail;
+    if (info.terminals > term_cap) { what = "too many terminal states for one census"; goto fail; }
+    while (cap < 2 * info.terminals) cap <<= 1;
+    what = "out of memory";
+    par = (uint32_t *)malloc((size_t)info.states * sizeof(uint32_t));
+    msk = (uint8_t *)malloc((size_t)info.states);
+    path = (uint8_t *)malloc(DSM_REACH_MAX_LEVELS);
+    term = (dsm_reach_terminal *)malloc((size_t)(info.terminals ? info.terminals : 1) * sizeof *term);
+    cen = (uint64_t *)calloc(DSM_CENSUS_WORDS(cap), sizeof(uint64_t));
+    outc = (dsm_outcome *)malloc((size_t)cap * sizeof(dsm_outcome));
+    if (!par || !msk || !path || !term || !cen || !outc) goto fail;
+    what = "read-back";
+    if (hipMemcpy(par, d_par, (size_t)info.states * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(msk, d_msk, (size_t)info.states, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(term, d_term, (size_t)info.terminals * sizeof *term, hipMemcpyDeviceToHost) != hipSuccess)
+        goto fail;
+    what = "dsm_census_insert";
+    for (uint64_t t = 0; t < info.terminals; ++t)
+        if ((rc = dsm_census_insert(cen, cap, dsm_outcome_key(kind, &term[t].res), term[t].state))) goto fail;
+    uint64_t k = 0;
+    what = "dsm_census_sorted";
+    if ((rc = dsm_census_sorted(cen, cap, outc, cap, &k))) goto fail;
+    const int truncated = (info.flags & (DSM_REACH_F_STATES | DSM_REACH_F_DEPTH)) != 0;
+    printf("reached %llu states, %llu transitions, %llu outcomes ", (unsigned long long)info.states,
+           (unsigned long long)info.transitions, (unsigned long long)k);
+    if (truncated) printf("(truncated at %llu states / depth %u: not exhaustive)\n", max_states, max_depth);
+    else printf("(exhaustive)\n");
+    if (info.flags & DSM_REACH_F_COLLISION)
+        printf("warning: %llu fingerprint collisions: the result is not exact\n", (unsigned long long)info.fp_collisions);
+    if (out_dir && mkdir(out_dir, 0777) != 0 && errno != EEXIST) { what = out_dir; rc = DSM_E_IO; goto fail; }
+    for (uint64_t o = 0; o < k; ++o) {
+        const dsm_reach_terminal *t = NULL;             /* the outcome's first terminal: ids ascend */
+        for (uint64_t lo = 0, hi = info.terminals; lo < hi;) {
+            const uint64_t mid = lo + (hi - lo) / 2;
+            if (term[mid].state < outc[o].first_sys) lo = mid + 1;
+            else { hi = mid; t = &term[mid]; }
+        }
+        what = "census";
+        if (!t || t->state != outc[o].first_sys) { rc = DSM_E_STATE; goto fail; }
+        const uint32_t st = t->res.status & 0xFFu, dumped = t->res.status >> 8;
+        printf("outcome %llu: count %llu first %llu status %s dumped 0x%x dump_hash 0x%016llx\n",
+               (unsigned long long)o, (unsigned long long)outc[o].count, (unsigned long long)outc[o].first_sys,
+               st < 5 ? status_names[st] : "?", dumped, (unsigned long long)t->res.dump_hash);
+        if (out_dir) {                                  /* the witness, replayed on the host */
+            char dir[512], file[600];
+            dsm_node_state dump[DSM_MAX_NP];
+            uint64_t n = 0;
+            what = "witness";
+            if ((rc = dsm_reach_path(par, msk, t->state, path, DSM_REACH_MAX_LEVELS, &n))) goto fail;
+            if ((rc = dsm_reach_replay(np, traces, counts, stride, inbox, path, n, dump, NULL, NULL))) goto fail;
+            rc = DSM_E_IO;
+            if (snprintf(dir, sizeof dir, "%s/outcome_%llu", out_dir, (unsigned long long)o) >= (int)sizeof dir ||
+                (mkdir(dir, 0777) != 0 && errno != EEXIST)) goto fail;
+            for (int c = 0; c < np; ++c)
+                if (((dumped >> c) & 1u) && (rc = dsm_write_dump(c, &dump[c], dir))) goto fail;
+            rc = DSM_E_IO;
+            snprintf(file, sizeof file, "%s/schedule.txt", dir);
+            FILE *f = fopen(file, "w");
+            if (!f) goto fail;
+            for (uint64_t r = 0; r < n; ++r) fprintf(f, "%02x\n", path[r]);
+            if (fclose(f) != 0) goto fail;
+            rc = DSM_OK;
+        }
+    }
+    code = 0;
+    if (check_dir) {
+        /* the DUMPS key of DIR's files: the dumped mask and the sum of the node hashes are known,
+         * the status is COMPLETED when every core wrote a file, else any of the three others */
+        dsm_sys_result r;
+        uint32_t mask = 0;
+        memset(&r, 0, sizeof r);
+        for (int c = 0; c < np; ++c)
+            if (have[c]) { mask |= 1u << c; r.dump_hash += dsm_node_hash(c, &want[c], 15); }
+        const uint32_t all = (1u << np) - 1u;
+        long long found = -1;
+        for (uint32_t st = (mask == all ? DSM_COMPLETED : DSM_DEADLOCKED); st <= (mask == all ? DSM_COMPLETED : DSM_ASSERT_FAILED) && found < 0; ++st) {
+            dsm_outcome hit;
+            r.status = st | (mask << 8);
+            what = "dsm_census_find";
+            if ((rc = dsm_census_find(cen, cap, dsm_outcome_key(DSM_CENSUS_DUMPS, &r), &hit)) < 0) goto fail;
+            for (uint64_t o = 0; rc && o < k; ++o)
+                if (outc[o].key == hit.key) found = (long long)o;
+            rc = DSM_OK;
+        }
+        if (found >= 0) printf("check: can occur (outcome %lld)\n", found);
+        else if (truncated) printf("check: not found; the exploration was truncated\n");
+        else printf("check: cannot occur\n");
+        code = found >= 0 ? 0 : truncated ? 3 : 4;
+    }
+    what = NULL;
+fail:
+    if (what) fprintf(stderr, "Error: reach: %s%s%s\n", what, rc ? ": " : "", rc ? dsm_strerror(rc) : "");
+    if (what) code = EXIT_FAILURE;
+    if (d_tr) (void)hipFree(d_tr);
+    if (d_cn) (void)hipFree(d_cn);
+    if (d_par) (void)hipFree(d_par);
+    if (d_msk) (void)hipFree(d_msk);
+    if (d_term) (void)hipFree(d_term);
+    free(par); free(msk); free(path); free(term); free(cen); free(outc);
+    return code;
+}
+
 int main(int argc, char **argv) {
-    int np = 4, device = 0, quiet = 0, audit = 0;
+    int np = 4, device = 0, quiet = 0, audit = 0, do_reach = 0;
+    long long reach_states = 1ll << 22, reach_depth = 0, reach_inbox = 16;
+    int reach_opts = 0;
     uint32_t max_instr = DSM_REF_MAX_INSTR;
     const char *dir = NULL, *issue_file = NULL;
     unsigned long long sched_seed = 0;
@@ -390,6 +561,10 @@ int main(int argc, char **argv) {
             explore_n = atoll(argv[++i]);
             if (explore_n < 1 || explore_n > (long long)DSM_CENSUS_MAX_CAP) { usage(argv[0]); return EXIT_FAILURE; }
         }
+        else if (!strcmp(argv[i], "--reach")) do_reach = 1;
+        else if (!strcmp(argv[i], "--reach-states") && i + 1 < argc) { reach_states = atoll(argv[++i]); reach_opts = 1; }
+        else if (!strcmp(argv[i], "--reach-depth") && i + 1 < argc) { reach_depth = atoll(argv[++i]); reach_opts = 1; }
+        else if (!strcmp(argv[i], "--reach-inbox") && i + 1 < argc) { reach_inbox = atoll(argv[++i]); reach_opts = 1; }
         else if (!strcmp(argv[i], "--explore-dir") && i + 1 < argc) { explore_dir = argv[++i]; explore_opts = 1; }
         else if (!strcmp(argv[i], "--check") && i + 1 < argc) { check_dir = argv[++i]; explore_opts = 1; }
         else if (!strcmp(argv[i], "--events") && i + 1 < argc) events_file = argv[++i];
@@ -417,7 +592,15 @@ int main(int argc, char **argv) {
         usage(argv[0]);
         return EXIT_FAILURE;
     }
-    if ((explore_n && issue_file) || (!explore_n && explore_opts)) { usage(argv[0]); return EXIT_FAILURE; }
+    if ((explore_n && issue_file) || (!explore_n && !do_reach && explore_opts)) { usage(argv[0]); return EXIT_FAILURE; }
+    if ((reach_opts && !do_reach) ||
+        (do_reach && (explore_n || have_sched || events_file || issue_file || audit || explore_kind == DSM_CENSUS_FULL ||
+                      (check_dir && explore_kind != DSM_CENSUS_DUMPS) || reach_states < 1 ||
+                      reach_states > (long long)DSM_REACH_MAX_STATES || reach_depth < 0 ||
+                      reach_depth >= (long long)DSM_REACH_MAX_LEVELS || reach_inbox < 1 || reach_inbox > 16))) {
+        usage(argv[0]);
+        return EXIT_FAILURE;
+    }
     if ((events_opts && !events_file) || (events_file && !*events_file) ||
         (explore_n && events_file && (!explore_dir || strchr(events_file, '/')))) { usage(argv[0]); return EXIT_FAILURE; }
     if (explore_n && !have_sched) { sched_seed = 0; sched_thresh = 0x8000u; }
@@ -480,6 +663,13 @@ int main(int argc, char **argv) {
     fflush(stdout);
     free(text);
 
+    if (do_reach) {
+        const int code = reach(ctx, np, stride, traces, counts, (unsigned long long)reach_states, (uint32_t)reach_depth,
+                               (uint32_t)reach_inbox, explore_kind, explore_dir, check_dir);
+        dsm_close(ctx);
+        free(traces);
+        return code;
+    }
     if (explore_n) {
         const int code = explore(ctx, np, stride, traces, counts, (uint32_t)explore_n, sched_seed, sched_thresh,
                                  explore_kind, explore_dir, audit, check_dir, events_file, events_kind);

@@ -7,7 +7,7 @@
  *                                             byte-for-byte
  *   dsm_parse_dump / dsm_read_dump            their inverse: an output file back into a record
  *   dsm_node_hash                             canonical 64-bit hash of a node record
- *   dsm_outcome_key / dsm_census_results / _merge / _sorted / _find
+ *   dsm_outcome_key / dsm_census_results / _insert / _merge / _sorted / _find
  *                                             the outcome census on the host
  *   dsm_audit_states / _merge / _class_name   the coherence audit on the host
  */
@@ -336,10 +336,15 @@ int dsm_census_results(const dsm_sys_result *res, uint64_t n_sys, uint64_t first
     if (!census || (n_sys && !res) || !census_cap_ok(cap)) return DSM_E_INVAL;
     if (kind != DSM_CENSUS_DUMPS && kind != DSM_CENSUS_FINAL && kind != DSM_CENSUS_FULL) return DSM_E_INVAL;
     memset(census, 0, DSM_CENSUS_WORDS(cap) * sizeof(uint64_t));
-    for (uint64_t i = 0; i < n_sys; ++i) {
-        census[0]++;
-        if (!census_add(census, cap, dsm_outcome_key(kind, &res[i]), 1, ~(first_sys + i))) census[2]++;
-    }
+    for (uint64_t i = 0; i < n_sys; ++i) (void)dsm_census_insert(census, cap, dsm_outcome_key(kind, &res[i]), first_sys + i);
+    return DSM_OK;
+}
+
+/* one system: the update dsm_census_results loops over */
+int dsm_census_insert(uint64_t *census, uint32_t cap, uint64_t key, uint64_t sys_id) {
+    if (!census || !census_cap_ok(cap) || key == 0) return DSM_E_INVAL;
+    census[0]++;
+    if (!census_add(census, cap, key, 1, ~sys_id)) census[2]++;
     return DSM_OK;
 }
 

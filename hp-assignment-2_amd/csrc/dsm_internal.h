@@ -9,6 +9,7 @@
  *   dsm_census.hip   outcome census
  *   dsm_audit.hip    coherence audit
  *   dsm_events.hip   event trace: the replay kernel, its host twin and the formatter
+ *   dsm_reach.hip    exhaustive exploration: the search kernels, the host search, witnesses
  * Each kernel is launched from the unit that defines it.  Not part of the ABI.
  */
 #ifndef DSM_INTERNAL_H
@@ -114,6 +115,12 @@ struct dsm_ctx {
 extern "C" int dsm_debug_order_state(dsm_ctx *c, uint32_t *counts, uint32_t *list, uint32_t *order,
                                      uint64_t cap, uint64_t sys, uint32_t *rec, uint32_t rec_cap,
                                      uint32_t *rec_words, int *host_long);
+
+/* Measurement-only view of the last dsm_reach_device call that ran with DSM_REACH_TIMING=1 in the
+ * environment (not part of the ABI; tools/reach_time.py): device milliseconds summed per kernel
+ * class -- count (with its scans), expand, insert, resolve (with its scan), settle -- and the
+ * number of chunks of the last call, timed or not. */
+extern "C" int dsm_debug_reach_times(double *ms, uint64_t *chunks);
 
 /* dsm_text.hip: called by dsm_close */
 void dsm_text_release(dsm_ctx *c);

@@ -78,6 +78,12 @@ class EventOpts(ctypes.Structure):
                 ("round_limit_log2", ctypes.c_uint32), ("inbox_limit", ctypes.c_uint32)]
 
 
+class ReachOpts(ctypes.Structure):
+    _fields_ = [("inbox_limit", ctypes.c_uint32), ("kind", ctypes.c_uint32),
+                ("max_states", ctypes.c_uint64), ("max_depth", ctypes.c_uint32),
+                ("chunk", ctypes.c_uint32)]
+
+
 RESUME_FORMS = {0: "none", 1: "lock-step", 2: "serial", 3: "fast-forward lock-step"}
 
 
@@ -171,7 +177,14 @@ def lib():
                                        vp, vp, vp]),
             "dsm_event_trace_hash": (u64, [vp, u64]),
             "dsm_format_event_trace": (i32, [vp, u64, i32, ctypes.c_char_p, ctypes.c_size_t]),
+            # ABI 5 (+reach): the exhaustive exploration
+            "dsm_reach": (i32, [i32, vp, vp, u32, ctypes.POINTER(ReachOpts), vp, vp, vp, vp, vp, vp, u64]),
+            "dsm_reach_device": (i32, [vp, vp, vp, ctypes.POINTER(ReachOpts), vp, vp, vp, vp, vp, vp, u64, vp]),
+            "dsm_reach_path": (i32, [vp, vp, u64, vp, u64, ctypes.POINTER(u64)]),
+            "dsm_reach_replay": (i32, [i32, vp, vp, u32, u32, vp, u64, vp, vp, vp]),
+            "dsm_census_insert": (i32, [vp, u32, u64, u64]),
             # test-only (csrc/dsm_internal.h, not in include/dsm.h)
+            "dsm_debug_reach_times": (i32, [vp, ctypes.POINTER(u64)]),
             "dsm_debug_order_state": (i32, [vp, vp, vp, vp, u64, u64, vp, u32, ctypes.POINTER(u32),
                                             ctypes.POINTER(i32)]),
         }
@@ -444,6 +457,98 @@ def format_event_trace(events, what=EV_FMT_ALL):
     return text
 
 
+# -- exhaustive exploration (ABI 5 +reach) ----------------------------------------------------
+REACH_F_STATES, REACH_F_DEPTH, REACH_F_COLLISION = 1, 2, 4
+REACH_MAX_LEVELS = 4096                      # DSM_REACH_MAX_LEVELS
+REACH_INFO_FIELDS = ("states", "transitions", "terminals", "levels", "max_frontier", "max_fill",
+                     "st0", "st1", "st2", "st3", "st4", "fp_collisions", "flags", "reserved")
+REACH_TERMINAL_DTYPE = np.dtype([("state", "<u8"), ("status", "<u4"), ("rounds", "<u4"), ("msgs", "<u4"),
+                                 ("instrs", "<u4"), ("dump_hash", "<u8"), ("final_hash", "<u8")])
+assert REACH_TERMINAL_DTYPE.itemsize == 40
+
+
+def reach_info_to_dict(v):
+    a = dict(zip(REACH_INFO_FIELDS, (int(x) for x in v)))
+    out = {k: a[k] for k in REACH_INFO_FIELDS if not k.startswith("st") or k == "states"}
+    out["by_status"] = [a[f"st{i}"] for i in range(5)]
+    return out
+
+
+def reach_census(terminals, kind=CENSUS_DUMPS, cap=None):
+    """The terminals of a search grouped with dsm_census_insert -> (table, cap): per key the
+    number of terminal states and the lowest terminal state id."""
+    terminals = np.ascontiguousarray(terminals).view(REACH_TERMINAL_DTYPE).reshape(-1)
+    if cap is None:
+        cap = min(CENSUS_MAX_CAP, max(CENSUS_MIN_CAP, 1 << (2 * max(len(terminals), 1) - 1).bit_length()))
+    table = np.zeros(CENSUS_WORDS(cap), dtype=np.uint64)
+    res = np.zeros(1, dtype=RESULT_DTYPE)
+    for t in terminals:
+        for f in RESULT_DTYPE.names:
+            res[0][f] = t[f]
+        key = int(lib().dsm_outcome_key(CENSUS_KINDS.get(kind, kind), _ptr(res)))
+        _check(lib().dsm_census_insert(_ptr(table), cap, key, int(t["state"])), "dsm_census_insert")
+    return table, cap
+
+
+def _reach_result(info, parents, masks, fps, level_off, terms, kind):
+    d = reach_info_to_dict(info)
+    n, nt = d["states"], min(d["terminals"], len(terms))
+    table, cap = reach_census(terms[:nt], kind)
+    return {"info": d, "parents": parents[:n], "masks": masks[:n], "fps": fps[:n],
+            "level_off": level_off[:d["levels"] + 1], "terminals": terms[:nt], "census": table,
+            "census_cap": cap, "outcomes": census_sorted(table, cap)}
+
+
+def reach(np_, traces, counts, inbox_limit=16, kind=CENSUS_DUMPS, max_states=1 << 22, max_depth=0, term_cap=None):
+    """dsm_reach (the host search; no GPU) of ONE system: traces [np, stride] u16, counts [np] ->
+    a dict: info, parents, masks, fps (the first `states` entries), level_off, terminals
+    (REACH_TERMINAL_DTYPE), and the terminals' census (table, cap, sorted outcomes)."""
+    traces = np.ascontiguousarray(traces, dtype=np.uint16)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+    assert traces.ndim == 2 and traces.shape[0] == np_ and counts.shape == (np_,)
+    kind = CENSUS_KINDS.get(kind, kind)
+    opts = ReachOpts(inbox_limit, kind, max_states, max_depth, 0)
+    ok = 0 < max_states <= 1 << 31
+    n = max_states if ok else 1
+    term_cap = min(n, 1 << 20) if term_cap is None else term_cap
+    info = np.zeros(len(REACH_INFO_FIELDS), dtype=np.uint64)
+    parents, masks, fps = np.zeros(n, np.uint32), np.zeros(n, np.uint8), np.zeros(n, np.uint64)
+    level_off = np.zeros(REACH_MAX_LEVELS + 1, dtype=np.uint64)
+    terms = np.zeros(max(term_cap, 1), dtype=REACH_TERMINAL_DTYPE)
+    _check(lib().dsm_reach(np_, _ptr(traces), _ptr(counts), traces.shape[1], ctypes.byref(opts), _ptr(info),
+                           _ptr(parents), _ptr(masks), _ptr(fps), _ptr(level_off), _ptr(terms), term_cap),
+           "dsm_reach")
+    return _reach_result(info, parents, masks, fps, level_off, terms, kind)
+
+
+def reach_path(parents, masks, state):
+    """dsm_reach_path: the masks of the rounds from the root to `state`, root first (uint8)."""
+    parents = np.ascontiguousarray(parents, dtype=np.uint32)
+    masks = np.ascontiguousarray(masks, dtype=np.uint8)
+    if not 0 <= state < len(parents):
+        raise DsmError(E_INVAL, "reach_path: state")
+    out = np.zeros(REACH_MAX_LEVELS, dtype=np.uint8)
+    n = ctypes.c_uint64(0)
+    _check(lib().dsm_reach_path(_ptr(parents), _ptr(masks), state, _ptr(out), len(out), ctypes.byref(n)),
+           "dsm_reach_path")
+    return out[:n.value].copy()
+
+
+def reach_replay(np_, traces, counts, masks, inbox_limit=16):
+    """dsm_reach_replay: the masks applied from the root -> (dump records uint8 [np, 64], final
+    records uint8 [np, 64], result RESULT_DTYPE record)."""
+    traces = np.ascontiguousarray(traces, dtype=np.uint16)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+    masks = np.ascontiguousarray(masks, dtype=np.uint8).reshape(-1)
+    assert traces.ndim == 2 and traces.shape[0] == np_ and counts.shape == (np_,)
+    dump, fin = np.zeros((np_, 64), np.uint8), np.zeros((np_, 64), np.uint8)
+    res = np.zeros(1, dtype=RESULT_DTYPE)
+    _check(lib().dsm_reach_replay(np_, _ptr(traces), _ptr(counts), traces.shape[1], inbox_limit,
+                                  _ptr(masks) if masks.size else None, masks.size, _ptr(dump), _ptr(fin), _ptr(res)),
+           "dsm_reach_replay")
+    return dump, fin, res[0]
+
+
 class Group:
     """dsm_group: one RCCL communicator per GPU for the end-of-run all-reduces (ABI 5).
     Rank 0 makes the id (Group.unique_id()) and hands it to every rank out of band."""
@@ -658,6 +763,44 @@ class Engine:
         ev = d_ev.cpu().numpy().view(np.uint64)[:n * cap].reshape(n, cap) if cap else None
         return (ev, d_n.cpu().numpy().view(np.uint32)[:n], d_h.cpu().numpy().view(np.uint64)[:n],
                 d_res.cpu().numpy().view(RESULT_DTYPE)[:n])
+
+    def reach_device(self, d_trace, d_counts, opts, info, d_parents, d_masks, d_fps, level_off, d_terminals,
+                     term_cap, stream=0):
+        """dsm_reach_device: device pointers or tensors; info and level_off numpy arrays (host);
+        each output may be None.  Synchronous."""
+        return lib().dsm_reach_device(self.ctx, _dptr(d_trace), _dptr(d_counts), ctypes.byref(opts), _ptr(info),
+                                      _dptr(d_parents), _dptr(d_masks), _dptr(d_fps), _ptr(level_off),
+                                      _dptr(d_terminals), term_cap, ctypes.c_void_p(stream))
+
+    def reach(self, traces, counts, inbox_limit=16, kind=CENSUS_DUMPS, max_states=1 << 22, max_depth=0, chunk=0,
+              term_cap=None):
+        """Every state ONE system (traces [np, max_instr] u16, counts [np]) can reach, searched
+        on the GPU -> the dict of pydsm.reach: info, parents, masks, fps, level_off, terminals and
+        their census built with dsm_census_insert."""
+        import torch
+        tr, cn = np.array(traces, dtype=np.uint16), np.array(counts, dtype=np.uint32)
+        if tr.shape != (self.np, self.max_instr) or cn.shape != (self.np,):
+            raise DsmError(E_INVAL, "reach: one system of the engine's np and max_instr")
+        kind = CENSUS_KINDS.get(kind, kind)
+        dev = torch.device("cuda", self.device)
+        d_tr = torch.from_numpy(tr.view(np.int16).reshape(-1)).to(dev)
+        d_cn = torch.from_numpy(cn.view(np.int32)).to(dev)
+        ok = 0 < max_states <= 1 << 31
+        n = max_states if ok else 1
+        term_cap = min(n, 1 << 20) if term_cap is None else term_cap
+        d_par = torch.zeros(n, dtype=torch.int32, device=dev)
+        d_msk = torch.zeros(n, dtype=torch.uint8, device=dev)
+        d_fps = torch.zeros(n, dtype=torch.int64, device=dev)
+        d_term = torch.zeros(5 * max(term_cap, 1), dtype=torch.int64, device=dev)
+        info = np.zeros(len(REACH_INFO_FIELDS), dtype=np.uint64)
+        level_off = np.zeros(REACH_MAX_LEVELS + 1, dtype=np.uint64)
+        opts = ReachOpts(inbox_limit, kind, max_states, max_depth, chunk)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _check(self.reach_device(d_tr, d_cn, opts, info, d_par, d_msk, d_fps, level_off, d_term, term_cap, st),
+               "dsm_reach_device")
+        return _reach_result(info, d_par.cpu().numpy().view(np.uint32), d_msk.cpu().numpy(),
+                             d_fps.cpu().numpy().view(np.uint64),
+                             level_off, d_term.cpu().numpy().view(REACH_TERMINAL_DTYPE), kind)
 
     def explore(self, traces, counts, k, seed, thresh=0x8000, kind=CENSUS_DUMPS, audit=False):
         """k seeded interleavings of ONE system (traces [np, max_instr] u16, counts [np]) in

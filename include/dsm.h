@@ -52,7 +52,9 @@ extern "C" {
                              5 (+dump reader): additive -- dsm_parse_dump / dsm_read_dump /
                                 dsm_parse_dumps_device and dsm_census_find likewise;
                              5 (+events): additive -- the event trace (dsm_trace_events*,
-                                dsm_event_trace_hash, dsm_format_event_trace) likewise */
+                                dsm_event_trace_hash, dsm_format_event_trace) likewise;
+                             5 (+reach): additive -- the exhaustive exploration (dsm_reach*,
+                                dsm_census_insert) likewise */
 
 #define DSM_MAX_NP 8             /* bitVector is one byte (README.md:51)                  */
 #define DSM_CACHE_SIZE 4         /* CACHE_SIZE      assignment.c:10                        */
@@ -611,6 +613,122 @@ uint64_t dsm_event_trace_hash(const uint64_t *events, uint64_t n);
  * or both, interleaved in event order); an ACCESS write hit on SHARED prints :637 and then :648.
  * Returns the length, or DSM_E_INVAL if cap is too small (host only). */
 int dsm_format_event_trace(const uint64_t *events, uint64_t n, int what, char *buf, size_t cap);
+
+/* ---- exhaustive exploration: every outcome the schedule model can reach ------------------- *
+ * dsm_set_schedule samples interleavings; this is their closure: the graph of every state ONE
+ * system can reach when, in each round, any non-empty subset of the nodes that have an action
+ * takes it.  Every run of dsm_set_schedule, with any seed and threshold, is a path of this graph
+ * as long as its round limit does not bite and its inbox limit is the search's, so a key that is
+ * absent from an untruncated search cannot occur, and a reachable DSM_DEADLOCKED is found.
+ *
+ * State under inbox limit L (1..16; 0 = 16), DSM_REACH_WORDS(np) 32-bit words in this order:
+ * the np node records (dsm_node_state, all 16 words: pending, flags and issued are state); the np
+ * inbox fills; the np inboxes, 16 words each, front first, zero at and after the fill; dump_hash
+ * so far (low word, high word); a status word (0 running, else DSM_ASSERT_FAILED or
+ * DSM_RING_OVERFLOW); one zero word.  An inbox entry is canonical, exactly what a receiver reads
+ * (the event trace's message fields) and the sender: bits 0-7 value (msg.value for
+ * WRITE_REQUEST, EVICT_MODIFIED, REPLY_RD, FLUSH, FLUSH_INVACK; bitVector & ((1 << np) - 1) for
+ * REPLY_ID; else 0), 8-14 address, 15 set for a REPLY_RD that installs EXCLUSIVE and for an
+ * EVICT_SHARED the home sent to another node, 16-19 type, 20-22 secondReceiver (WRITEBACK_INT,
+ * WRITEBACK_INV, FLUSH, FLUSH_INVACK; else 0), 24-26 sender.  A state with an error status keeps
+ * no inbox (fills and entries 0).  Rounds, messages handled and instructions issued are no part
+ * of a state.  The root is initializeProcessor's state with empty inboxes.
+ *
+ * Enabled set A(s): node n when its inbox is not empty, or it is not waitingForReply and has an
+ * instruction left (counts clamped to the stride) or has not dumped.  A state is terminal when A
+ * is empty or its status is not 0; its result status is the error status, else DSM_COMPLETED when
+ * every node has dumped, else DSM_DEADLOCKED.  A running state has one successor per non-empty
+ * subset M of A, in ascending order of the mask: one round of SURVEY.md Appendix A in which
+ * exactly the nodes of M act in ascending order, their sends staged and delivered at the end of
+ * the round in ascending sender order, then program order, each delivery checked against L
+ * (beyond it: DSM_RING_OVERFLOW).  An action that asserts gives DSM_ASSERT_FAILED with no
+ * delivery; the other nodes of M still act.  The all-stall round is no successor.
+ *
+ * Numbering is breadth first: the root is 0; levels in order, within a level parents by ascending
+ * id and masks ascending; a successor gets the next id the first time it is seen.  Level d is the
+ * id range [level_off[d], level_off[d + 1]).  States are told apart by their 64-bit fingerprint
+ * alone (hash compaction): h = 0x9E3779B97F4A7C15, then h = fmix64(h ^ (w[2i] | w[2i+1] << 32))
+ * over the state's word pairs, 0 mapped to 1.  Two different states share a fingerprint with
+ * probability about n^2 / 2^65 among n states: 8e-6 at 2^24 states, 0.03 at 2^30.  The host search
+ * compares the full states of every fingerprint-equal pair it meets and counts the unequal ones in
+ * fp_collisions; the device counts those it sees between candidates of one chunk.  A non-zero
+ * count sets DSM_REACH_F_COLLISION: the result is then not exact.
+ *
+ * Limits: a level that would push the number of states past max_states is dropped whole
+ * (DSM_REACH_F_STATES); no level deeper than max_depth (0 = none, at most DSM_REACH_MAX_LEVELS - 1)
+ * is numbered (DSM_REACH_F_DEPTH when that left successors unexplored).  A result holds complete
+ * levels only; terminal states of the last kept level count.  transitions counts every successor
+ * of every expanded level, duplicates and those of a dropped level included. */
+#define DSM_REACH_WORDS(np) (33u * (unsigned)(np) + 4u)
+#define DSM_REACH_MAX_LEVELS 4096u     /* level_off holds DSM_REACH_MAX_LEVELS + 1 entries */
+#define DSM_REACH_MAX_STATES (1ull << 31)
+#define DSM_REACH_F_STATES 1u
+#define DSM_REACH_F_DEPTH 2u
+#define DSM_REACH_F_COLLISION 4u
+typedef struct dsm_reach_opts {
+    uint32_t inbox_limit;      /* 1..16, 0 = 16                                               */
+    uint32_t kind;             /* DSM_CENSUS_DUMPS or DSM_CENSUS_FINAL: the key the caller groups
+                                * the terminals by; DSM_CENSUS_FULL is DSM_E_INVAL (rounds, msgs
+                                * and instrs depend on the path)                               */
+    uint64_t max_states;       /* 1..DSM_REACH_MAX_STATES; sizes the caller's arrays          */
+    uint32_t max_depth;        /* 0 = none                                                    */
+    uint32_t chunk;            /* device: candidates per launch, 0 = a default (1 << 18)      */
+} dsm_reach_opts;
+typedef struct dsm_reach_info {
+    uint64_t states;
+    uint64_t transitions;
+    uint64_t terminals;        /* may exceed term_cap; min(term_cap, terminals) are written    */
+    uint64_t levels;
+    uint64_t max_frontier;     /* the largest level                                           */
+    uint64_t max_fill;         /* the deepest inbox of any numbered state                     */
+    uint64_t by_status[5];     /* terminals per status                                        */
+    uint64_t fp_collisions;
+    uint64_t flags;            /* DSM_REACH_F_*                                               */
+    uint64_t reserved;         /* zero                                                        */
+} dsm_reach_info;
+typedef struct dsm_reach_terminal {
+    uint64_t state;            /* the terminal state's id                                     */
+    dsm_sys_result res;        /* status with the dumped-node mask, dump_hash, final_hash;
+                                * rounds, msgs, instrs 0                                       */
+} dsm_reach_terminal;
+/* The host search, the plain reference (no GPU needed): a loop over the shared round step with an
+ * ordinary hash table.  trace [np][stride] packed u16, counts [np].  The output arrays are the
+ * caller's, max_states entries each (level_off: DSM_REACH_MAX_LEVELS + 1, terminals: term_cap),
+ * and each may be NULL: parents[id] and masks[id] (the round that first made the state; the
+ * root's are 0), fps[id], terminals in ascending state id.  Entries at and after info->states are
+ * unspecified. */
+int dsm_reach(int np, const uint16_t *trace, const uint32_t *counts, uint32_t stride,
+              const dsm_reach_opts *opts, dsm_reach_info *info, uint32_t *parents, uint8_t *masks,
+              uint64_t *fps, uint64_t *level_off, dsm_reach_terminal *terminals, uint64_t term_cap);
+/* The same on the GPU, for ONE system of the ctx's np and max_instr (d_trace [np][max_instr],
+ * d_counts [np], device).  SYNCHRONOUS: the size of each level decides the next launches, so the
+ * call waits for the device chunk by chunk; `stream` carries its launches.  The state store, the
+ * visited table and the chunk buffers are allocated for the call and freed before it returns
+ * (DSM_E_NOMEM with nothing leaked when they do not fit).  d_parents, d_masks, d_fps and
+ * d_terminals are device buffers (d_terminals 8-byte aligned), info and level_off host memory;
+ * each output may be NULL.  A bad argument is DSM_E_INVAL with nothing written. */
+int dsm_reach_device(dsm_ctx *ctx, const uint16_t *d_trace, const uint32_t *d_counts,
+                     const dsm_reach_opts *opts, dsm_reach_info *info, uint32_t *d_parents,
+                     uint8_t *d_masks, uint64_t *d_fps, uint64_t *level_off,
+                     dsm_reach_terminal *d_terminals, uint64_t term_cap, void *stream);
+/* The witness of state id (host only): the masks of the rounds from the root to it, root first.
+ * *n = their number (the state's depth); DSM_E_INVAL when it exceeds cap (nothing written) or the
+ * arrays are not a search's (a parent not below its child). */
+int dsm_reach_path(const uint32_t *parents, const uint8_t *masks, uint64_t id, uint8_t *out_masks,
+                   uint64_t cap, uint64_t *n);
+/* Apply n masks from the root with the shared step (host only).  dump[np] and final_state[np]
+ * (either may be NULL) receive the records, res (may be NULL) the full result: rounds = n, msgs
+ * and instrs as handled and issued, and the status of the state reached (DSM_ROUND_LIMIT where it
+ * is not terminal).  A mask that is empty or no subset of the enabled set -- any mask after an
+ * error status -- is DSM_E_INVAL. */
+int dsm_reach_replay(int np, const uint16_t *trace, const uint32_t *counts, uint32_t stride,
+                     uint32_t inbox_limit, const uint8_t *masks, uint64_t n, dsm_node_state *dump,
+                     dsm_node_state *final_state, dsm_sys_result *res);
+/* One system into a host census: the update dsm_census_results loops over (header systems + 1;
+ * the key's count + 1 and first = min(first, sys_id), or dropped + 1 when the table is full).
+ * The terminals of a search are grouped with it: key dsm_outcome_key(kind, &terminal.res), id the
+ * terminal's state, so count is the terminal states with the key and first the lowest of them. */
+int dsm_census_insert(uint64_t *census, uint32_t cap, uint64_t key, uint64_t sys_id);
 
 /* ---- multi-GPU group: RCCL over xGMI --------------------------------------- *
  * Systems are independent, so an ensemble shards over GPUs with no data-path exchange; the
