@@ -89,6 +89,12 @@
  *   --reach-states N   at most N states (default 4194304); a level that would pass N is dropped
  *   --reach-depth D    no level deeper than D (default 0: none)
  *   --reach-inbox L    inbox limit 1..16 (default 16)
+ *   --reach-prob T[,T...]  the exact probability of every outcome under the seeded schedules'
+ *                    threshold T (1..65536, at most 16 of them; dsm_reach_dist_device): every
+ *                    `outcome k:` line gains ` p[0xT] 0.dddddddddddddddddd` per threshold (18
+ *                    digits, rounded down), and after them one line per threshold,
+ *                        prob 0xT: deadlocked P completed P ring_overflow P assert_failed P lost P escaped P residual P rounds R
+ *                    Without it --reach prints exactly what it printed before.
  *                    With --reach, --explore-kind takes dumps or final; --explore-dir D replays
  *                    each outcome's first terminal state's witness on the host and writes
  *                    D/outcome_<k>/core_<n>_output.txt for the dumped nodes and
@@ -115,7 +121,8 @@ static void usage(const char *argv0) {
                     "          [--schedule SEED:THRESH] [--explore N [--explore-dir DIR]\n"
                     "          [--explore-kind dumps|final|full] [--check DIR]] [--audit]\n"
                     "          [--events FILE [--events-kind instr|msg|all]]\n"
-                    "          [--reach [--reach-states N] [--reach-depth D] [--reach-inbox L] [--explore-dir DIR]\n"
+                    "          [--reach [--reach-states N] [--reach-depth D] [--reach-inbox L] [--reach-prob T[,T...]]\n"
+                    "          [--explore-dir DIR]\n"
                     "          [--explore-kind dumps|final] [--check DIR]] <test_directory>\n", argv0);
 }
 
@@ -389,13 +396,21 @@ fail:
     return code;
 }
 
+/* mass / 2^63 in 18 decimal digits, rounded down */
+static void print_mass(uint64_t mass) {
+    const unsigned __int128 v = ((unsigned __int128)mass * 1000000000000000000ull) >> 63;
+    printf("%llu.%018llu", (unsigned long long)(v / 1000000000000000000ull), (unsigned long long)(v % 1000000000000000000ull));
+}
+
 /* --reach: every state the system can reach under the schedule model (dsm_reach_device), the
  * terminal states grouped by outcome on the host (dsm_census_insert).  Returns the process exit
  * code. */
 static int reach(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces, const uint32_t *counts,
                  unsigned long long max_states, uint32_t max_depth, uint32_t inbox, int kind, const char *out_dir,
-                 const char *check_dir) {
+                 const char *check_dir, const uint32_t *prob_t, uint32_t n_prob) {
     const size_t tr_bytes = (size_t)np * stride * sizeof(uint16_t);
+    uint64_t *d_tmass = NULL, *tmass = NULL, *omass = NULL;
+    dsm_dist_info dinfo[DSM_DIST_MAX_THRESH];
     const uint64_t term_cap = max_states < (DSM_CENSUS_MAX_CAP / 2) ? max_states : (DSM_CENSUS_MAX_CAP / 2);
     uint32_t cap = DSM_CENSUS_MIN_CAP;
     uint16_t *d_tr = NULL;
@@ -434,6 +449,17 @@ static int reach(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces, 
     what = "dsm_reach_device";
     if ((rc = dsm_reach_device(ctx, d_tr, d_cn, &opts, &info, d_par, d_msk, NULL, NULL, d_term, term_cap, NULL))) goto fail;
     if (info.terminals > term_cap) { what = "too many terminal states for one census"; goto fail; }
+    if (n_prob) {                                       /* the same search again, then the rounds */
+        dsm_reach_info again;
+        const size_t tm_words = (size_t)n_prob * (size_t)term_cap;
+        what = "device memory";
+        if (hipMalloc((void **)&d_tmass, tm_words * sizeof(uint64_t)) != hipSuccess) goto fail;
+        what = "dsm_reach_dist_device";
+        if ((rc = dsm_reach_dist_device(ctx, d_tr, d_cn, &opts, prob_t, n_prob, 0, &again, dinfo, d_term, d_tmass, term_cap,
+                                        NULL, NULL)))
+            goto fail;
+        if (again.states != info.states || again.terminals != info.terminals) { rc = DSM_E_STATE; goto fail; }
+    }
     while (cap < 2 * info.terminals) cap <<= 1;
     what = "out of memory";
     par = (uint32_t *)malloc((size_t)info.states * sizeof(uint32_t));
@@ -443,6 +469,13 @@ static int reach(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces, 
     cen = (uint64_t *)calloc(DSM_CENSUS_WORDS(cap), sizeof(uint64_t));
     outc = (dsm_outcome *)malloc((size_t)cap * sizeof(dsm_outcome));
     if (!par || !msk || !path || !term || !cen || !outc) goto fail;
+    if (n_prob) {
+        tmass = (uint64_t *)malloc((size_t)n_prob * (size_t)term_cap * sizeof(uint64_t));
+        if (!tmass) goto fail;
+        what = "read-back";
+        if (hipMemcpy(tmass, d_tmass, (size_t)n_prob * (size_t)term_cap * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
+            goto fail;
+    }
     what = "read-back";
     if (hipMemcpy(par, d_par, (size_t)info.states * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(msk, d_msk, (size_t)info.states, hipMemcpyDeviceToHost) != hipSuccess ||
@@ -461,6 +494,19 @@ static int reach(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces, 
     else printf("(exhaustive)\n");
     if (info.flags & DSM_REACH_F_COLLISION)
         printf("warning: %llu fingerprint collisions: the result is not exact\n", (unsigned long long)info.fp_collisions);
+    if (n_prob) {                                       /* the terminals' mass per outcome and threshold */
+        what = "out of memory";
+        omass = (uint64_t *)calloc((size_t)(k ? k : 1) * n_prob, sizeof(uint64_t));
+        if (!omass) goto fail;
+        for (uint64_t t = 0; t < info.terminals; ++t) {
+            const uint64_t key = dsm_outcome_key(kind, &term[t].res);
+            for (uint64_t o = 0; o < k; ++o)
+                if (outc[o].key == key) {
+                    for (uint32_t j = 0; j < n_prob; ++j) omass[o * n_prob + j] += tmass[(size_t)j * term_cap + t];
+                    break;
+                }
+        }
+    }
     if (out_dir && mkdir(out_dir, 0777) != 0 && errno != EEXIST) { what = out_dir; rc = DSM_E_IO; goto fail; }
     for (uint64_t o = 0; o < k; ++o) {
         const dsm_reach_terminal *t = NULL;             /* the outcome's first terminal: ids ascend */
@@ -472,9 +518,14 @@ static int reach(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces, 
         what = "census";
         if (!t || t->state != outc[o].first_sys) { rc = DSM_E_STATE; goto fail; }
         const uint32_t st = t->res.status & 0xFFu, dumped = t->res.status >> 8;
-        printf("outcome %llu: count %llu first %llu status %s dumped 0x%x dump_hash 0x%016llx\n",
+        printf("outcome %llu: count %llu first %llu status %s dumped 0x%x dump_hash 0x%016llx",
                (unsigned long long)o, (unsigned long long)outc[o].count, (unsigned long long)outc[o].first_sys,
                st < 5 ? status_names[st] : "?", dumped, (unsigned long long)t->res.dump_hash);
+        for (uint32_t j = 0; j < n_prob; ++j) {
+            printf(" p[0x%x] ", prob_t[j]);
+            print_mass(omass[o * n_prob + j]);
+        }
+        printf("\n");
         if (out_dir) {                                  /* the witness, replayed on the host */
             char dir[512], file[600];
             dsm_node_state dump[DSM_MAX_NP];
@@ -495,6 +546,17 @@ static int reach(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces, 
             if (fclose(f) != 0) goto fail;
             rc = DSM_OK;
         }
+    }
+    for (uint32_t j = 0; j < n_prob; ++j) {
+        const dsm_dist_info *d = &dinfo[j];
+        printf("prob 0x%x: deadlocked ", prob_t[j]); print_mass(d->by_status[DSM_DEADLOCKED]);
+        printf(" completed "); print_mass(d->by_status[DSM_COMPLETED]);
+        printf(" ring_overflow "); print_mass(d->by_status[DSM_RING_OVERFLOW]);
+        printf(" assert_failed "); print_mass(d->by_status[DSM_ASSERT_FAILED]);
+        printf(" lost "); print_mass(d->lost);
+        printf(" escaped "); print_mass(d->escaped);
+        printf(" residual "); print_mass(d->residual);
+        printf(" rounds %llu\n", (unsigned long long)d->rounds);
     }
     code = 0;
     if (check_dir) {
@@ -530,6 +592,8 @@ fail:
     if (d_par) (void)hipFree(d_par);
     if (d_msk) (void)hipFree(d_msk);
     if (d_term) (void)hipFree(d_term);
+    if (d_tmass) (void)hipFree(d_tmass);
+    free(tmass); free(omass);
     free(par); free(msk); free(path); free(term); free(cen); free(outc);
     return code;
 }
@@ -538,6 +602,7 @@ int main(int argc, char **argv) {
     int np = 4, device = 0, quiet = 0, audit = 0, do_reach = 0;
     long long reach_states = 1ll << 22, reach_depth = 0, reach_inbox = 16;
     int reach_opts = 0;
+    uint32_t prob_t[DSM_DIST_MAX_THRESH], n_prob = 0;
     uint32_t max_instr = DSM_REF_MAX_INSTR;
     const char *dir = NULL, *issue_file = NULL;
     unsigned long long sched_seed = 0;
@@ -565,6 +630,19 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--reach-states") && i + 1 < argc) { reach_states = atoll(argv[++i]); reach_opts = 1; }
         else if (!strcmp(argv[i], "--reach-depth") && i + 1 < argc) { reach_depth = atoll(argv[++i]); reach_opts = 1; }
         else if (!strcmp(argv[i], "--reach-inbox") && i + 1 < argc) { reach_inbox = atoll(argv[++i]); reach_opts = 1; }
+        else if (!strcmp(argv[i], "--reach-prob") && i + 1 < argc) {
+            const char *v = argv[++i];
+            reach_opts = 1;
+            for (n_prob = 0;;) {
+                char *end;
+                const unsigned long t = strtoul(v, &end, 0);
+                if (end == v || t < 1 || t > 65536 || n_prob == DSM_DIST_MAX_THRESH) { usage(argv[0]); return EXIT_FAILURE; }
+                prob_t[n_prob++] = (uint32_t)t;
+                if (*end == '\0') break;
+                if (*end != ',') { usage(argv[0]); return EXIT_FAILURE; }
+                v = end + 1;
+            }
+        }
         else if (!strcmp(argv[i], "--explore-dir") && i + 1 < argc) { explore_dir = argv[++i]; explore_opts = 1; }
         else if (!strcmp(argv[i], "--check") && i + 1 < argc) { check_dir = argv[++i]; explore_opts = 1; }
         else if (!strcmp(argv[i], "--events") && i + 1 < argc) events_file = argv[++i];
@@ -665,7 +743,7 @@ int main(int argc, char **argv) {
 
     if (do_reach) {
         const int code = reach(ctx, np, stride, traces, counts, (unsigned long long)reach_states, (uint32_t)reach_depth,
-                               (uint32_t)reach_inbox, explore_kind, explore_dir, check_dir);
+                               (uint32_t)reach_inbox, explore_kind, explore_dir, check_dir, prob_t, n_prob);
         dsm_close(ctx);
         free(traces);
         return code;

@@ -10,6 +10,7 @@
  *   dsm_audit.hip    coherence audit
  *   dsm_events.hip   event trace: the replay kernel, its host twin and the formatter
  *   dsm_reach.hip    exhaustive exploration: the search kernels, the host search, witnesses
+ *   dsm_dist.hip     outcome distribution: the edge list and the rounds, the host reference
  * Each kernel is launched from the unit that defines it.  Not part of the ABI.
  */
 #ifndef DSM_INTERNAL_H
@@ -121,6 +122,21 @@ extern "C" int dsm_debug_order_state(dsm_ctx *c, uint32_t *counts, uint32_t *lis
  * class -- count (with its scans), expand, insert, resolve (with its scan), settle -- and the
  * number of chunks of the last call, timed or not. */
 extern "C" int dsm_debug_reach_times(double *ms, uint64_t *chunks);
+
+/* Test-only view of the outcome distribution's edge list (not part of the ABI): the edges of
+ * dsm_reach_dist / dsm_reach_dist_device in their order (sources ascending, masks ascending) into
+ * host arrays of cap entries -- source id, target id (0xFFFFFFFF: no numbered state) and the
+ * probability index 8 (k - 1) + (m - 1).  *n = their number; DSM_E_INVAL when it exceeds cap. */
+extern "C" int dsm_debug_dist_edges(int np, const uint16_t *trace, const uint32_t *counts, uint32_t stride,
+                                    const dsm_reach_opts *opts, uint32_t *src, uint32_t *dst, uint8_t *pk, uint64_t cap,
+                                    uint64_t *n);
+extern "C" int dsm_debug_dist_edges_device(dsm_ctx *c, const uint16_t *d_trace, const uint32_t *d_counts,
+                                           const dsm_reach_opts *opts, uint32_t *src, uint32_t *dst, uint8_t *pk,
+                                           uint64_t cap, uint64_t *n, void *stream);
+/* Measurement-only view of the last dsm_reach_dist_device call that ran with DSM_DIST_TIMING=1 in
+ * the environment (tools/dist_time.py): milliseconds on the stream per phase -- search, rebuild
+ * (with classes and offsets), table, edges, push (all rounds of all thresholds). */
+extern "C" int dsm_debug_dist_times(double *ms);
 
 /* dsm_text.hip: called by dsm_close */
 void dsm_text_release(dsm_ctx *c);

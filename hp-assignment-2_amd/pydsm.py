@@ -183,7 +183,17 @@ def lib():
             "dsm_reach_path": (i32, [vp, vp, u64, vp, u64, ctypes.POINTER(u64)]),
             "dsm_reach_replay": (i32, [i32, vp, vp, u32, u32, vp, u64, vp, vp, vp]),
             "dsm_census_insert": (i32, [vp, u32, u64, u64]),
+            # ABI 5 (+dist): the outcome distribution
+            "dsm_sched_prob": (u64, [u32, u32, u32]),
+            "dsm_reach_dist": (i32, [i32, vp, vp, u32, ctypes.POINTER(ReachOpts), vp, u32, u32, vp, vp, vp, vp, u64, vp]),
+            "dsm_reach_dist_device": (i32, [vp, vp, vp, ctypes.POINTER(ReachOpts), vp, u32, u32, vp, vp, vp, vp, u64,
+                                            vp, vp]),
             # test-only (csrc/dsm_internal.h, not in include/dsm.h)
+            "dsm_debug_dist_edges": (i32, [i32, vp, vp, u32, ctypes.POINTER(ReachOpts), vp, vp, vp, u64,
+                                           ctypes.POINTER(u64)]),
+            "dsm_debug_dist_edges_device": (i32, [vp, vp, vp, ctypes.POINTER(ReachOpts), vp, vp, vp, u64,
+                                                  ctypes.POINTER(u64), vp]),
+            "dsm_debug_dist_times": (i32, [vp]),
             "dsm_debug_reach_times": (i32, [vp, ctypes.POINTER(u64)]),
             "dsm_debug_order_state": (i32, [vp, vp, vp, vp, u64, u64, vp, u32, ctypes.POINTER(u32),
                                             ctypes.POINTER(i32)]),
@@ -549,6 +559,94 @@ def reach_replay(np_, traces, counts, masks, inbox_limit=16):
     return dump, fin, res[0]
 
 
+# -- outcome distribution (ABI 5 +dist) -------------------------------------------------------
+DIST_ONE = 1 << 63                           # DSM_DIST_ONE: mass is in units of 2^-63
+DIST_MAX_THRESH, DIST_MAX_ROUNDS = 16, 65536
+DIST_F_RESIDUAL, DIST_F_ESCAPED, DIST_F_INEXACT = 1, 2, 4
+DIST_INFO_FIELDS = ("thresh", "rounds", "absorbed", "escaped", "residual", "lost", "st0", "st1", "st2", "st3",
+                    "st4", "edges", "missing_edges", "flags", "reserved0", "reserved1")
+
+
+def sched_prob(thresh, k, m):
+    """dsm_sched_prob: the probability, in units of 2^-64, that exactly m given nodes of k enabled
+    ones act in a round in which somebody acts; 0 outside 1 <= m <= k <= 8, 1 <= thresh <= 65536."""
+    if not all(0 <= x < 1 << 32 for x in (thresh, k, m)):
+        return 0
+    return int(lib().dsm_sched_prob(thresh, k, m))
+
+
+def dist_info_to_dict(v):
+    a = dict(zip(DIST_INFO_FIELDS, (int(x) for x in v)))
+    out = {k: a[k] for k in DIST_INFO_FIELDS if not (k.startswith("st") or k.startswith("reserved"))}
+    out["by_status"] = [a[f"st{i}"] for i in range(5)]
+    out["reserved"] = [a["reserved0"], a["reserved1"]]
+    return out
+
+
+def _dist_rounds(max_rounds):
+    return max_rounds if 0 < max_rounds <= DIST_MAX_ROUNDS else 4096
+
+
+def _dist_result(r, kind, dinfo, term_mass, round_mass):
+    """The dict of pydsm.reach plus "dist": per threshold the info, term_mass (uint64, one per
+    written terminal), round_mass (the running mass entering rounds 0 .. rounds) and the outcomes
+    of r["outcomes"], in that order, each with the mass of its terminals as a Python int and
+    p = mass / 2**63."""
+    terms = r["terminals"]
+    res = np.zeros(1, dtype=RESULT_DTYPE)
+    keys = []
+    for t in terms:
+        for f in RESULT_DTYPE.names:
+            res[0][f] = t[f]
+        keys.append(int(lib().dsm_outcome_key(kind, _ptr(res))))
+    r["dist"] = []
+    for j in range(len(dinfo)):
+        d = dist_info_to_dict(dinfo[j])
+        tm = term_mass[j, :len(terms)].copy()
+        by_key = {}
+        for k, v in zip(keys, tm):
+            by_key[k] = by_key.get(k, 0) + int(v)
+        d["term_mass"] = tm
+        d["round_mass"] = round_mass[j, :d["rounds"] + 1].copy()
+        d["outcomes"] = [{"key": int(o["key"]), "count": int(o["count"]), "first_sys": int(o["first_sys"]),
+                          "mass": by_key.get(int(o["key"]), 0), "p": by_key.get(int(o["key"]), 0) / DIST_ONE}
+                         for o in r["outcomes"]]
+        r["dist"].append(d)
+    return r
+
+
+def reach_dist(np_, traces, counts, thresh=(0x8000,), max_rounds=0, inbox_limit=16, kind=CENSUS_DUMPS,
+               max_states=1 << 22, max_depth=0, term_cap=None):
+    """dsm_reach_dist (the host reference; no GPU) of ONE system: the search of pydsm.reach, then
+    the exact distribution over its terminals under each threshold -> the dict of pydsm.reach
+    (without parents, masks, fps and level_off, which the call does not return) plus "dist"."""
+    traces = np.ascontiguousarray(traces, dtype=np.uint16)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+    assert traces.ndim == 2 and traces.shape[0] == np_ and counts.shape == (np_,)
+    kind = CENSUS_KINDS.get(kind, kind)
+    th = np.ascontiguousarray(thresh, dtype=np.uint32).reshape(-1)
+    opts = ReachOpts(inbox_limit, kind, max_states, max_depth, 0)
+    n = max_states if 0 < max_states <= 1 << 31 else 1
+    term_cap = min(n, 1 << 20) if term_cap is None else term_cap
+    R = _dist_rounds(max_rounds)
+    info = np.zeros(len(REACH_INFO_FIELDS), dtype=np.uint64)
+    dinfo = np.zeros((max(len(th), 1), len(DIST_INFO_FIELDS)), dtype=np.uint64)
+    terms = np.zeros(max(term_cap, 1), dtype=REACH_TERMINAL_DTYPE)
+    term_mass = np.zeros((max(len(th), 1), max(term_cap, 1)), dtype=np.uint64)
+    round_mass = np.zeros((max(len(th), 1), R + 1), dtype=np.uint64)
+    _check(lib().dsm_reach_dist(np_, _ptr(traces), _ptr(counts), traces.shape[1], ctypes.byref(opts), _ptr(th), len(th),
+                                max_rounds, _ptr(info), _ptr(dinfo), _ptr(terms), _ptr(term_mass), max(term_cap, 1),
+                                _ptr(round_mass)), "dsm_reach_dist")
+    return _dist_result(_reach_terminals_result(info, terms, kind), kind, dinfo, term_mass, round_mass)
+
+
+def _reach_terminals_result(info, terms, kind):
+    d = reach_info_to_dict(info)
+    nt = min(d["terminals"], len(terms))
+    table, cap = reach_census(terms[:nt], kind)
+    return {"info": d, "terminals": terms[:nt], "census": table, "census_cap": cap, "outcomes": census_sorted(table, cap)}
+
+
 class Group:
     """dsm_group: one RCCL communicator per GPU for the end-of-run all-reduces (ABI 5).
     Rank 0 makes the id (Group.unique_id()) and hands it to every rank out of band."""
@@ -801,6 +899,45 @@ class Engine:
         return _reach_result(info, d_par.cpu().numpy().view(np.uint32), d_msk.cpu().numpy(),
                              d_fps.cpu().numpy().view(np.uint64),
                              level_off, d_term.cpu().numpy().view(REACH_TERMINAL_DTYPE), kind)
+
+    def reach_dist_device(self, d_trace, d_counts, opts, thresh, max_rounds, rinfo, dinfo, d_terminals, d_term_mass,
+                          term_cap, round_mass, stream=0):
+        """dsm_reach_dist_device: device pointers or tensors for the trace, counts, terminals and
+        term_mass; thresh (uint32), rinfo, dinfo and round_mass numpy arrays (host); each output
+        may be None.  Synchronous."""
+        n = 0 if thresh is None else len(thresh)
+        return lib().dsm_reach_dist_device(self.ctx, _dptr(d_trace), _dptr(d_counts), ctypes.byref(opts), _ptr(thresh), n,
+                                           max_rounds, _ptr(rinfo), _ptr(dinfo), _dptr(d_terminals), _dptr(d_term_mass),
+                                           term_cap, _ptr(round_mass), ctypes.c_void_p(stream))
+
+    def reach_dist(self, traces, counts, thresh=(0x8000,), max_rounds=0, inbox_limit=16, kind=CENSUS_DUMPS,
+                   max_states=1 << 22, max_depth=0, chunk=0, term_cap=None):
+        """The exact distribution over the terminals of ONE system's reach graph under each
+        threshold, on the GPU -> the dict of pydsm.reach_dist."""
+        import torch
+        tr, cn = np.array(traces, dtype=np.uint16), np.array(counts, dtype=np.uint32)
+        if tr.shape != (self.np, self.max_instr) or cn.shape != (self.np,):
+            raise DsmError(E_INVAL, "reach_dist: one system of the engine's np and max_instr")
+        kind = CENSUS_KINDS.get(kind, kind)
+        th = np.ascontiguousarray(thresh, dtype=np.uint32).reshape(-1)
+        dev = torch.device("cuda", self.device)
+        d_tr = torch.from_numpy(tr.view(np.int16).reshape(-1)).to(dev)
+        d_cn = torch.from_numpy(cn.view(np.int32)).to(dev)
+        n = max_states if 0 < max_states <= 1 << 31 else 1
+        term_cap = max(min(n, 1 << 20) if term_cap is None else term_cap, 1)
+        R, nth = _dist_rounds(max_rounds), max(len(th), 1)
+        d_term = torch.zeros(5 * term_cap, dtype=torch.int64, device=dev)
+        d_tm = torch.zeros(nth * term_cap, dtype=torch.int64, device=dev)
+        info = np.zeros(len(REACH_INFO_FIELDS), dtype=np.uint64)
+        dinfo = np.zeros((nth, len(DIST_INFO_FIELDS)), dtype=np.uint64)
+        round_mass = np.zeros((nth, R + 1), dtype=np.uint64)
+        opts = ReachOpts(inbox_limit, kind, max_states, max_depth, chunk)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _check(self.reach_dist_device(d_tr, d_cn, opts, th, max_rounds, info, dinfo, d_term, d_tm, term_cap, round_mass, st),
+               "dsm_reach_dist_device")
+        terms = d_term.cpu().numpy().view(REACH_TERMINAL_DTYPE)
+        term_mass = d_tm.cpu().numpy().view(np.uint64).reshape(nth, term_cap)
+        return _dist_result(_reach_terminals_result(info, terms, kind), kind, dinfo, term_mass, round_mass)
 
     def explore(self, traces, counts, k, seed, thresh=0x8000, kind=CENSUS_DUMPS, audit=False):
         """k seeded interleavings of ONE system (traces [np, max_instr] u16, counts [np]) in

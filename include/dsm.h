@@ -54,7 +54,9 @@ extern "C" {
                              5 (+events): additive -- the event trace (dsm_trace_events*,
                                 dsm_event_trace_hash, dsm_format_event_trace) likewise;
                              5 (+reach): additive -- the exhaustive exploration (dsm_reach*,
-                                dsm_census_insert) likewise */
+                                dsm_census_insert) likewise;
+                             5 (+dist): additive -- the outcome distribution (dsm_sched_prob,
+                                dsm_reach_dist*) likewise */
 
 #define DSM_MAX_NP 8             /* bitVector is one byte (README.md:51)                  */
 #define DSM_CACHE_SIZE 4         /* CACHE_SIZE      assignment.c:10                        */
@@ -729,6 +731,78 @@ int dsm_reach_replay(int np, const uint16_t *trace, const uint32_t *counts, uint
  * The terminals of a search are grouped with it: key dsm_outcome_key(kind, &terminal.res), id the
  * terminal's state, so count is the terminal states with the key and first the lowest of them. */
 int dsm_census_insert(uint64_t *census, uint32_t cap, uint64_t key, uint64_t sys_id);
+
+/* ---- outcome distribution: the exact probabilities behind the seeded schedules -------------- *
+ * The reach graph is the Markov chain dsm_set_schedule samples: under threshold t every node of
+ * the enabled set A(s) acts, independently, with probability t / 65536 in each round.  The round
+ * in which nobody acts leaves the state as it is, so it is conditioned away: from a running state
+ * with k = |A| the successor by mask M, m = popcount(M), is taken with probability
+ *   t^m q^(k-m) / (65536^k - q^k),   q = 65536 - t.
+ * Mass is a uint64_t in units of 2^-63; the root starts with DSM_DIST_ONE.  No floating point.
+ *
+ * dsm_sched_prob(t, k, m) = min(2^64 - 1, floor(2^64 t^m q^(k-m) / (65536^k - q^k))) for
+ * 1 <= m <= k <= 8 and 1 <= t <= 65536, in exact integer arithmetic; 0 outside that domain.
+ * t = 65536 is lock-step: only m = k carries mass.
+ *
+ * One round: every running state u with mass pi(u) > 0 gives each successor v by mask M
+ * umul64hi(pi(u), dsm_sched_prob(t, k, popcount(M))) (the high 64 bits of the 128-bit product);
+ * contributions of several masks and several parents to one v add.  A terminal state keeps what
+ * arrives (absorbed).  In a truncated search (DSM_REACH_F_STATES / _DEPTH) the states of the last
+ * kept level were not expanded: those that are not terminal keep what arrives too (escaped).
+ * Rounds repeat until no running state holds mass, or max_rounds rounds were made (0 = 4096, at
+ * most DSM_DIST_MAX_ROUNDS); what is still running then is residual.  lost = DSM_DIST_ONE -
+ * absorbed - escaped - residual is the rounding loss: at most one unit per mass-carrying edge per
+ * round.  Every update is an integer addition, so the result does not depend on the order of
+ * summation: host and device agree bit for bit.
+ *
+ * An edge whose target's fingerprint is not among the numbered states carries its mass nowhere
+ * (into lost) and is counted in missing_edges: 0 for every sane run. */
+#define DSM_DIST_ONE (1ull << 63)
+#define DSM_DIST_MAX_THRESH 16u
+#define DSM_DIST_MAX_ROUNDS 65536u
+#define DSM_DIST_F_RESIDUAL 1u   /* residual != 0                                             */
+#define DSM_DIST_F_ESCAPED 2u    /* escaped != 0                                              */
+#define DSM_DIST_F_INEXACT 4u    /* DSM_REACH_F_COLLISION, or missing_edges != 0              */
+typedef struct dsm_dist_info {
+    uint64_t thresh;
+    uint64_t rounds;           /* rounds made                                                 */
+    uint64_t absorbed;         /* mass on terminal states                                     */
+    uint64_t escaped;          /* mass on unexpanded running states of a truncated search     */
+    uint64_t residual;         /* mass still running after max_rounds                         */
+    uint64_t lost;             /* rounding loss                                               */
+    uint64_t by_status[5];     /* absorbed mass per terminal status                           */
+    uint64_t edges;            /* successors of every expanded state, duplicates included     */
+    uint64_t missing_edges;
+    uint64_t flags;            /* DSM_DIST_F_*                                                */
+    uint64_t reserved[2];      /* zero                                                        */
+} dsm_dist_info;
+uint64_t dsm_sched_prob(uint32_t thresh, uint32_t k, uint32_t m);
+/* The host reference (no GPU needed): dsm_reach, then the edge list (source, target, k, m) in one
+ * pass of the shared round step over every expanded state, targets found by fingerprint, then
+ * the rounds, once per threshold (thresh[n_thresh], 1 <= n_thresh <= DSM_DIST_MAX_THRESH, each
+ * 1..65536).  rinfo and terminals are dsm_reach's.  term_mass[j * term_cap + i] is the mass of
+ * terminal i (the order of terminals: ascending state id) under thresh[j], written for
+ * i < min(term_cap, terminals); terminals past term_cap still count in the info.
+ * round_mass[j * (R + 1) + d], R = max_rounds (4096 for 0), is the running mass entering round d:
+ * DSM_DIST_ONE at d = 0 (0 where the root itself does not run: a search cut at one state leaves
+ * all mass escaped at once, in no round), 0 after the last round.  term_mass entries at and after
+ * min(term_cap, terminals) are not written.  Every output may be NULL. */
+int dsm_reach_dist(int np, const uint16_t *trace, const uint32_t *counts, uint32_t stride,
+                   const dsm_reach_opts *opts, const uint32_t *thresh, uint32_t n_thresh,
+                   uint32_t max_rounds, dsm_reach_info *rinfo, dsm_dist_info *dinfo,
+                   dsm_reach_terminal *terminals, uint64_t *term_mass, uint64_t term_cap,
+                   uint64_t *round_mass);
+/* The same on the GPU (dsm_reach_device's search, then dist_*_kernel).  d_terminals and
+ * d_term_mass are device buffers (8-byte aligned); thresh, rinfo, dinfo and round_mass host
+ * memory.  SYNCHRONOUS like dsm_reach_device; everything it allocates (the search's arrays, the
+ * rebuilt state store, the fingerprint table, the edge list, the mass vectors) is freed before
+ * it returns: DSM_E_NOMEM with nothing leaked when they do not fit.  A bad argument is
+ * DSM_E_INVAL with nothing written. */
+int dsm_reach_dist_device(dsm_ctx *ctx, const uint16_t *d_trace, const uint32_t *d_counts,
+                          const dsm_reach_opts *opts, const uint32_t *thresh, uint32_t n_thresh,
+                          uint32_t max_rounds, dsm_reach_info *rinfo, dsm_dist_info *dinfo,
+                          dsm_reach_terminal *d_terminals, uint64_t *d_term_mass, uint64_t term_cap,
+                          uint64_t *round_mass, void *stream);
 
 /* ---- multi-GPU group: RCCL over xGMI --------------------------------------- *
  * Systems are independent, so an ensemble shards over GPUs with no data-path exchange; the
