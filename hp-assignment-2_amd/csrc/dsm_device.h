@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dsm_hash.h"
+
 #define DEVI __device__ __forceinline__
 
 /* s_waitcnt vmcnt(0) with expcnt / lgkmcnt left open, as the raw immediate of the gfx9 encoding
@@ -33,17 +35,11 @@ DEVI uint32_t set2(uint32_t w, uint32_t i, uint32_t v) {
 }
 
 /* ---- hashing (definitions in DESIGN.md; pinned by tests) ----------------------------- */
-DEVI uint64_t fmix64(uint64_t z) {
-    z ^= z >> 33; z *= 0xff51afd7ed558ccdULL;
-    z ^= z >> 33; z *= 0xc4ceb9fe1a85ec53ULL;
-    z ^= z >> 33;
-    return z;
-}
+/* dsm_hash.h's, under the names the engine's kernels use */
+DEVI uint64_t fmix64(uint64_t z) { return hs_fmix64(z); }
 /* the node hash (dsm_host.c dsm_node_hash): from node_hash_seed, one step per record word wi */
-DEVI uint64_t node_hash_seed(uint32_t node) { return 0x9E3779B97F4A7C15ULL * (uint64_t)(node + 1); }
-DEVI uint64_t node_hash_step(uint64_t h, uint32_t w, int wi) {
-    return fmix64(h ^ ((uint64_t)w | ((uint64_t)wi << 32)));
-}
+DEVI uint64_t node_hash_seed(uint32_t node) { return hs_node_seed(node); }
+DEVI uint64_t node_hash_step(uint64_t h, uint32_t w, int wi) { return hs_node_step(h, w, wi); }
 /* the chain over a 32-byte dsm_sys_result (dsm_host.c dsm_result_digest, dsm_outcome_key): its
  * first 16 bytes `a` as two steps, then one step per 64-bit hash */
 DEVI uint64_t res_hash_step(uint64_t h, uint64_t x) { return fmix64(h ^ x); }

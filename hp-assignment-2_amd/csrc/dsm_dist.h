@@ -23,14 +23,10 @@
 DSM_HD uint32_t dist_pidx(uint32_t k, uint32_t m) { return (k - 1u) * 8u + (m - 1u); }
 
 template <int NP>
-DSM_HD uint32_t dist_class(const EvMem &m, uint32_t enabled, bool expanded) {
+DSM_HD uint32_t dist_class(const StMem &m, uint32_t enabled, bool expanded) {
     const uint32_t st = m.ld(RS_STATUS(NP));
     if (st == 0u && enabled != 0u) return expanded ? DIST_RUNNING : DIST_ESCAPED;
-    uint32_t mask = 0;
-    for (uint32_t n = 0; n < (uint32_t)NP; ++n)
-        if ((m.ld(16u * n + 15u) >> 9) & 1u) mask |= 1u << n;
-    const uint32_t status = st ? st : (mask == (1u << NP) - 1u ? (uint32_t)DSM_COMPLETED : (uint32_t)DSM_DEADLOCKED);
-    return DIST_TERMINAL + (status & 7u);
+    return DIST_TERMINAL + (rs_end_status<NP>(m) & 7u);
 }
 
 /* Host only from here on.  256-bit unsigned integers in eight 32-bit limbs, as far as the long

@@ -12,8 +12,8 @@
  *                             the micro-op table in LDS
  *   dist_class_kernel<NP>     one lane per state: its class byte (running / escaped / terminal +
  *                             status), its enabled set A and its successor count 2^|A| - 1 (0
- *                             unless running); an exclusive scan of the counts gives every
- *                             state's first edge
+ *                             unless running); an exclusive scan of the counts (dsm_reach.hip's,
+ *                             dsm_exscan_launch) gives every state's first edge
  *   dist_table_kernel         fingerprint -> id: open addressing, compare-and-swap on the key;
  *                             the fingerprints of a search are distinct, so the winner stores id
  *   dist_edges_kernel<NP>     per chunk of edges, one lane per edge: the source by a search of
@@ -45,18 +45,11 @@
 #include <unordered_map>
 #include <vector>
 
-#include "dsm_internal.h"
-#include "dsm_reach.h"
+#include "dsm_reach_dev.h"
 #include "dsm_dist.h"
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int RT = 256;                      /* threads per workgroup, every kernel here */
-constexpr uint32_t DEFAULT_CHUNK = 1u << 18; /* as the search's */
-constexpr uint32_t MAX_CHUNK = 1u << 24;
-constexpr unsigned MAX_GRID = 1u << 16;      /* workgroups of a grid-stride kernel */
 constexpr uint32_t ROUND_BATCH = 8;          /* rounds between two reads of the running mass */
 
 struct DistCtr {                             /* device counters of one call */
@@ -70,80 +63,11 @@ struct EdgeDump {
     uint64_t cap, n;
 };
 
-/* ---- exclusive scan of n uint32 into n + 1 uint64 (out[n] = the total): dsm_reach.hip's ------ */
-constexpr int SCAN_ITEMS = 8;
-constexpr int SCAN_TILE = RT * SCAN_ITEMS;
-
-__device__ __forceinline__ u64 block_exscan(u64 v, u64 *s_buf, u64 *total) {
-    const uint32_t t = threadIdx.x;
-    s_buf[t] = v;
-    __syncthreads();
-    for (uint32_t off = 1; off < (uint32_t)RT; off <<= 1) {
-        const u64 add = t >= off ? s_buf[t - off] : 0;
-        __syncthreads();
-        s_buf[t] += add;
-        __syncthreads();
-    }
-    const u64 incl = s_buf[t];
-    *total = s_buf[RT - 1];
-    __syncthreads();
-    return incl - v;
-}
-
-__device__ __forceinline__ u64 tile_items(const uint32_t *in, u64 n, u64 first, uint32_t v[SCAN_ITEMS]) {
-    u64 s = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; ++k) {
-        const u64 i = first + k;
-        v[k] = i < n ? in[i] : 0u;
-        s += v[k];
-    }
-    return s;
-}
-
-__global__ void __launch_bounds__(RT) dist_scan_sums_kernel(const uint32_t *in, u64 n, u64 *bsum) {
-    __shared__ u64 s_buf[RT];
-    uint32_t v[SCAN_ITEMS];
-    const u64 s = tile_items(in, n, (u64)blockIdx.x * SCAN_TILE + (u64)threadIdx.x * SCAN_ITEMS, v);
-    u64 total;
-    (void)block_exscan(s, s_buf, &total);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
-}
-
-__global__ void __launch_bounds__(RT) dist_scan_top_kernel(u64 *bsum, u64 nb) {
-    __shared__ u64 s_buf[RT];
-    u64 carry = 0;
-    for (u64 base = 0; base < nb; base += RT) {
-        const u64 i = base + threadIdx.x;
-        const u64 v = i < nb ? bsum[i] : 0;
-        u64 total;
-        const u64 ex = block_exscan(v, s_buf, &total);
-        if (i < nb) bsum[i] = carry + ex;
-        carry += total;
-    }
-}
-
-__global__ void __launch_bounds__(RT) dist_scan_final_kernel(const uint32_t *in, u64 n, const u64 *bsum, u64 *out) {
-    __shared__ u64 s_buf[RT];
-    uint32_t v[SCAN_ITEMS];
-    const u64 first = (u64)blockIdx.x * SCAN_TILE + (u64)threadIdx.x * SCAN_ITEMS;
-    const u64 s = tile_items(in, n, first, v);
-    u64 total;
-    u64 run = bsum[blockIdx.x] + block_exscan(s, s_buf, &total);
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; ++k) {
-        const u64 i = first + k;
-        if (i < n) out[i] = run;
-        run += v[k];
-    }
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) out[n] = bsum[blockIdx.x] + total;
-}
-
 /* ---- the state store ------------------------------------------------------------------------ */
 template <int NP>
 __global__ void dist_root_kernel(uint32_t *store, u64 n) {
     if (blockIdx.x || threadIdx.x) return;
-    const EvMem m = {store, (size_t)n};
+    const StMem m = {store, (size_t)n};
     rs_init<NP>(m);
 }
 
@@ -152,27 +76,18 @@ struct RebuildArgs {
     u64 n, lo, cnt;               /* states [lo, lo + cnt) of n: one level */
     const uint32_t *parents;
     const uint8_t *masks;
-    const uint16_t *trace;
-    const uint32_t *counts;
-    const uint32_t *table;
-    uint32_t stride, L;
+    StepArgs step;
 };
 
 template <int NP>
 __global__ void __launch_bounds__(RT) dist_rebuild_kernel(const RebuildArgs a) {
     __shared__ uint32_t s_tab[DT_TABLE_WORDS];
-    for (uint32_t i = threadIdx.x; i < DT_TABLE_WORDS; i += RT) s_tab[i] = a.table[i];
-    __syncthreads();
+    table_to_lds(s_tab, a.step.table);
     for (u64 i = (u64)blockIdx.x * RT + threadIdx.x; i < a.cnt; i += (u64)gridDim.x * RT) {
         const u64 id = a.lo + i;
         const u64 par = a.parents[id];
         if (par >= a.lo) continue;                                /* no search's arrays: nothing is read past the level */
-        uint32_t *dst = a.store + id;
-        const uint32_t *src = a.store + par;
-        for (uint32_t w = 0; w < RS_WORDS(NP); ++w) dst[(size_t)w * a.n] = src[(size_t)w * a.n];
-        const EvMem m = {dst, (size_t)a.n};
-        RsStat st = {0u, 0u};
-        rs_round<NP>(m, s_tab, a.trace, a.counts, a.stride, a.masks[id], a.L, &st, nullptr);
+        (void)step_from<NP>(a.store + par, (size_t)a.n, a.store + id, (size_t)a.n, a.masks[id], s_tab, a.step);
     }
 }
 
@@ -182,7 +97,7 @@ template <int NP>
 __global__ void __launch_bounds__(RT) dist_class_kernel(const uint32_t *store, u64 n, u64 n_exp, const uint32_t *counts,
                                                         uint32_t stride, uint8_t *cls, uint8_t *A, uint32_t *cnt) {
     for (u64 id = (u64)blockIdx.x * RT + threadIdx.x; id < n; id += (u64)gridDim.x * RT) {
-        const EvMem m = {const_cast<uint32_t *>(store) + id, (size_t)n};
+        const StMem m = {const_cast<uint32_t *>(store) + id, (size_t)n};
         const uint32_t a = rs_enabled<NP>(m, counts, stride);
         const uint32_t c = dist_class<NP>(m, a, id < n_exp);
         cls[id] = (uint8_t)c;
@@ -232,10 +147,7 @@ struct EdgeArgs {
     u64 e0, cnt;                  /* edges [e0, e0 + cnt) */
     uint32_t *cand;               /* RS_WORK(np) rows of cs words */
     u64 cs;
-    const uint16_t *trace;
-    const uint32_t *counts;
-    const uint32_t *table;
-    uint32_t stride, L;
+    StepArgs step;
     const u64 *keys;
     const uint32_t *vals;
     u64 slots;
@@ -247,29 +159,19 @@ struct EdgeArgs {
 template <int NP>
 __global__ void __launch_bounds__(RT) dist_edges_kernel(const EdgeArgs a) {
     __shared__ uint32_t s_tab[DT_TABLE_WORDS];
-    for (uint32_t i = threadIdx.x; i < DT_TABLE_WORDS; i += RT) s_tab[i] = a.table[i];
-    __syncthreads();
+    table_to_lds(s_tab, a.step.table);
     const u64 j = (u64)blockIdx.x * RT + threadIdx.x;
     if (j >= a.cnt) return;
     const u64 g = a.e0 + j;
-    u64 lo = 0, hi = a.n;                     /* the largest p with offs[p] <= g */
-    while (hi - lo > 1) {
-        const u64 mid = lo + (hi - lo) / 2;
-        if (a.offs[mid] <= g) lo = mid; else hi = mid;
-    }
-    const uint32_t en = a.A[lo];
-    const uint32_t mask = rs_deposit((uint32_t)(g - a.offs[lo]) + 1u, en);
-    const uint32_t *src = a.store + lo;
-    uint32_t *dst = a.cand + j;
-    for (uint32_t i = 0; i < RS_WORDS(NP); ++i) dst[(size_t)i * a.cs] = src[(size_t)i * a.n];
-    const EvMem m = {dst, (size_t)a.cs};
-    RsStat st = {0u, 0u};
-    rs_round<NP>(m, s_tab, a.trace, a.counts, a.stride, mask, a.L, &st, nullptr);
+    u64 lo;
+    uint32_t mask;
+    const StMem m = successor<NP>(a.store, (size_t)a.n, a.n, a.offs, a.A, g, a.cand + j, (size_t)a.cs, s_tab, a.step, &lo,
+                                  &mask);
     const uint32_t to = table_find(a.keys, a.vals, a.slots, rs_fingerprint<NP>(m));
     if (to == DIST_MISSING) __hip_atomic_fetch_add(&a.ctr->missing, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     a.esrc[g] = (uint32_t)lo;
     a.edst[g] = to;
-    a.epk[g] = (uint8_t)dist_pidx((uint32_t)__builtin_popcount(en), (uint32_t)__builtin_popcount(mask));
+    a.epk[g] = (uint8_t)dist_pidx((uint32_t)__builtin_popcount(a.A[lo]), (uint32_t)__builtin_popcount(mask));
 }
 
 /* ---- the rounds ----------------------------------------------------------------------------- */
@@ -335,24 +237,6 @@ __global__ void __launch_bounds__(RT) dist_gather_kernel(const u64 *sink, u64 n,
     }
 }
 
-/* a device buffer freed when the call returns, whichever way */
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes) {
-        if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) { p = nullptr; (void)hipGetLastError(); return DSM_E_NOMEM; }
-        return DSM_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; }
-    template <typename T> T *as() const { return static_cast<T *>(p); }
-};
-
-unsigned grid_of(u64 n) { return (unsigned)((n + RT - 1) / RT); }
-unsigned grid_cap(u64 n) {
-    const u64 g = (n + RT - 1) / RT;
-    return (unsigned)(g < 1 ? 1 : g > MAX_GRID ? MAX_GRID : g);
-}
-
 /* Measurement only (DSM_DIST_TIMING=1 in the environment at the call; tools/dist_time.py): device
  * events between the phases of the call, which follow each other on the stream -- search,
  * rebuild (with the class kernel and the scan), table, edges, push (every round of every
@@ -384,15 +268,6 @@ struct PhaseTimer {
         (void)hipGetLastError();
     }
 };
-
-/* dsm_reach's own conditions on its options, checked here before anything is allocated */
-int opts_ok(const dsm_reach_opts *o) {
-    if (!o || o->inbox_limit > RS_RING) return 0;
-    if (o->kind != DSM_CENSUS_DUMPS && o->kind != DSM_CENSUS_FINAL) return 0;
-    if (o->max_states == 0 || o->max_states > DSM_REACH_MAX_STATES) return 0;
-    if (o->max_depth >= DSM_REACH_MAX_LEVELS || o->chunk > MAX_CHUNK) return 0;
-    return 1;
-}
 
 int args_ok(const uint32_t *thresh, uint32_t n_thresh, uint32_t max_rounds, uint32_t *R) {
     if (!thresh || n_thresh < 1 || n_thresh > DSM_DIST_MAX_THRESH || max_rounds > DSM_DIST_MAX_ROUNDS) return 0;
@@ -427,14 +302,13 @@ void fill_info(dsm_dist_info *d, uint32_t thresh, u64 rounds, const u64 acc[6], 
 
 template <int NP>
 int dist_device(dsm_ctx *c, const uint16_t *d_trace, const uint32_t *d_counts, const dsm_reach_opts *o,
-                const uint32_t *thresh, uint32_t n_thresh, uint32_t R, dsm_reach_info *rinfo, dsm_dist_info *dinfo,
+                uint32_t L, const uint32_t *thresh, uint32_t n_thresh, uint32_t R, dsm_reach_info *rinfo, dsm_dist_info *dinfo,
                 dsm_reach_terminal *d_terminals, u64 *d_term_mass, u64 term_cap, uint64_t *round_mass, EdgeDump *dump,
                 hipStream_t st) {
     const u64 cap = o->max_states;
     const u64 chunk = o->chunk ? o->chunk : DEFAULT_CHUNK;
-    const uint32_t L = o->inbox_limit ? o->inbox_limit : RS_RING;
     const uint32_t stride = c->cfg.max_instr;
-    const uint32_t *table = reinterpret_cast<const uint32_t *>(c->d_table);
+    const StepArgs step = {d_trace, d_counts, reinterpret_cast<const uint32_t *>(c->d_table), stride, L};
     PhaseTimer tm(st);
     int rc;
 
@@ -455,7 +329,7 @@ int dist_device(dsm_ctx *c, const uint16_t *d_trace, const uint32_t *d_counts, c
 
     /* 2. the state store, the classes, the edge offsets */
     DevBuf b_store, b_cls, b_A, b_cnt, b_offs, b_bsum, b_ctr;
-    const u64 nb = (n + SCAN_TILE - 1) / SCAN_TILE;
+    const u64 nb = (n + DSM_EXSCAN_TILE - 1) / DSM_EXSCAN_TILE;
     if ((rc = b_store.alloc((size_t)RS_WORK(NP) * n * 4)) || (rc = b_cls.alloc(n)) || (rc = b_A.alloc(n)) ||
         (rc = b_cnt.alloc(n * 4)) || (rc = b_offs.alloc((n + 1) * 8)) || (rc = b_bsum.alloc(nb * 8)) ||
         (rc = b_ctr.alloc(sizeof(DistCtr))))
@@ -465,16 +339,12 @@ int dist_device(dsm_ctx *c, const uint16_t *d_trace, const uint32_t *d_counts, c
     for (u64 d = 1; d < ri.levels; ++d) {
         RebuildArgs ra;
         ra.store = b_store.as<uint32_t>(); ra.n = n; ra.lo = loff[d]; ra.cnt = loff[d + 1] - loff[d];
-        ra.parents = b_par.as<uint32_t>(); ra.masks = b_msk.as<uint8_t>(); ra.trace = d_trace; ra.counts = d_counts;
-        ra.table = table; ra.stride = stride; ra.L = L;
+        ra.parents = b_par.as<uint32_t>(); ra.masks = b_msk.as<uint8_t>(); ra.step = step;
         hipLaunchKernelGGL(dist_rebuild_kernel<NP>, dim3(grid_cap(ra.cnt)), dim3(RT), 0, st, ra);
     }
     hipLaunchKernelGGL(dist_class_kernel<NP>, dim3(grid_cap(n)), dim3(RT), 0, st, b_store.as<uint32_t>(), n, n_exp, d_counts,
                        stride, b_cls.as<uint8_t>(), b_A.as<uint8_t>(), b_cnt.as<uint32_t>());
-    hipLaunchKernelGGL(dist_scan_sums_kernel, dim3((unsigned)nb), dim3(RT), 0, st, b_cnt.as<uint32_t>(), n, b_bsum.as<u64>());
-    hipLaunchKernelGGL(dist_scan_top_kernel, dim3(1), dim3(RT), 0, st, b_bsum.as<u64>(), nb);
-    hipLaunchKernelGGL(dist_scan_final_kernel, dim3((unsigned)nb), dim3(RT), 0, st, b_cnt.as<uint32_t>(), n, b_bsum.as<u64>(),
-                       b_offs.as<u64>());
+    dsm_exscan_launch(b_cnt.as<uint32_t>(), n, b_bsum.as<u64>(), b_offs.as<u64>(), st);
     u64 n_edges = 0;
     HIPCK(hipMemcpyAsync(&n_edges, b_offs.as<u64>() + n, 8, hipMemcpyDeviceToHost, st));
     HIPCK(hipStreamSynchronize(st));
@@ -501,7 +371,7 @@ int dist_device(dsm_ctx *c, const uint16_t *d_trace, const uint32_t *d_counts, c
         EdgeArgs ea;
         ea.store = b_store.as<uint32_t>(); ea.n = n; ea.offs = b_offs.as<u64>(); ea.A = b_A.as<uint8_t>();
         ea.e0 = e0; ea.cnt = n_edges - e0 < cs ? n_edges - e0 : cs; ea.cand = b_cand.as<uint32_t>(); ea.cs = cs;
-        ea.trace = d_trace; ea.counts = d_counts; ea.table = table; ea.stride = stride; ea.L = L;
+        ea.step = step;
         ea.keys = b_keys.as<u64>(); ea.vals = b_vals.as<uint32_t>(); ea.slots = slots;
         ea.esrc = b_esrc.as<uint32_t>(); ea.edst = b_edst.as<uint32_t>(); ea.epk = b_epk.as<uint8_t>();
         ea.ctr = b_ctr.as<DistCtr>();
@@ -597,11 +467,10 @@ struct HostBuf {
 
 template <int NP>
 int dist_host(const uint16_t *trace, const uint32_t *counts, uint32_t stride, const dsm_reach_opts *o,
-              const uint32_t *thresh, uint32_t n_thresh, uint32_t R, dsm_reach_info *rinfo, dsm_dist_info *dinfo,
+              uint32_t L, const uint32_t *thresh, uint32_t n_thresh, uint32_t R, dsm_reach_info *rinfo, dsm_dist_info *dinfo,
               dsm_reach_terminal *terminals, uint64_t *term_mass, uint64_t term_cap, uint64_t *round_mass, EdgeDump *dump) {
     constexpr uint32_t W = RS_WORDS(NP);
     const u64 cap = o->max_states;
-    const uint32_t L = o->inbox_limit ? o->inbox_limit : RS_RING;
     uint32_t tab[DT_TABLE_WORDS];
     if (dt_build(tab) > DT_ENTRIES) return DSM_E_INVAL;
     HostBuf<uint32_t> parents;
@@ -619,15 +488,14 @@ int dist_host(const uint16_t *trace, const uint32_t *counts, uint32_t stride, co
     std::vector<uint32_t> S((size_t)n * W);
     uint32_t tmp[RS_WORK(NP)];
     {
-        const EvMem m = {S.data(), 1};
+        const StMem m = {S.data(), 1};
         rs_init<NP>(m);
     }
     for (u64 id = 1; id < n; ++id) {
         if (parents.p[id] >= id) return DSM_E_STATE;
         memcpy(tmp, &S[(size_t)parents.p[id] * W], W * 4);
-        const EvMem m = {tmp, 1};
-        RsStat st = {0u, 0u};
-        rs_round<NP>(m, tab, trace, counts, stride, masks.p[id], L, &st, nullptr);
+        const StMem m = {tmp, 1};
+        (void)rs_round<NP>(m, tab, trace, counts, stride, masks.p[id], L, nullptr);
         memcpy(&S[(size_t)id * W], tmp, W * 4);
     }
     std::unordered_map<uint64_t, uint32_t> by_fp;
@@ -640,7 +508,7 @@ int dist_host(const uint16_t *trace, const uint32_t *counts, uint32_t stride, co
     std::vector<uint8_t> epk;
     u64 missing = 0;
     for (u64 id = 0; id < n; ++id) {
-        const EvMem s = {&S[(size_t)id * W], 1};
+        const StMem s = {&S[(size_t)id * W], 1};
         const uint32_t a = rs_enabled<NP>(s, counts, stride);
         cls[id] = (uint8_t)dist_class<NP>(s, a, id < n_exp);
         if (cls[id] != DIST_RUNNING) continue;
@@ -648,9 +516,8 @@ int dist_host(const uint16_t *trace, const uint32_t *counts, uint32_t stride, co
         for (uint32_t j = 1; j <= cnt; ++j) {
             const uint32_t mask = rs_deposit(j, a);
             memcpy(tmp, &S[(size_t)id * W], W * 4);
-            const EvMem m = {tmp, 1};
-            RsStat st = {0u, 0u};
-            rs_round<NP>(m, tab, trace, counts, stride, mask, L, &st, nullptr);
+            const StMem m = {tmp, 1};
+            (void)rs_round<NP>(m, tab, trace, counts, stride, mask, L, nullptr);
             const auto it = by_fp.find(rs_fingerprint<NP>(m));
             if (it == by_fp.end()) ++missing;
             esrc.push_back((uint32_t)id);
@@ -712,15 +579,15 @@ int dist_host(const uint16_t *trace, const uint32_t *counts, uint32_t stride, co
 int host_entry(int np, const uint16_t *trace, const uint32_t *counts, uint32_t stride, const dsm_reach_opts *opts,
                const uint32_t *thresh, uint32_t n_thresh, uint32_t max_rounds, dsm_reach_info *rinfo, dsm_dist_info *dinfo,
                dsm_reach_terminal *terminals, uint64_t *term_mass, uint64_t term_cap, uint64_t *round_mass, EdgeDump *dump) {
-    uint32_t R;
-    if ((np != 4 && np != 8) || !trace || !counts || stride == 0 || stride > DSM_MAX_INSTR || !opts_ok(opts) ||
+    uint32_t R, L;
+    if ((np != 4 && np != 8) || !trace || !counts || stride == 0 || stride > DSM_MAX_INSTR || !opts_ok(opts, &L) ||
         !args_ok(thresh, n_thresh, max_rounds, &R))
         return DSM_E_INVAL;
     try {
         if (np == 4)
-            return dist_host<4>(trace, counts, stride, opts, thresh, n_thresh, R, rinfo, dinfo, terminals, term_mass, term_cap,
+            return dist_host<4>(trace, counts, stride, opts, L, thresh, n_thresh, R, rinfo, dinfo, terminals, term_mass, term_cap,
                                 round_mass, dump);
-        return dist_host<8>(trace, counts, stride, opts, thresh, n_thresh, R, rinfo, dinfo, terminals, term_mass, term_cap,
+        return dist_host<8>(trace, counts, stride, opts, L, thresh, n_thresh, R, rinfo, dinfo, terminals, term_mass, term_cap,
                             round_mass, dump);
     } catch (const std::bad_alloc &) {
         return DSM_E_NOMEM;
@@ -731,16 +598,16 @@ int device_entry(dsm_ctx *c, const uint16_t *d_trace, const uint32_t *d_counts, 
                  const uint32_t *thresh, uint32_t n_thresh, uint32_t max_rounds, dsm_reach_info *rinfo, dsm_dist_info *dinfo,
                  dsm_reach_terminal *d_terminals, uint64_t *d_term_mass, uint64_t term_cap, uint64_t *round_mass,
                  EdgeDump *dump, void *stream) {
-    uint32_t R;
-    if (!c || !d_trace || !d_counts || !opts_ok(opts) || !args_ok(thresh, n_thresh, max_rounds, &R) ||
+    uint32_t R, L;
+    if (!c || !d_trace || !d_counts || !opts_ok(opts, &L) || !args_ok(thresh, n_thresh, max_rounds, &R) ||
         ((uintptr_t)d_term_mass & 7u) || ((uintptr_t)d_terminals & 7u))
         return DSM_E_INVAL;
     HIPCK(hipSetDevice(c->device));
     try {
         if (c->cfg.np == 4)
-            return dist_device<4>(c, d_trace, d_counts, opts, thresh, n_thresh, R, rinfo, dinfo, d_terminals, (u64 *)d_term_mass,
+            return dist_device<4>(c, d_trace, d_counts, opts, L, thresh, n_thresh, R, rinfo, dinfo, d_terminals, (u64 *)d_term_mass,
                                   term_cap, round_mass, dump, (hipStream_t)stream);
-        return dist_device<8>(c, d_trace, d_counts, opts, thresh, n_thresh, R, rinfo, dinfo, d_terminals, (u64 *)d_term_mass,
+        return dist_device<8>(c, d_trace, d_counts, opts, L, thresh, n_thresh, R, rinfo, dinfo, d_terminals, (u64 *)d_term_mass,
                               term_cap, round_mass, dump, (hipStream_t)stream);
     } catch (const std::bad_alloc &) {
         return DSM_E_NOMEM;

@@ -5,10 +5,10 @@
  *
  * replay_kernel<NP>: one system per lane, workgroups of one wave in a grid-stride loop over the
  * ids, at most DSM_EVENTS_MAX_LANES lanes.  The transition is dsm_events.h ev_run -- the same code
- * the host entry runs -- over dsm_table.h's datapath, with the micro-op table in LDS.  A lane's
- * system state (node records, inboxes, staged sends: EV_WORDS(np) words) lies in the ctx-owned
- * scratch, word i of lane l at scratch[i * lanes + l], so a wave's accesses to the same word of
- * its 64 systems coalesce.  The scratch is sized by the lanes of the launch, not by n_ids.
+ * the host entry runs: the loop around dsm_step.h's st_round -- with the micro-op table in LDS.
+ * A lane's system state (node records, inboxes, staged sends: EV_WORDS(np) words) lies in the
+ * ctx-owned scratch, word i of lane l at scratch[i * lanes + l], so a wave's accesses to the same
+ * word of its 64 systems coalesce.  The scratch is sized by the lanes of the launch, not by n_ids.
  *
  * The log is not taken from sim_kernel or ser_kernel: a MODE bit there would add instantiations
  * to kernels the tests pin one by one and put work on the benchmark path.  The replay computes
@@ -55,7 +55,7 @@ __global__ void __launch_bounds__(EV_THREADS) replay_kernel(const ReplayArgs a) 
     __syncthreads();
     const uint64_t lanes = (uint64_t)gridDim.x * EV_THREADS;
     const uint64_t lane = (uint64_t)blockIdx.x * EV_THREADS + threadIdx.x;
-    const EvMem m = {a.scratch + lane, (size_t)lanes};
+    const StMem m = {a.scratch + lane, (size_t)lanes};
     for (uint64_t i = lane; i < a.n_ids; i += lanes) {
         const uint64_t id = a.ids ? a.ids[i] : i;
         EvSink sink = {a.events ? a.events + i * a.cap : nullptr, a.events ? a.cap : 0u, 0u, EV_HASH0};
@@ -138,7 +138,7 @@ extern "C" int dsm_trace_events(int np, const uint16_t *traces, const uint32_t *
     uint32_t *mem = (uint32_t *)malloc(sizeof(uint32_t) * EV_WORDS(8));
     if (!mem) return DSM_E_NOMEM;
     if (dt_build(tab) > DT_ENTRIES) { free(mem); return DSM_E_INVAL; }
-    const EvMem m = {mem, 1};
+    const StMem m = {mem, 1};
     for (uint64_t i = 0; i < n_ids; ++i) {
         const uint64_t id = ids ? ids[i] : i;
         EvSink sink = {events ? events + i * event_cap : nullptr, event_cap, 0u, EV_HASH0};
@@ -156,7 +156,7 @@ extern "C" int dsm_trace_events(int np, const uint16_t *traces, const uint32_t *
 
 extern "C" uint64_t dsm_event_trace_hash(const uint64_t *events, uint64_t n) {
     uint64_t h = EV_HASH0;
-    for (uint64_t i = 0; events && i < n; ++i) h = ev_fmix64(h ^ events[i]);
+    for (uint64_t i = 0; events && i < n; ++i) h = hs_fmix64(h ^ events[i]);
     return h;
 }
 

@@ -10,15 +10,11 @@
 #include <stdint.h>
 
 #include "dsm.h"
+#include "dsm_hash.h"
 
 namespace dsmg {
 
-__device__ __forceinline__ uint64_t splitmix(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ULL;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
+__device__ __forceinline__ uint64_t splitmix(uint64_t z) { return hs_splitmix64(z); }    /* dsm_hash.h's */
 /* One splitmix64 output feeds 4 consecutive instructions, 16 bits each. */
 template <int NP>
 __device__ __forceinline__ uint32_t instr_from_bits(uint32_t h, int dist) {

@@ -9,8 +9,12 @@
  *   dsm_census.hip   outcome census
  *   dsm_audit.hip    coherence audit
  *   dsm_events.hip   event trace: the replay kernel, its host twin and the formatter
- *   dsm_reach.hip    exhaustive exploration: the search kernels, the host search, witnesses
+ *   dsm_reach.hip    exhaustive exploration: the search kernels, the host search, witnesses;
+ *                    the exclusive scan
  *   dsm_dist.hip     outcome distribution: the edge list and the rounds, the host reference
+ * The last three replay ONE system a round at a time: the round is dsm_step.h's st_round, once,
+ * under dsm_events.h's and dsm_reach.h's inbox and log policies, the hashes are dsm_hash.h's, and
+ * dsm_reach_dev.h holds the device plumbing dsm_reach.hip and dsm_dist.hip share.
  * Each kernel is launched from the unit that defines it.  Not part of the ABI.
  */
 #ifndef DSM_INTERNAL_H
@@ -138,6 +142,10 @@ extern "C" int dsm_debug_dist_edges_device(dsm_ctx *c, const uint16_t *d_trace, 
  * (with classes and offsets), table, edges, push (all rounds of all thresholds). */
 extern "C" int dsm_debug_dist_times(double *ms);
 
+/* Test-only (not part of the ABI): dsm_exscan_launch with tile sums of its own, waited for --
+ * d_out[0 .. n] = the exclusive scan of d_in[0 .. n) in 64 bits, d_out[n] the total. */
+extern "C" int dsm_debug_exscan_device(dsm_ctx *c, const uint32_t *d_in, uint64_t n, uint64_t *d_out, void *stream);
+
 /* dsm_text.hip: called by dsm_close */
 void dsm_text_release(dsm_ctx *c);
 /* dsm_events.hip: called by dsm_close */
@@ -165,6 +173,11 @@ DSM_LOCAL void dsm_scan_launch(int np, unsigned blocks, hipStream_t st, const ui
                                unsigned long long *counters);
 DSM_LOCAL void dsm_digest_launch(int np, unsigned blocks, hipStream_t st, uint64_t n_sys, const uint4 *recs,
                                  dsm_sys_result *results, unsigned long long *counters);
+/* dsm_reach.hip: scan_sums_kernel, scan_top_kernel, scan_final_kernel -- out[0 .. n] = the exclusive
+ * scan of in[0 .. n) in 64 bits, out[n] the total; n > 0; bsum: a word per tile of DSM_EXSCAN_TILE */
+#define DSM_EXSCAN_TILE 2048
+DSM_LOCAL void dsm_exscan_launch(const uint32_t *in, unsigned long long n, unsigned long long *bsum,
+                                 unsigned long long *out, hipStream_t st);
 
 /* is [first_sys, first_sys + n_sys) inside the node records of the last run?  DSM_E_STATE where
  * the context holds none, or was opened without the flags in `need` (DSM_F_SNAPSHOTS, or 0);

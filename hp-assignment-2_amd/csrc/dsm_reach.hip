@@ -16,7 +16,8 @@
  *   reach_expand_kernel<NP>   one lane per candidate: its parent by a search of the scanned
  *                             counts, its mask (the candidate's rank deposited into A), the parent
  *                             copied into the chunk buffer (word-major across the chunk), one
- *                             rs_round in place with the micro-op table in LDS, the fingerprint
+ *                             rs_round in place with the micro-op table in LDS (dsm_reach_dev.h
+ *                             successor), the fingerprint
  *   reach_insert_kernel       the fingerprint into the visited table (open addressing, {key,
  *                             meta} slots): compare-and-swap on the key, then an unconditional max
  *                             on meta with a pending value that encodes ~candidate index.  A
@@ -29,7 +30,8 @@
  *   reach_settle_kernel       owners write meta = settled | id; new states move to the store in
  *                             id order with their parent, mask and fingerprint
  * The scans are three small kernels of this unit (tile sums, one workgroup over the sums, tile
- * scans): integers, so deterministic, and no workgroup ever waits for another.  Atomics are
+ * scans; dsm_exscan_launch, which dsm_dist.hip uses too): integers, so deterministic, and no
+ * workgroup ever waits for another.  Atomics are
  * relaxed and agent scope: the table is read only after the kernel that wrote it.  Every probe
  * loop is bounded by the slot count, every launch by its chunk.
  *
@@ -48,17 +50,11 @@
 #include <unordered_map>
 #include <vector>
 
-#include "dsm_internal.h"
-#include "dsm_reach.h"
+#include "dsm_reach_dev.h"
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int RT = 256;                      /* threads per workgroup, every kernel here */
 constexpr u64 SETTLED = 1ull << 63;
-constexpr uint32_t DEFAULT_CHUNK = 1u << 18;
-constexpr uint32_t MAX_CHUNK = 1u << 24;
 
 struct ReachCtr {                            /* device counters of one call */
     u64 coll, table_full, max_fill, by_status[5];
@@ -69,6 +65,7 @@ DSM_HD u64 pending_of(u64 j) { return ~j & ~SETTLED; }
 /* ---- exclusive scan of n uint32 into n + 1 uint64 (out[n] = the total) --------------------- */
 constexpr int SCAN_ITEMS = 8;
 constexpr int SCAN_TILE = RT * SCAN_ITEMS;
+static_assert(SCAN_TILE == DSM_EXSCAN_TILE, "dsm_internal.h sizes the callers' tile sums");
 
 /* exclusive scan of one value per thread over the workgroup; *total = the sum */
 __device__ __forceinline__ u64 block_exscan(u64 v, u64 *s_buf, u64 *total) {
@@ -144,7 +141,7 @@ __global__ void __launch_bounds__(RT) reach_count_kernel(const uint32_t *store, 
                                                          uint32_t *cnt, uint32_t *term, ReachCtr *ctr) {
     const u64 i = (u64)blockIdx.x * RT + threadIdx.x;
     if (i >= n) return;
-    const EvMem m = {const_cast<uint32_t *>(store) + lo + i, (size_t)cap};
+    const StMem m = {const_cast<uint32_t *>(store) + lo + i, (size_t)cap};
     const uint32_t a = rs_enabled<NP>(m, counts, stride);
     const bool t = rs_terminal<NP>(m, a, nullptr);
     A[i] = a;
@@ -161,7 +158,7 @@ __global__ void __launch_bounds__(RT) reach_term_kernel(const uint32_t *store, u
                                                         u64 *terminals, u64 term_cap, ReachCtr *ctr) {
     const u64 i = (u64)blockIdx.x * RT + threadIdx.x;
     if (i >= n || !term[i]) return;
-    const EvMem m = {const_cast<uint32_t *>(store) + lo + i, (size_t)cap};
+    const StMem m = {const_cast<uint32_t *>(store) + lo + i, (size_t)cap};
     dsm_sys_result res;
     (void)rs_terminal<NP>(m, 0u, &res);
     __hip_atomic_fetch_add(&ctr->by_status[res.status & 7u], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -185,10 +182,7 @@ struct ExpandArgs {
     u64 c0, n;                    /* candidates [c0, c0 + n) of the level */
     uint32_t *cand;               /* RS_WORK(np) rows of cs words */
     u64 cs;
-    const uint16_t *trace;
-    const uint32_t *counts;
-    const uint32_t *table;
-    uint32_t stride, L;
+    StepArgs step;
     u64 *cfp;
     uint32_t *cpar, *cmask;
 };
@@ -196,23 +190,13 @@ struct ExpandArgs {
 template <int NP>
 __global__ void __launch_bounds__(RT) reach_expand_kernel(const ExpandArgs a) {
     __shared__ uint32_t s_tab[DT_TABLE_WORDS];
-    for (uint32_t i = threadIdx.x; i < DT_TABLE_WORDS; i += RT) s_tab[i] = a.table[i];
-    __syncthreads();
+    table_to_lds(s_tab, a.step.table);
     const u64 j = (u64)blockIdx.x * RT + threadIdx.x;
     if (j >= a.n) return;
-    const u64 g = a.c0 + j;
-    u64 lo = 0, hi = a.nfront;                /* the largest p with offs[p] <= g */
-    while (hi - lo > 1) {
-        const u64 mid = lo + (hi - lo) / 2;
-        if (a.offs[mid] <= g) lo = mid; else hi = mid;
-    }
-    const uint32_t mask = rs_deposit((uint32_t)(g - a.offs[lo]) + 1u, a.A[lo]);
-    const uint32_t *src = a.store + a.lo + lo;
-    uint32_t *dst = a.cand + j;
-    for (uint32_t i = 0; i < RS_WORDS(NP); ++i) dst[(size_t)i * a.cs] = src[(size_t)i * a.cap];
-    const EvMem m = {dst, (size_t)a.cs};
-    RsStat st = {0u, 0u};
-    rs_round<NP>(m, s_tab, a.trace, a.counts, a.stride, mask, a.L, &st, nullptr);
+    u64 lo;
+    uint32_t mask;
+    const StMem m = successor<NP>(a.store + a.lo, (size_t)a.cap, a.nfront, a.offs, a.A, a.c0 + j, a.cand + j, (size_t)a.cs,
+                                  s_tab, a.step, &lo, &mask);
     a.cfp[j] = rs_fingerprint<NP>(m);
     a.cpar[j] = (uint32_t)(a.lo + lo);
     a.cmask[j] = mask;
@@ -299,7 +283,7 @@ template <int NP>
 __global__ void reach_root_kernel(uint32_t *store, u64 cap, u64 *table, u64 slots, uint32_t *parents, uint8_t *masks,
                                   u64 *fps) {
     if (blockIdx.x || threadIdx.x) return;
-    const EvMem m = {store, (size_t)cap};
+    const StMem m = {store, (size_t)cap};
     rs_init<NP>(m);
     const u64 fp = rs_fingerprint<NP>(m);
     table[2 * (fp & (slots - 1))] = fp;
@@ -308,23 +292,6 @@ __global__ void reach_root_kernel(uint32_t *store, u64 cap, u64 *table, u64 slot
     if (masks) masks[0] = 0u;
     if (fps) fps[0] = fp;
 }
-
-/* a device buffer freed when the call returns, whichever way */
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int ensure(size_t bytes) {
-        if (p && cap >= bytes) return DSM_OK;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) { p = nullptr; (void)hipGetLastError(); return DSM_E_NOMEM; }
-        cap = bytes;
-        return DSM_OK;
-    }
-    template <typename T> T *as() const { return static_cast<T *>(p); }
-};
-
-unsigned grid_of(u64 n) { return (unsigned)((n + RT - 1) / RT); }
 
 /* Measurement only (DSM_REACH_TIMING=1 in the environment at the call; tools/reach_time.py): a
  * pair of device events around every kernel class of the search, summed when the call ends and
@@ -366,23 +333,6 @@ struct SpanTimer {
     }
 };
 
-/* out[0 .. n] = exclusive scan of in[0 .. n); bsum holds ceil(n / SCAN_TILE) words; n > 0 */
-void scan_launch(const uint32_t *in, u64 n, u64 *bsum, u64 *out, hipStream_t st) {
-    const u64 nb = (n + SCAN_TILE - 1) / SCAN_TILE;
-    hipLaunchKernelGGL(scan_sums_kernel, dim3((unsigned)nb), dim3(RT), 0, st, in, n, bsum);
-    hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(RT), 0, st, bsum, nb);
-    hipLaunchKernelGGL(scan_final_kernel, dim3((unsigned)nb), dim3(RT), 0, st, in, n, bsum, out);
-}
-
-int opts_ok(const dsm_reach_opts *o, uint32_t *L) {
-    if (!o || o->inbox_limit > RS_RING) return 0;
-    if (o->kind != DSM_CENSUS_DUMPS && o->kind != DSM_CENSUS_FINAL) return 0;
-    if (o->max_states == 0 || o->max_states > DSM_REACH_MAX_STATES) return 0;
-    if (o->max_depth >= DSM_REACH_MAX_LEVELS || o->chunk > MAX_CHUNK) return 0;
-    *L = o->inbox_limit ? o->inbox_limit : RS_RING;
-    return 1;
-}
-
 /* the end of a level, the same on both sides: does the search stop before expanding level
  * `depth` (which has `total` successors)? */
 bool stop_before_expand(const dsm_reach_opts *o, u64 depth, u64 total, uint64_t *flags) {
@@ -403,7 +353,7 @@ int reach_device(dsm_ctx *c, const uint16_t *d_trace, const uint32_t *d_counts, 
     u64 slots = 64;
     while (slots < 2 * (cap + chunk)) slots <<= 1;
     const uint32_t stride = c->cfg.max_instr;
-    const uint32_t *table = reinterpret_cast<const uint32_t *>(c->d_table);
+    const StepArgs step = {d_trace, d_counts, reinterpret_cast<const uint32_t *>(c->d_table), stride, L};
 
     DevBuf b_store, b_table, b_cand, b_cfp, b_cpar, b_cmask, b_cslot, b_new, b_newoff, b_ctr;
     DevBuf b_A, b_cnt, b_term, b_offs, b_toff, b_bsum;
@@ -437,8 +387,8 @@ int reach_device(dsm_ctx *c, const uint16_t *d_trace, const uint32_t *d_counts, 
         tm.begin(T_COUNT);
         hipLaunchKernelGGL(reach_count_kernel<NP>, dim3(grid_of(nf)), dim3(RT), 0, st, b_store.as<uint32_t>(), cap, lo, nf,
                            d_counts, stride, b_A.as<uint32_t>(), b_cnt.as<uint32_t>(), b_term.as<uint32_t>(), ctr);
-        scan_launch(b_cnt.as<uint32_t>(), nf, b_bsum.as<u64>(), b_offs.as<u64>(), st);
-        scan_launch(b_term.as<uint32_t>(), nf, b_bsum.as<u64>(), b_toff.as<u64>(), st);
+        dsm_exscan_launch(b_cnt.as<uint32_t>(), nf, b_bsum.as<u64>(), b_offs.as<u64>(), st);
+        dsm_exscan_launch(b_term.as<uint32_t>(), nf, b_bsum.as<u64>(), b_toff.as<u64>(), st);
         tm.end();
         u64 total = 0, nterm = 0;
         HIPCK(hipMemcpyAsync(&total, b_offs.as<u64>() + nf, 8, hipMemcpyDeviceToHost, st));
@@ -456,9 +406,8 @@ int reach_device(dsm_ctx *c, const uint16_t *d_trace, const uint32_t *d_counts, 
             ExpandArgs ea;
             ea.store = b_store.as<uint32_t>(); ea.cap = cap; ea.lo = lo; ea.nfront = nf;
             ea.offs = b_offs.as<u64>(); ea.A = b_A.as<uint32_t>(); ea.c0 = c0; ea.n = n;
-            ea.cand = b_cand.as<uint32_t>(); ea.cs = chunk; ea.trace = d_trace; ea.counts = d_counts; ea.table = table;
-            ea.stride = stride; ea.L = L; ea.cfp = b_cfp.as<u64>(); ea.cpar = b_cpar.as<uint32_t>();
-            ea.cmask = b_cmask.as<uint32_t>();
+            ea.cand = b_cand.as<uint32_t>(); ea.cs = chunk; ea.step = step; ea.cfp = b_cfp.as<u64>();
+            ea.cpar = b_cpar.as<uint32_t>(); ea.cmask = b_cmask.as<uint32_t>();
             ++g_reach_chunks;
             tm.begin(T_EXPAND);
             hipLaunchKernelGGL(reach_expand_kernel<NP>, dim3(grid_of(n)), dim3(RT), 0, st, ea);
@@ -470,7 +419,7 @@ int reach_device(dsm_ctx *c, const uint16_t *d_trace, const uint32_t *d_counts, 
             tm.begin(T_RESOLVE);
             hipLaunchKernelGGL(reach_resolve_kernel, dim3(grid_of(n)), dim3(RT), 0, st, b_cand.as<uint32_t>(), chunk,
                                RS_WORDS(NP), n, b_table.as<u64>(), b_cslot.as<u64>(), b_new.as<uint32_t>(), ctr);
-            scan_launch(b_new.as<uint32_t>(), n, b_bsum.as<u64>(), b_newoff.as<u64>(), st);
+            dsm_exscan_launch(b_new.as<uint32_t>(), n, b_bsum.as<u64>(), b_newoff.as<u64>(), st);
             tm.end();
             SettleArgs sa;
             sa.cand = b_cand.as<uint32_t>(); sa.cs = chunk; sa.n = n; sa.newflag = b_new.as<uint32_t>();
@@ -523,7 +472,7 @@ int reach_host(const uint16_t *trace, const uint32_t *counts, uint32_t stride, c
     std::vector<uint64_t> loff;
     std::vector<uint32_t> A;
     {
-        const EvMem m = {S.data(), 1};
+        const StMem m = {S.data(), 1};
         rs_init<NP>(m);
         const uint64_t fp = rs_fingerprint<NP>(m);
         seen.emplace(fp, 0);
@@ -539,7 +488,7 @@ int reach_host(const uint16_t *trace, const uint32_t *counts, uint32_t stride, c
         A.assign(nf, 0);
         u64 total = 0;
         for (u64 i = 0; i < nf; ++i) {
-            const EvMem m = {&S[(lo + i) * W], 1};
+            const StMem m = {&S[(lo + i) * W], 1};
             const uint32_t a = rs_enabled<NP>(m, counts, stride);
             const uint64_t f = rs_max_fill<NP>(m);
             if (f > r.max_fill) r.max_fill = f;
@@ -564,9 +513,8 @@ int reach_host(const uint16_t *trace, const uint32_t *counts, uint32_t stride, c
             for (uint32_t j = 1; j <= cnt && fresh <= cap; ++j) {
                 const uint32_t mask = rs_deposit(j, A[i]);
                 memcpy(tmp, &S[(lo + i) * W], W * 4);
-                const EvMem m = {tmp, 1};
-                RsStat st = {0u, 0u};
-                rs_round<NP>(m, tab, trace, counts, stride, mask, L, &st, nullptr);
+                const StMem m = {tmp, 1};
+                (void)rs_round<NP>(m, tab, trace, counts, stride, mask, L, nullptr);
                 const uint64_t fp = rs_fingerprint<NP>(m);
                 const auto it = seen.find(fp);
                 if (it != seen.end()) {
@@ -602,13 +550,15 @@ int replay_host(const uint16_t *trace, const uint32_t *counts, uint32_t stride, 
     uint32_t tab[DT_TABLE_WORDS], tmp[RS_WORK(NP)], dumpw[16 * NP];
     if (dt_build(tab) > DT_ENTRIES) return DSM_E_INVAL;
     memset(dumpw, 0, sizeof dumpw);
-    const EvMem m = {tmp, 1};
+    const StMem m = {tmp, 1};
     rs_init<NP>(m);
-    RsStat st = {0u, 0u};
+    uint32_t msgs = 0, instrs = 0;
     for (uint64_t k = 0; k < n; ++k) {
         const uint32_t a = rs_enabled<NP>(m, counts, stride), mask = masks[k];
         if (mask == 0 || (mask & ~a)) return DSM_E_INVAL;
-        rs_round<NP>(m, tab, trace, counts, stride, mask, L, &st, dumpw);
+        const StRound rd = rs_round<NP>(m, tab, trace, counts, stride, mask, L, dumpw);
+        msgs += rd.msgs;
+        instrs += rd.instrs;
     }
     if (dump) memcpy(dump, dumpw, sizeof dumpw);
     if (fin) memcpy(fin, tmp, 64 * NP);
@@ -617,13 +567,37 @@ int replay_host(const uint16_t *trace, const uint32_t *counts, uint32_t stride, 
         (void)rs_terminal<NP>(m, 0u, res);
         if (!term) res->status = (res->status & ~0xFFu) | DSM_ROUND_LIMIT;
         res->rounds = (uint32_t)n;
-        res->msgs = st.msgs;
-        res->instrs = st.instrs;
+        res->msgs = msgs;
+        res->instrs = instrs;
     }
     return DSM_OK;
 }
 
 }  // namespace
+
+/* out[0 .. n] = exclusive scan of in[0 .. n); bsum holds ceil(n / DSM_EXSCAN_TILE) words; n > 0 */
+void dsm_exscan_launch(const uint32_t *in, u64 n, u64 *bsum, u64 *out, hipStream_t st) {
+    const u64 nb = (n + SCAN_TILE - 1) / SCAN_TILE;
+    hipLaunchKernelGGL(scan_sums_kernel, dim3((unsigned)nb), dim3(RT), 0, st, in, n, bsum);
+    hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(RT), 0, st, bsum, nb);
+    hipLaunchKernelGGL(scan_final_kernel, dim3((unsigned)nb), dim3(RT), 0, st, in, n, bsum, out);
+}
+
+extern "C" int dsm_debug_exscan_device(dsm_ctx *c, const uint32_t *d_in, uint64_t n, uint64_t *d_out, void *stream) {
+    if (!c || !d_out || (n && !d_in) || ((uintptr_t)d_out & 7u) || ((uintptr_t)d_in & 3u)) return DSM_E_INVAL;
+    HIPCK(hipSetDevice(c->device));
+    const hipStream_t st = (hipStream_t)stream;
+    DevBuf b_bsum;
+    if (n == 0) {
+        HIPCK(hipMemsetAsync(d_out, 0, 8, st));
+    } else {
+        if (int rc = b_bsum.alloc((size_t)((n + SCAN_TILE - 1) / SCAN_TILE) * 8)) return rc;
+        dsm_exscan_launch(d_in, n, b_bsum.as<u64>(), (u64 *)d_out, st);
+    }
+    HIPCK(hipStreamSynchronize(st));          /* the tile sums are freed on return */
+    HIPCK(hipGetLastError());
+    return DSM_OK;
+}
 
 extern "C" int dsm_debug_reach_times(double *ms, uint64_t *chunks) {
     if (!ms || !chunks) return DSM_E_INVAL;

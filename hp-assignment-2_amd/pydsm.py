@@ -195,6 +195,7 @@ def lib():
                                                   ctypes.POINTER(u64), vp]),
             "dsm_debug_dist_times": (i32, [vp]),
             "dsm_debug_reach_times": (i32, [vp, ctypes.POINTER(u64)]),
+            "dsm_debug_exscan_device": (i32, [vp, vp, u64, vp, vp]),
             "dsm_debug_order_state": (i32, [vp, vp, vp, vp, u64, u64, vp, u32, ctypes.POINTER(u32),
                                             ctypes.POINTER(i32)]),
         }
@@ -822,6 +823,13 @@ class Engine:
         _check(lib().dsm_audit_run_device(self.ctx, first_sys, n_sys, _dptr(d_words, 4 * n_sys),
                                           _dptr(d_audit, 8 * NAUDIT), ctypes.c_void_p(stream)),
                "dsm_audit_run_device")
+
+    def debug_exscan_device(self, d_in, n, d_out, stream=0):
+        """dsm_debug_exscan_device (test-only): the exclusive scan the exploration and the outcome
+        distribution share -- n uint32 in d_in -> n + 1 uint64 in d_out, d_out[n] the total.
+        Waits for the stream."""
+        _check(lib().dsm_debug_exscan_device(self.ctx, _dptr(d_in, 4 * n), n, _dptr(d_out, 8 * (n + 1)),
+                                             ctypes.c_void_p(stream)), "dsm_debug_exscan_device")
 
     def trace_events_device(self, d_traces, d_counts, n_sys, d_ids, n_ids, d_events, event_cap,
                             d_n_events, d_hash, d_results, stream=0):

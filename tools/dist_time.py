@@ -34,7 +34,8 @@ ONE, FOUR = (0x8000,), (0x2000, 0x4000, 0x8000, 0xC000)
 
 
 def stats(ms):
-    return {"min": round(min(ms), 3), "max": round(max(ms), 3), "median": round(statistics.median(ms), 3)}
+    return {"min": round(min(ms), 3), "max": round(max(ms), 3), "median": round(statistics.median(ms), 3),
+            "calls": [round(x, 3) for x in ms]}
 
 
 def main():

@@ -10,8 +10,8 @@ Beside it, the yardstick that predates the search: Engine.explore of `explore` s
 of the same system (default 1 Mi), its time and how many outcomes it found; and, with --host, the
 host reference's single-thread time on the same input, as a plain fact.
 
-Prints one JSON line: min / max / median milliseconds per search, states and transitions per
-second (at the median), levels, chunks, the kernel shares, the outcomes of both.
+Prints one JSON line: min / max / median milliseconds per search and every call's in order, states
+and transitions per second (at the median), levels, chunks, the kernel shares, the outcomes of both.
 
     python tools/reach_time.py [--input contention|sample|test_4|..] [--max-states 16777216] [--chunk 0]
                                [--reps 5] [--warmup 2] [--explore 1048576] [--host] [--out FILE]
@@ -89,7 +89,8 @@ def main():
         terms = d_term.cpu().numpy().view(pydsm.REACH_TERMINAL_DTYPE)[:min(i["terminals"], term_cap)]
         table, cap = pydsm.reach_census(terms, pydsm.CENSUS_DUMPS)
         med = float(np.median(ms))
-        out.update({"info": i, "ms": {"min": min(ms), "max": max(ms), "median": med, "reps": len(ms)},
+        out.update({"info": i, "ms": {"min": min(ms), "max": max(ms), "median": med, "reps": len(ms),
+                           "calls": [round(x, 3) for x in ms]},
                     "states_per_s": i["states"] / (med * 1e-3), "transitions_per_s": i["transitions"] / (med * 1e-3),
                     "levels": i["levels"], "chunks": int(chunks.value), "timed_run_ms": timed_ms,
                     "kernel_ms": dict(zip(CLASSES, (float(x) for x in kms))),
