@@ -35,18 +35,26 @@
 
 /* ---- the serial resume pass (dsm_ser.hip, dsm_serial.h) -------------------------------- */
 #ifndef SER_HB
-#define SER_HB 8            /* finished lanes that trigger a batched hand-over (1: at once) */
+#define SER_HB 8            /* finished lanes that trigger a batched hand-over (1: at once); round 9,
+                               kernel ms C3 / C5, 4 / 8 / 16: 30.97 / 30.86 / 30.83, 19.68 / 19.62 / 19.34
+                               alone, 16 with SER_SOLO_HW 2 19.50 against 19.62: inside the run-to-run
+                               spread of C3 (0.4 ms) and twice that of C5 (0.1 ms), left */
 #endif
 #ifndef SER_HT
-#define SER_HT 32           /* ... or iterations the oldest finished lane has waited */
+#define SER_HT 32           /* ... or iterations the oldest finished lane has waited (16 / 32 / 64:
+                               C3 30.87 / 30.86 / 30.73, C5 19.58 / 19.62 / 19.61) */
 #endif
 /* the run phase (dsm_serial.h ser_solo) in front of each refill period's iterations: taken by a
  * wave when at least SER_SOLO_MIN of 64 of its running lanes are eligible */
 #ifndef SER_SOLO_MIN
-#define SER_SOLO_MIN 48     /* C3 64 / 56 / 48 / 32: 32.45 / 31.97 / 32.30 / 32.29 ms; C5 21.98 / 21.86 / 21.80 / 21.81 */
+#define SER_SOLO_MIN 48     /* C3 64 / 56 / 48 / 32: 32.45 / 31.97 / 32.30 / 32.29 ms; C5 21.98 / 21.86 / 21.80 / 21.81;
+                               round 9 (the run's simple-only transaction): 32.25 / 31.07 / 30.86 / 30.77,
+                               19.93 / 19.61 / 19.62 / 19.61 */
 #endif
 #ifndef SER_SOLO_HW
-#define SER_SOLO_HW 4       /* a run's weight in SER_HT's iterations */
+#define SER_SOLO_HW 2       /* a run's weight in SER_HT's iterations: its measured cost, 7,709 cycles
+                               against 3,156 per iteration (SER_PROBE 2, C3; round 8: 12,188 / 3,568 and
+                               4).  Kernel ms 4 / 3 / 2: C3 30.86 / 30.88 / 30.54, C5 19.62 / 19.60 / 19.58 */
 #endif
 /* what ser_macro (a lone node's whole transaction in one step) covers besides hits and misses */
 #ifndef SER_DEAD_FWD

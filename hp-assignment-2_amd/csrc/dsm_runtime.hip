@@ -177,7 +177,7 @@ static const char *build_variant() {
     add("SER_HB", SER_HB, 8);
     add("SER_HT", SER_HT, 32);
     add("SER_SOLO_MIN", SER_SOLO_MIN, 48);
-    add("SER_SOLO_HW", SER_SOLO_HW, 4);
+    add("SER_SOLO_HW", SER_SOLO_HW, 2);
     add("FF_LONG_U", FF_LONG_U, 8);
     add("SER_DEAD_FWD", SER_DEAD_FWD, 1);
     add("SER_NOTICE_HOME", SER_NOTICE_HOME, 1);

@@ -702,66 +702,216 @@ DSM_HD bool ser_macro(M &m, SReg &r, SCache &cc, F &&fetch, R &&on_dump, P &&sta
  * the first step that is not simple: a forward, a notice, a fan-out, !ok as ser_macro defines
  * it for a simple step (a home >= NP, EM with no bit), the end of the trace, or the round
  * limit within reach (ser_quiet_lone's test, again before every step: a run adds up to 8 x 4
- * rounds).  A stopped lane idles through the rest of the run (its stores go to the dummy
- * word).  Returns the steps applied. */
+ * rounds).  A stopped lane idles through the rest of the run (it writes the words it read back
+ * as they were).  Each step is ser_txn_simple's (below, round 9), not the general transaction's:
+ * the eight slots are one straight stretch of code with no exec-masked region.  Returns the
+ * steps applied. */
 enum : uint32_t { SOLO_FWD = 0, SOLO_NOTICE, SOLO_FAN, SOLO_HOME, SOLO_TRACE_END, SOLO_ROUND_LIMIT, SOLO_CAUSES };
+
+/* ---- the run's transaction (round 9): simple steps only, predicates as integers ------------
+ * ser_txn_front + ser_txn_home (above; ser_macro's, and this one's reference:
+ * tests/model/txn_simple_model.cpp compares the two on every input) decide everything a
+ * transaction can be, each predicate a compare into a lane mask and each outcome a chain of
+ * selects on such masks.  A run applies only simple steps, so here a forward, a notice, a
+ * fan-out and the home cases are only detected (`stop`), the updates are computed with those
+ * cases absent, and the small decisions are read from constant look-up words by a packed
+ * condition code: bit c of a 32-bit word is the predicate at code c, read as the all-ones
+ * mask a bit merge takes (one v_bfe_i32).  The codes:
+ *   lc = Ls | (La != a) << 2 | (La == 0xFF) << 3                          the line
+ *   vc = dV | (Ls != 0) << 2 | min(sharers of the victim, 3) << 3         the victim's home
+ *   hc = dH | wr << 2 | miss << 3 | (hit on SHARED) << 4                  the request's home
+ * Every update is the identity where its case is absent -- the victim's words without an
+ * eviction, the request's home words on a plain hit -- so the four stores need no flags of
+ * their own (the lane's alone) and the forwarding between the two homes needs no `ev`.
+ * Exact for every line address a line can hold (a block's, < 0x80, or the initial 0xFF). */
+DSM_HD uint32_t s_min(uint32_t a, uint32_t b) { return a < b ? a : b; }
+DSM_HD uint32_t s_mask(uint32_t L, uint32_t c) {          /* bit c of L as 0 / all-ones */
+#ifdef __HIP_DEVICE_COMPILE__
+    return (uint32_t)__builtin_amdgcn_sbfe((int)L, c, 1u);
+#else
+    return 0u - ((L >> c) & 1u);
+#endif
+}
+DSM_HD uint32_t s_sel(uint32_t a, uint32_t b, uint32_t m) { return (a & ~m) | (b & m); }   /* b where m */
+/* look-up words: bit c (s_lut), or bits 2c and 2c + 1 (s_lut2, c < 16), = f(c) */
+template <class F>
+constexpr uint32_t s_lut(F f) {
+    uint32_t w = 0;
+    for (uint32_t c = 0; c < 32u; ++c) w |= (f(c) ? 1u : 0u) << c;
+    return w;
+}
+template <class F>
+constexpr uint32_t s_lut2(F f) {
+    uint32_t w = 0;
+    for (uint32_t c = 0; c < 16u; ++c) w |= (f(c) & 3u) << (2u * c);
+    return w;
+}
+struct LcCode {       /* the line: hit :608, :635; a victim :616-618, :670-672 */
+    uint32_t Ls; bool diff, ff;
+    constexpr LcCode(uint32_t c) : Ls(c & 3u), diff((c >> 2) & 1u), ff((c >> 3) & 1u) {}
+    constexpr bool hit() const { return !diff && Ls != 3u; }
+};
+constexpr uint32_t LC_MISS = s_lut([](uint32_t c) { return !LcCode(c).hit(); });
+constexpr uint32_t LC_EV = s_lut([](uint32_t c) { const LcCode k(c); return !k.hit() && !k.ff && k.Ls != 3u; });
+constexpr uint32_t LC_HITS = s_lut([](uint32_t c) { const LcCode k(c); return k.hit() && k.Ls == 2u; });
+struct VcCode {       /* the eviction at the victim's home :498-561 (had: the node's bit is set) */
+    uint32_t dV, kc; bool mod;
+    constexpr VcCode(uint32_t c) : dV(c & 3u), kc((c >> 3) & 3u), mod(!((c >> 2) & 1u)) {}
+};
+/* the entry becomes UNOWNED: EVICT_MODIFIED of an EM entry, EVICT_SHARED of the last sharer */
+constexpr uint32_t VC_TOU = s_lut([](uint32_t c) { const VcCode k(c); return k.mod ? k.dV == 0u : k.kc == 1u; });
+/* EVICT_SHARED leaving one sharer of an S entry: the upgrade notice (:507-519) */
+constexpr uint32_t VC_NOTICE = s_lut([](uint32_t c) { const VcCode k(c); return !k.mod && k.dV == 1u && k.kc == 2u; });
+constexpr uint32_t VC_MOD = s_lut([](uint32_t c) { return VcCode(c).mod; });
+struct HcCode {       /* the request at its home :188-236, :298-328, :375-435 */
+    uint32_t dH; bool wr, miss, upg, rdq, wrq, req;
+    constexpr HcCode(uint32_t c)
+        : dH(c & 3u), wr((c >> 2) & 1u), miss((c >> 3) & 1u), upg((c >> 4) & 1u),
+          rdq(miss && !wr), wrq(miss && wr), req(miss || upg) {}
+};
+/* the new bitVector = (the old one where HC_KEEP) | (the requester's bit where HC_BIT) */
+constexpr uint32_t HC_KEEP = s_lut([](uint32_t c) { const HcCode k(c); return !k.req || (k.rdq ? k.dH != 2u : (k.wrq && k.dH == 0u)); });
+constexpr uint32_t HC_BIT = s_lut([](uint32_t c) { const HcCode k(c); return k.req && (k.rdq ? (k.dH == 1u || k.dH == 2u) : !(k.wrq && k.dH == 0u)); });
+/* the directory state becomes EM (0): every request but a read of an EM or S entry */
+constexpr uint32_t HC_EM = s_lut([](uint32_t c) { const HcCode k(c); return k.req && !(k.rdq && k.dH != 2u); });
+/* what stops the run: a miss on an EM entry (at another owner, or with no bit: `stop` when the
+ * lowest bit is not the node's), a write or upgrade on an S entry (when others share it) */
+constexpr uint32_t HC_EMMISS = s_lut([](uint32_t c) { const HcCode k(c); return k.miss && k.dH == 0u; });
+constexpr uint32_t HC_FAN = s_lut([](uint32_t c) { const HcCode k(c); return k.req && k.wr && k.dH == 1u; });
+/* the requester's line: its state changes (else a read hit), to M on a write, else to S after
+ * a read of an S entry, to E after any other read (REPLY_RD's bitVector == 2) */
+constexpr uint32_t HC_NLS = s_lut2([](uint32_t c) { const HcCode k(c); return k.rdq ? (k.dH == 1u ? 2u : 1u) : 0u; });
+
+struct SSimple {
+    uint32_t stop;                        /* != 0: not a simple step; nothing below is to be used */
+    uint32_t vh, h, wV, wH;               /* the two homes and their memory words */
+    uint32_t dsV, mbV, dsH, mbH;          /* ... as they are (a lane that stops writes them back) */
+    uint32_t dsV2, mbV2, dsH2, mbH2;      /* ... after the step (unchanged where it has no part) */
+    uint32_t la, lv, ct;                  /* the node's own words after the step */
+    uint32_t inc;                         /* rounds << 24 | 1 << 16 | messages << 8 */
+};
+template <int NP, class M>
+DSM_HD void ser_txn_simple(M &m, SSimple &o, uint32_t ins, uint32_t ct, uint32_t laW, uint32_t lvW,
+                           uint32_t n, uint32_t bit) {
+    const uint32_t a = (ins >> 8) & 0x7Fu, wrm = s_mask(ins, 15u), val = ins & 0xFFu;
+    const uint32_t idx = a & 3u, sh8 = 8u * idx, lsh = SC_LS + 2u * idx;
+    const uint32_t La = (laW >> sh8) & 0xFFu, Lv = (lvW >> sh8) & 0xFFu, Ls = (ct >> lsh) & 3u;
+    const uint32_t x = La ^ a;                 /* >= 0x80: the line's initial address, 0xFF */
+    /* the four words, all read at once (ser_txn_front's; the victim's home and word as there) */
+    const uint32_t vh = (La >> 4) & 7u, wV = S_MB + ((La >> 1) & 63u), h = a >> 4, wH = S_MB + (a >> 1);
+    const uint32_t mbV = m.ld(wV), dsV = m.ld(S_DS + vh);
+    const uint32_t mbH0 = m.ld(wH), dsH0 = m.ld(S_DS + h);
+    const uint32_t lc = Ls | (s_min(x, 1u) << 2) | ((x >> 7) << 3);
+    const uint32_t missm = s_mask(LC_MISS, lc), upgm = wrm & s_mask(LC_HITS, lc), evm = s_mask(LC_EV, lc);
+    /* the eviction at the victim's home, under evm: else its words stay as they are */
+    const uint32_t hv = (La & 1u) << 4, sv = (La & 15u) << 1;
+    const uint32_t memV = (mbV >> hv) & 0xFFu, bvV = (mbV >> (hv + 8u)) & 0xFFu, dV = (dsV >> sv) & 3u;
+    const uint32_t vc = dV | (s_min(Ls, 1u) << 2) | (s_min((uint32_t)__builtin_popcount(bvV), 3u) << 3);
+    const uint32_t hadm = evm & s_mask(bvV, n);
+    const uint32_t toUm = hadm & s_mask(VC_TOU, vc), modm = evm & s_mask(VC_MOD, vc);
+    const uint32_t clr = bvV & (toUm | (evm & ~modm & bit));      /* EVICT_SHARED: the node's bit */
+    const uint32_t mbV2 = mbV ^ (((((memV ^ Lv) & modm) | (clr << 8))) << hv);
+    const uint32_t dsV2 = dsV ^ (((dV ^ 2u) << sv) & toUm);
+    /* the request's home sees the eviction where they share a word, or the home */
+    const uint32_t mbH = (x & 0x7Eu) == 0u ? mbV2 : mbH0;
+    const uint32_t dsH = (x & 0x70u) == 0u ? dsV2 : dsH0;
+    const uint32_t hh = (a & 1u) << 4, shb = (a & 15u) << 1;
+    const uint32_t memH = (mbH >> hh) & 0xFFu, bvH = (mbH >> (hh + 8u)) & 0xFFu, dH = (dsH >> shb) & 3u;
+    const uint32_t hc = dH | (wrm & 4u) | (missm & 8u) | (upgm & 16u);
+    const uint32_t wrqm = wrm & missm, reqm = missm | upgm;
+    const uint32_t nbvH = (bvH & s_mask(HC_KEEP, hc)) | (bit & s_mask(HC_BIT, hc));
+    const uint32_t nmemH = s_sel(memH, val, wrqm);
+    o.mbH2 = (mbH & ~(0xFFFFu << hh)) | ((nmemH | (nbvH << 8)) << hh);
+    o.dsH2 = dsH & ~((3u << shb) & s_mask(HC_EM, hc));
+    o.stop = (bvV & bit & evm & s_mask(VC_NOTICE, vc)) | (((bvH & (0u - bvH)) ^ bit) & s_mask(HC_EMMISS, hc)) |
+             (bvH & ~bit & s_mask(HC_FAN, hc)) | (NP == 8 ? 0u : (NP == 4 ? a >> 6 : (uint32_t)(h >= (uint32_t)NP)));
+    /* the requester's line (:243-246, :445-447, :334-336; a write hit :642-643, :656-657),
+     * pendingWriteValue (:633), the instruction index */
+    const uint32_t nLv = s_sel(s_sel(Lv, memH, missm), val, wrm);
+    const uint32_t dLs = (Ls & (wrm | missm)) ^ dt_ubfe(HC_NLS, 2u * (hc & 15u), 2u);
+    o.la = (laW & ~(0xFFu << sh8)) | (a << sh8);
+    o.lv = (lvW & ~(0xFFu << sh8)) | (nLv << sh8);
+    o.ct = (ct ^ ((dLs << lsh) | ((ct ^ val) & 0xFFu & wrm))) + (1u << SC_IP);
+    o.vh = vh; o.h = h; o.wV = wV; o.wH = wH; o.dsV2 = dsV2; o.mbV2 = mbV2;
+    o.dsV = dsV; o.mbV = mbV; o.dsH = dsH0; o.mbH = mbH0;
+    /* rounds: 1 for a plain hit, else the issue, the request's round (the third when the
+     * eviction queued before it at the same home) and the reply's; messages: eviction, request,
+     * reply */
+    o.inc = 0x01010000u + ((reqm & 0x02000200u) | (evm & 0x100u) | (evm & ((x & 0x70u) == 0u ? 0x01000000u : 0u)));
+}
+/* write-back: the victim's words first (unchanged without an eviction), then the request's,
+ * which hold both where they coincide; a lane that does not take the step writes the four
+ * words back as it read them (a select of the value: no flag on the store, no dummy word) */
+template <class M>
+DSM_HD void ser_simple_store(M &m, const SSimple &t, bool en) {
+    m.st(S_DS + t.vh, en ? t.dsV2 : t.dsV);
+    m.st(t.wV, en ? t.mbV2 : t.mbV);
+    m.st(S_DS + t.h, en ? t.dsH2 : t.dsH);
+    m.st(t.wH, en ? t.mbH2 : t.mbH);
+}
+/* what the general path says of the same step (the host model's counts only) */
+template <class M>
+DSM_HD STxn ser_solo_front(M &m, uint32_t ins, uint32_t ct, uint32_t la, uint32_t lv, uint32_t n, uint32_t bit) {
+    STxn t;
+    ser_txn_front(m, t, ins, ct, la, lv, n, bit, [](int) {});
+    return t;
+}
+template <int NP, class M>
+DSM_HD uint32_t ser_solo_cause(M &m, uint32_t ins, uint32_t ct, uint32_t la, uint32_t lv, uint32_t n, uint32_t bit) {
+    const STxn t = ser_solo_front(m, ins, ct, la, lv, n, bit);
+    const bool home = (!((NP == 8) || (t.h < (uint32_t)NP))) | ((t.dH == 0u) & t.miss & (t.bvH == 0u));
+    return home ? SOLO_HOME : t.fwd ? SOLO_FWD : t.fan ? SOLO_FAN : SOLO_NOTICE;
+}
+
 template <int NP, class M>
 DSM_HD uint32_t ser_solo(M &m, SReg &r, SCache &cc, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
                          uint32_t lim_rsh) {
     constexpr uint32_t NPM = (1u << NP) - 1u;
     const uint32_t n = s_ctz(r.A), bit = 1u << n, nins = s_ni(r, n);
     uint32_t ct = cc.ct, la = cc.la, lv = cc.lv;
-    uint32_t rounds = r.rounds, msgs = r.msgs, steps = 0u;
-    const uint32_t j0 = (ct >> SC_IP) & 7u;
+    const uint32_t ip0 = ct >> SC_IP, j0 = ip0 & 7u, base = ip0 & ~7u;
     SER_COUNT_SOLO_ENTRY(j0);
-    bool go = true;
+    /* jm: bit j set for the slots the lane may take -- from j0 up to the trace's end (a lane
+     * applies its slots in order, so slot j holds instruction base + j) */
+    const uint32_t left = nins > base ? s_min(nins - base, 8u) : 0u;
+    const uint32_t jm = (0xFFu << j0) & ((1u << left) - 1u);
+    /* acc: the run's rounds in bits 24-31, on top of a start value that sets bit 31 once the round
+     * limit is within reach (ser_quiet_lone's test: rounds + SER_MACRO_MAX_ROUNDS + 1 >= the
+     * limit; a run adds at most 8 x 4), its steps in bits 16-19, its messages in bits 8-15; bit
+     * 23: the lane has stopped */
+    constexpr uint32_t ACC_STOPPED = 1u << 23, ACC_LIMIT = 1u << 31;
+    const uint32_t near = r.rounds + SER_MACRO_MAX_ROUNDS + 1u, cap = 1u << lim_rsh;
+    const uint32_t acc0 = (0x80u - (near >= cap ? 0u : s_min(cap - near, 0x80u))) << 24;
+    uint32_t acc = acc0;
 #ifdef __clang__
 #pragma unroll
 #endif
     for (uint32_t j = 0; j < 8u; ++j) {
-        if (!s_any(go)) break;
         const uint32_t w = j < 2u ? c0 : (j < 4u ? c1 : (j < 6u ? c2 : c3));
         const uint32_t ins = (w >> (16u * (j & 1u))) & 0xFFFFu;
-        const bool act = go & (j >= j0);
-        STxn t;
-        ser_txn_front(m, t, ins, ct, la, lv, n, bit, [](int) {});
-        const bool end = (ct >> SC_IP) >= nins;
-        const bool lim = ((rounds + SER_MACRO_MAX_ROUNDS + 1u) >> lim_rsh) != 0u;
-        const bool home = (!((NP == 8) || (t.h < (uint32_t)NP))) | ((t.dH == 0u) & t.miss & (t.bvH == 0u));
-        const bool simple = !(end | lim | home | t.fwd | t.notice | t.fan);
-        const bool en = act & simple;
-        if (act & !simple)
-            SER_COUNT_SOLO_STOP(end ? SOLO_TRACE_END : lim ? SOLO_ROUND_LIMIT : home ? SOLO_HOME :
-                                t.fwd ? SOLO_FWD : t.fan ? SOLO_FAN : SOLO_NOTICE, j);
-        go = go & (!act | simple);
-        SHome hm;
-        ser_txn_home(hm, t, bit, false, false, 0u);
-        if (en) SER_COUNT_MACRO(t.hit, t.upg, t.ev, t.mod, false, false, false, false, false, t.wr != 0u, false);
-        /* write-back as ser_macro's, every store under the lane's flag */
-        m.st_if(en & hm.req, S_DS + t.h, (t.dsH & ~(3u << t.shb)) | (hm.ndH << t.shb));
-        m.st_if(en & hm.req, t.wH, (t.mbH & ~(0xFFFFu << t.hh)) | ((hm.nmemH | (hm.nbvH << 8)) << t.hh));
-        m.st_if(en & t.ev & (t.vh != t.h), S_DS + t.vh, t.dsV2);
-        m.st_if(en & t.ev & (t.wV != t.wH), t.wV, t.mbV2);
-        const uint32_t nla = (la & ~(0xFFu << t.sh8)) | (t.a << t.sh8);
-        const uint32_t nlv = (lv & ~(0xFFu << t.sh8)) | (hm.nLv << t.sh8);
-        uint32_t nct = (ct & ~(3u << t.lsh)) | (hm.nLs << t.lsh);
-        nct = (t.wr ? ((nct & ~0xFFu) | t.val) : nct) + (1u << SC_IP);
-        la = en ? nla : la;
-        lv = en ? nlv : lv;
-        ct = en ? nct : ct;
-        /* rounds and messages as ser_macro's, without a forward, a notice or a fan-out */
-        const bool lone = t.hit & !t.upg;
-        const uint32_t treq = (t.ev & (t.vh == t.h)) ? 3u : 2u;
-        rounds += en ? (lone ? 1u : treq + 1u) : 0u;
-        msgs += en ? (lone ? 0u : (t.ev ? 1u : 0u) + 2u) : 0u;
-        steps += en ? 1u : 0u;
+        const uint32_t actm = s_mask(jm, j);
+        SSimple t;
+        ser_txn_simple<NP>(m, t, ins, ct, la, lv, n, bit);
+        const bool en = (t.stop | (acc & (ACC_STOPPED | ACC_LIMIT)) | ~actm) == 0u;
+        if (!(acc & ACC_STOPPED) && j >= j0 && j == left) SER_COUNT_SOLO_STOP(SOLO_TRACE_END, j);
+        if (!(acc & ACC_STOPPED) && actm && !en)
+            SER_COUNT_SOLO_STOP((acc & ACC_LIMIT) ? (uint32_t)SOLO_ROUND_LIMIT : ser_solo_cause<NP>(m, ins, ct, la, lv, n, bit), j);
+        if (en) SER_COUNT_MACRO(ser_solo_front(m, ins, ct, la, lv, n, bit).hit, ser_solo_front(m, ins, ct, la, lv, n, bit).upg,
+                                ser_solo_front(m, ins, ct, la, lv, n, bit).ev, ser_solo_front(m, ins, ct, la, lv, n, bit).mod,
+                                false, false, false, false, false, (ins >> 15) != 0u, false);
+        ser_simple_store(m, t, en);
+        la = en ? t.la : la;
+        lv = en ? t.lv : lv;
+        ct = en ? t.ct : ct;
+        acc = en ? acc + t.inc : (acc | (actm & ACC_STOPPED));
     }
+    const uint32_t steps = (acc >> 16) & 0xFu;
     m.st(S_LA + n, la);
     m.st(S_LV + n, lv);
     m.st(S_CT + n, ct);
     cc.ct = ct; cc.la = la; cc.lv = lv;
-    r.rounds = rounds;
-    r.msgs = msgs;
+    r.rounds += ((acc & ~ACC_STOPPED) - acc0) >> 24;
+    r.msgs += (acc >> 8) & 0xFFu;
     r.E = steps ? 0u : r.E;
     r.st = steps ? ((r.dmp == NPM) ? (uint32_t)SS_COMPLETED : (uint32_t)SS_DEADLOCKED) : r.st;
     return steps;
