@@ -105,6 +105,22 @@
  *                        check: cannot occur
  *                        check: not found; the exploration was truncated
  *                    with exit code 0, 4 or 3.
+ *   --fate TARGET    with --reach: the fate of the outcomes TARGET names -- a status (completed,
+ *                    deadlocked, ring_overflow, assert_failed, round_limit) or one outcome key
+ *                    0xKEY of --explore-kind -- in one dsm_reach_fate_device call in place of the
+ *                    plain search, under --reach-prob's thresholds when that is given.  After
+ *                    --reach's lines:
+ *                        fate TARGET: targets N doomed N safe N open N none N sealing N averting N
+ *                        fate first sealing: state S depth D rank J mask 0xMM -> state S'
+ *                        fate first averting: state S depth D rank J mask 0xMM -> state S'
+ *                        fate 0xT: lo P hi P
+ *                    (`none` in place of the edge where there is none; P as --reach-prob prints
+ *                    it: the probability of ending in TARGET from the root lies in [lo, hi]).
+ *                    With --explore-dir every outcome in TARGET also gets
+ *                    D/outcome_<k>/fate.txt: one line per state of its witness, root first,
+ *                        ROUND MASK STATE CLASS [LO per threshold]
+ *                    (the root's mask is 00).  Without --fate, --reach prints what it printed
+ *                    before.
  */
 #include <errno.h>
 #include <stdio.h>
@@ -122,12 +138,15 @@ static void usage(const char *argv0) {
                     "          [--explore-kind dumps|final|full] [--check DIR]] [--audit]\n"
                     "          [--events FILE [--events-kind instr|msg|all]]\n"
                     "          [--reach [--reach-states N] [--reach-depth D] [--reach-inbox L] [--reach-prob T[,T...]]\n"
+                    "          [--fate completed|deadlocked|ring_overflow|assert_failed|round_limit|0xKEY]\n"
                     "          [--explore-dir DIR]\n"
                     "          [--explore-kind dumps|final] [--check DIR]] <test_directory>\n", argv0);
 }
 
 static const char *const status_names[5] = {"COMPLETED", "DEADLOCKED", "RING_OVERFLOW", "ASSERT_FAILED",
                                             "ROUND_LIMIT"};
+static const char *const fate_targets[5] = {"completed", "deadlocked", "ring_overflow", "assert_failed", "round_limit"};
+static const char *const fate_classes[4] = {"NONE", "DOOMED", "SAFE", "OPEN"};
 
 /* "coherent", or "0x0c DIR_EM,DIR_S lines 3 first 0x15 bad 0" */
 static void print_audit_word(const char *prefix, uint32_t w) {
@@ -407,7 +426,8 @@ static void print_mass(uint64_t mass) {
  * code. */
 static int reach(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces, const uint32_t *counts,
                  unsigned long long max_states, uint32_t max_depth, uint32_t inbox, int kind, const char *out_dir,
-                 const char *check_dir, const uint32_t *prob_t, uint32_t n_prob) {
+                 const char *check_dir, const uint32_t *prob_t, uint32_t n_prob, const dsm_fate_opts *fate,
+                 const char *fate_name) {
     const size_t tr_bytes = (size_t)np * stride * sizeof(uint16_t);
     uint64_t *d_tmass = NULL, *tmass = NULL, *omass = NULL;
     dsm_dist_info dinfo[DSM_DIST_MAX_THRESH];
@@ -419,6 +439,10 @@ static int reach(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces, 
     dsm_reach_terminal *d_term = NULL, *term = NULL;
     uint64_t *cen = NULL;
     dsm_outcome *outc = NULL;
+    uint8_t *d_cls = NULL, *cls = NULL;
+    uint64_t *d_lo = NULL, *lo = NULL, *loff = NULL;
+    dsm_fate_info finfo;
+    dsm_fate_value fval[DSM_DIST_MAX_THRESH];
     dsm_reach_info info;
     dsm_reach_opts opts;
     int rc = DSM_OK, code = EXIT_FAILURE;
@@ -446,8 +470,19 @@ static int reach(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces, 
         hipMemcpy(d_tr, traces, tr_bytes, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(d_cn, counts, (size_t)np * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
         goto fail;
-    what = "dsm_reach_device";
-    if ((rc = dsm_reach_device(ctx, d_tr, d_cn, &opts, &info, d_par, d_msk, NULL, NULL, d_term, term_cap, NULL))) goto fail;
+    if (fate) {                                         /* the search and its fate in one call */
+        loff = (uint64_t *)malloc((DSM_REACH_MAX_LEVELS + 1) * sizeof(uint64_t));
+        if (!loff || hipMalloc((void **)&d_cls, (size_t)max_states) != hipSuccess ||
+            (n_prob && hipMalloc((void **)&d_lo, (size_t)n_prob * (size_t)max_states * sizeof(uint64_t)) != hipSuccess))
+            goto fail;
+        what = "dsm_reach_fate_device";
+        if ((rc = dsm_reach_fate_device(ctx, d_tr, d_cn, &opts, fate, prob_t, n_prob, &info, &finfo, fval, d_par, d_msk, loff,
+                                        d_term, term_cap, d_cls, d_lo, NULL, NULL)))
+            goto fail;
+    } else {
+        what = "dsm_reach_device";
+        if ((rc = dsm_reach_device(ctx, d_tr, d_cn, &opts, &info, d_par, d_msk, NULL, NULL, d_term, term_cap, NULL))) goto fail;
+    }
     if (info.terminals > term_cap) { what = "too many terminal states for one census"; goto fail; }
     if (n_prob) {                                       /* the same search again, then the rounds */
         dsm_reach_info again;
@@ -469,6 +504,18 @@ static int reach(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces, 
     cen = (uint64_t *)calloc(DSM_CENSUS_WORDS(cap), sizeof(uint64_t));
     outc = (dsm_outcome *)malloc((size_t)cap * sizeof(dsm_outcome));
     if (!par || !msk || !path || !term || !cen || !outc) goto fail;
+    if (fate) {
+        cls = (uint8_t *)malloc((size_t)info.states);
+        lo = (uint64_t *)malloc((size_t)(n_prob ? n_prob : 1) * (size_t)info.states * sizeof(uint64_t));
+        if (!cls || !lo) goto fail;
+        what = "read-back";
+        if (hipMemcpy(cls, d_cls, (size_t)info.states, hipMemcpyDeviceToHost) != hipSuccess) goto fail;
+        for (uint32_t j = 0; j < n_prob; ++j)
+            if (hipMemcpy(lo + (size_t)j * info.states, d_lo + (size_t)j * max_states, (size_t)info.states * sizeof(uint64_t),
+                          hipMemcpyDeviceToHost) != hipSuccess)
+                goto fail;
+        what = "out of memory";
+    }
     if (n_prob) {
         tmass = (uint64_t *)malloc((size_t)n_prob * (size_t)term_cap * sizeof(uint64_t));
         if (!tmass) goto fail;
@@ -544,6 +591,26 @@ static int reach(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces, 
             if (!f) goto fail;
             for (uint64_t r = 0; r < n; ++r) fprintf(f, "%02x\n", path[r]);
             if (fclose(f) != 0) goto fail;
+            if (fate && ((fate->status_mask >> st) & 1u) && (!fate->key || fate->key == outc[o].key)) {
+                /* the witness's states, root first: path[] is reused for nothing else below */
+                uint64_t ids[DSM_REACH_MAX_LEVELS + 1];
+                uint64_t s = t->state;
+                for (uint64_t r = n + 1; r-- > 0; s = par[s]) ids[r] = s;
+                snprintf(file, sizeof file, "%s/fate.txt", dir);
+                f = fopen(file, "w");
+                if (!f) goto fail;
+                for (uint64_t r = 0; r <= n; ++r) {
+                    fprintf(f, "%llu %02x %llu %s", (unsigned long long)r, r ? path[r - 1] : 0u, (unsigned long long)ids[r],
+                            fate_classes[cls[ids[r]] & 3u]);
+                    for (uint32_t j = 0; j < n_prob; ++j) {
+                        const unsigned __int128 v = ((unsigned __int128)lo[(size_t)j * info.states + ids[r]] * 1000000000000000000ull) >> 63;
+                        fprintf(f, " %llu.%018llu", (unsigned long long)(v / 1000000000000000000ull),
+                                (unsigned long long)(v % 1000000000000000000ull));
+                    }
+                    fprintf(f, "\n");
+                }
+                if (fclose(f) != 0) goto fail;
+            }
             rc = DSM_OK;
         }
     }
@@ -557,6 +624,29 @@ static int reach(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces, 
         printf(" escaped "); print_mass(d->escaped);
         printf(" residual "); print_mass(d->residual);
         printf(" rounds %llu\n", (unsigned long long)d->rounds);
+    }
+    if (fate) {
+        printf("fate %s: targets %llu doomed %llu safe %llu open %llu none %llu sealing %llu averting %llu\n", fate_name,
+               (unsigned long long)finfo.targets, (unsigned long long)finfo.by_class[DSM_FATE_DOOMED],
+               (unsigned long long)finfo.by_class[DSM_FATE_SAFE], (unsigned long long)finfo.by_class[DSM_FATE_OPEN],
+               (unsigned long long)finfo.by_class[DSM_FATE_NONE], (unsigned long long)finfo.seal_edges,
+               (unsigned long long)finfo.avert_edges);
+        if (finfo.flags & DSM_FATE_F_UNCONVERGED) printf("warning: the class sweeps hit their cap: classes are lower bounds\n");
+        for (int k = 0; k < 2; ++k) {
+            const dsm_fate_edge *e = k ? &finfo.first_avert : &finfo.first_seal;
+            uint64_t depth = 0;
+            printf("fate first %s: ", k ? "averting" : "sealing");
+            if (e->src == ~0ull) { printf("none\n"); continue; }
+            while (depth + 1 < info.levels && loff[depth + 1] <= e->src) ++depth;
+            printf("state %llu depth %llu rank %llu mask 0x%02llx -> state %llu\n", (unsigned long long)e->src,
+                   (unsigned long long)depth, (unsigned long long)e->rank, (unsigned long long)e->mask,
+                   (unsigned long long)e->dst);
+        }
+        for (uint32_t j = 0; j < n_prob; ++j) {
+            printf("fate 0x%x: lo ", prob_t[j]); print_mass(fval[j].root_lo);
+            printf(" hi "); print_mass(fval[j].root_hi);
+            printf("\n");
+        }
     }
     code = 0;
     if (check_dir) {
@@ -593,6 +683,9 @@ fail:
     if (d_msk) (void)hipFree(d_msk);
     if (d_term) (void)hipFree(d_term);
     if (d_tmass) (void)hipFree(d_tmass);
+    if (d_cls) (void)hipFree(d_cls);
+    if (d_lo) (void)hipFree(d_lo);
+    free(cls); free(lo); free(loff);
     free(tmass); free(omass);
     free(par); free(msk); free(path); free(term); free(cen); free(outc);
     return code;
@@ -603,6 +696,8 @@ int main(int argc, char **argv) {
     long long reach_states = 1ll << 22, reach_depth = 0, reach_inbox = 16;
     int reach_opts = 0;
     uint32_t prob_t[DSM_DIST_MAX_THRESH], n_prob = 0;
+    dsm_fate_opts fate_opts;
+    const char *fate_name = NULL;
     uint32_t max_instr = DSM_REF_MAX_INSTR;
     const char *dir = NULL, *issue_file = NULL;
     unsigned long long sched_seed = 0;
@@ -642,6 +737,20 @@ int main(int argc, char **argv) {
                 if (*end != ',') { usage(argv[0]); return EXIT_FAILURE; }
                 v = end + 1;
             }
+        }
+        else if (!strcmp(argv[i], "--fate") && i + 1 < argc) {
+            const char *v = argv[++i];
+            char *end = NULL;
+            reach_opts = 1;
+            memset(&fate_opts, 0, sizeof fate_opts);
+            for (uint32_t k = 0; k < 5; ++k)
+                if (!strcmp(v, fate_targets[k])) fate_opts.status_mask = 1u << k;
+            if (!fate_opts.status_mask && v[0] == '0' && (v[1] == 'x' || v[1] == 'X')) {
+                fate_opts.key = strtoull(v, &end, 16);
+                if (*end == '\0' && end != v + 2 && fate_opts.key) fate_opts.status_mask = DSM_FATE_STATUS_ALL;
+            }
+            if (!fate_opts.status_mask) { usage(argv[0]); return EXIT_FAILURE; }
+            fate_name = v;
         }
         else if (!strcmp(argv[i], "--explore-dir") && i + 1 < argc) { explore_dir = argv[++i]; explore_opts = 1; }
         else if (!strcmp(argv[i], "--check") && i + 1 < argc) { check_dir = argv[++i]; explore_opts = 1; }
@@ -743,7 +852,8 @@ int main(int argc, char **argv) {
 
     if (do_reach) {
         const int code = reach(ctx, np, stride, traces, counts, (unsigned long long)reach_states, (uint32_t)reach_depth,
-                               (uint32_t)reach_inbox, explore_kind, explore_dir, check_dir, prob_t, n_prob);
+                               (uint32_t)reach_inbox, explore_kind, explore_dir, check_dir, prob_t, n_prob,
+                               fate_name ? &fate_opts : NULL, fate_name);
         dsm_close(ctx);
         free(traces);
         return code;

@@ -11,11 +11,13 @@
  *   dsm_events.hip   event trace: the replay kernel, its host twin and the formatter
  *   dsm_reach.hip    exhaustive exploration: the search kernels, the host search, witnesses;
  *                    the exclusive scan
- *   dsm_dist.hip     outcome distribution: the edge list and the rounds, the host reference
- * The last three replay ONE system a round at a time: the round is dsm_step.h's st_round, once,
- * under dsm_events.h's and dsm_reach.h's inbox and log policies, the hashes are dsm_hash.h's, and
- * dsm_reach_dev.h holds the device plumbing dsm_reach.hip and dsm_dist.hip share.
- * Each kernel is launched from the unit that defines it.  Not part of the ABI.
+ *   dsm_dist.hip     outcome distribution: the rounds over the edge list, the host reference
+ *   dsm_fate.hip     outcome fate: the class and value sweeps over the edge list, the host reference
+ * The last four replay ONE system a round at a time: the round is dsm_step.h's st_round, once,
+ * under dsm_events.h's and dsm_reach.h's inbox and log policies, the hashes are dsm_hash.h's,
+ * dsm_reach_dev.h holds the device plumbing dsm_reach.hip, dsm_dist.hip and dsm_fate.hip share, and
+ * dsm_dist_dev.h the edge list (its kernels and its host twin) of the last two.
+ * Each kernel is launched from the unit that defines or instantiates it.  Not part of the ABI.
  */
 #ifndef DSM_INTERNAL_H
 #define DSM_INTERNAL_H
@@ -141,6 +143,11 @@ extern "C" int dsm_debug_dist_edges_device(dsm_ctx *c, const uint16_t *d_trace, 
  * the environment (tools/dist_time.py): milliseconds on the stream per phase -- search, rebuild
  * (with classes and offsets), table, edges, push (all rounds of all thresholds). */
 extern "C" int dsm_debug_dist_times(double *ms);
+/* The same of the last dsm_reach_fate_device call that ran with DSM_FATE_TIMING=1 in the
+ * environment (tools/fate_time.py): seven phases -- search, rebuild, table, edges, marks and class
+ * sweeps, value sweeps, the rest -- and, in sweeps[2] (may be NULL), the class sweeps and the most
+ * value sweeps any threshold took. */
+extern "C" int dsm_debug_fate_times(double *ms, uint64_t *sweeps);
 
 /* Test-only (not part of the ABI): dsm_exscan_launch with tile sums of its own, waited for --
  * d_out[0 .. n] = the exclusive scan of d_in[0 .. n) in 64 bits, d_out[n] the total. */

@@ -84,6 +84,10 @@ class ReachOpts(ctypes.Structure):
                 ("chunk", ctypes.c_uint32)]
 
 
+class FateOpts(ctypes.Structure):
+    _fields_ = [("status_mask", ctypes.c_uint32), ("max_sweeps", ctypes.c_uint32), ("key", ctypes.c_uint64)]
+
+
 RESUME_FORMS = {0: "none", 1: "lock-step", 2: "serial", 3: "fast-forward lock-step"}
 
 
@@ -188,7 +192,14 @@ def lib():
             "dsm_reach_dist": (i32, [i32, vp, vp, u32, ctypes.POINTER(ReachOpts), vp, u32, u32, vp, vp, vp, vp, u64, vp]),
             "dsm_reach_dist_device": (i32, [vp, vp, vp, ctypes.POINTER(ReachOpts), vp, u32, u32, vp, vp, vp, vp, u64,
                                             vp, vp]),
+            # ABI 5 (+fate): the outcome fate
+            "dsm_reach_fate": (i32, [i32, vp, vp, u32, ctypes.POINTER(ReachOpts), ctypes.POINTER(FateOpts), vp, u32,
+                                     vp, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp]),
+            "dsm_reach_fate_device": (i32, [vp, vp, vp, ctypes.POINTER(ReachOpts), ctypes.POINTER(FateOpts), vp, u32,
+                                            vp, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, vp]),
+            "dsm_fate_seal_point": (i32, [vp, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
             # test-only (csrc/dsm_internal.h, not in include/dsm.h)
+            "dsm_debug_fate_times": (i32, [vp, vp]),
             "dsm_debug_dist_edges": (i32, [i32, vp, vp, u32, ctypes.POINTER(ReachOpts), vp, vp, vp, u64,
                                            ctypes.POINTER(u64)]),
             "dsm_debug_dist_edges_device": (i32, [vp, vp, vp, ctypes.POINTER(ReachOpts), vp, vp, vp, u64,
@@ -641,6 +652,101 @@ def reach_dist(np_, traces, counts, thresh=(0x8000,), max_rounds=0, inbox_limit=
     return _dist_result(_reach_terminals_result(info, terms, kind), kind, dinfo, term_mass, round_mass)
 
 
+# -- outcome fate (ABI 5 +fate) ---------------------------------------------------------------
+FATE_CAN_TARGET, FATE_CAN_OTHER = 1, 2
+FATE_NONE, FATE_DOOMED, FATE_SAFE, FATE_OPEN = 0, 1, 2, 3
+FATE_CLASS_NAMES = ["NONE", "DOOMED", "SAFE", "OPEN"]
+FATE_F_TRUNCATED, FATE_F_INEXACT, FATE_F_UNCONVERGED = 1, 2, 4
+FATE_STATUS_ALL = 0x1F
+FATE_NO_EDGE = (1 << 64) - 1
+FATE_INFO_FIELDS = ("targets", "cls0", "cls1", "cls2", "cls3", "seal_edges", "avert_edges",
+                    "seal_src", "seal_rank", "seal_mask", "seal_dst", "avert_src", "avert_rank", "avert_mask",
+                    "avert_dst", "edges", "missing_edges", "sweeps", "flags", "reserved0", "reserved1")
+FATE_VALUE_FIELDS = ("thresh", "root_lo", "root_hi", "max_slack", "sweeps", "flags", "reserved0", "reserved1")
+
+
+def fate_info_to_dict(v):
+    a = dict(zip(FATE_INFO_FIELDS, (int(x) for x in v)))
+    out = {k: a[k] for k in ("targets", "seal_edges", "avert_edges", "edges", "missing_edges", "sweeps", "flags")}
+    out["by_class"] = [a[f"cls{i}"] for i in range(4)]
+    for kind in ("seal", "avert"):
+        out[f"first_{kind}"] = {f: a[f"{kind}_{f}"] for f in ("src", "rank", "mask", "dst")}
+    out["reserved"] = [a["reserved0"], a["reserved1"]]
+    return out
+
+
+def fate_value_to_dict(v):
+    a = dict(zip(FATE_VALUE_FIELDS, (int(x) for x in v)))
+    a["reserved"] = [a.pop("reserved0"), a.pop("reserved1")]
+    return a
+
+
+def fate_target(target):
+    """A target as the CLI names it -> (status_mask, key): a status name, a list of them, an int
+    status mask, or ("key", K[, mask])."""
+    if isinstance(target, str):
+        return 1 << [n.lower() for n in STATUS_NAMES].index(target.lower()), 0
+    if isinstance(target, int):
+        return target, 0
+    if len(target) and target[0] == "key":
+        return (target[2] if len(target) > 2 else FATE_STATUS_ALL), int(target[1])
+    m = 0
+    for t in target:
+        m |= fate_target(t)[0]
+    return m, 0
+
+
+def _fate_result(info, finfo, values, parents, masks, level_off, terms, kind, cls, lo, hi, nth):
+    d = reach_info_to_dict(info)
+    n, nt = d["states"], min(d["terminals"], len(terms))
+    return {"info": d, "fate": fate_info_to_dict(finfo), "values": [fate_value_to_dict(values[j]) for j in range(nth)],
+            "parents": parents[:n], "masks": masks[:n], "level_off": level_off[:d["levels"] + 1], "terminals": terms[:nt],
+            "cls": cls[:n], "lo": lo[:nth, :n], "hi": hi[:nth, :n]}
+
+
+def reach_fate(np_, traces, counts, target="deadlocked", thresh=(0x8000,), max_sweeps=0, inbox_limit=16,
+               kind=CENSUS_DUMPS, max_states=1 << 22, max_depth=0, term_cap=None):
+    """dsm_reach_fate (the host reference; no GPU) of ONE system -> a dict: info (the search's),
+    fate (dsm_fate_info), values (one dsm_fate_value per threshold), parents, masks, level_off,
+    terminals, cls (uint8 per state), lo and hi (uint64 [n_thresh, states])."""
+    traces = np.ascontiguousarray(traces, dtype=np.uint16)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+    assert traces.ndim == 2 and traces.shape[0] == np_ and counts.shape == (np_,)
+    kind = CENSUS_KINDS.get(kind, kind)
+    th = np.ascontiguousarray(thresh, dtype=np.uint32).reshape(-1)
+    mask, key = fate_target(target)
+    opts = ReachOpts(inbox_limit, kind, max_states, max_depth, 0)
+    fopts = FateOpts(mask, max_sweeps, key)
+    n = max_states if 0 < max_states <= 1 << 31 else 1
+    term_cap = min(n, 1 << 20) if term_cap is None else term_cap
+    nth = len(th)
+    info = np.zeros(len(REACH_INFO_FIELDS), dtype=np.uint64)
+    finfo = np.zeros(len(FATE_INFO_FIELDS), dtype=np.uint64)
+    values = np.zeros((max(nth, 1), len(FATE_VALUE_FIELDS)), dtype=np.uint64)
+    parents, masks, cls = np.zeros(n, np.uint32), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+    level_off = np.zeros(REACH_MAX_LEVELS + 1, dtype=np.uint64)
+    terms = np.zeros(max(term_cap, 1), dtype=REACH_TERMINAL_DTYPE)
+    lo, hi = np.zeros((max(nth, 1), n), np.uint64), np.zeros((max(nth, 1), n), np.uint64)
+    _check(lib().dsm_reach_fate(np_, _ptr(traces), _ptr(counts), traces.shape[1], ctypes.byref(opts), ctypes.byref(fopts),
+                                _ptr(th) if nth else None, nth, _ptr(info), _ptr(finfo), _ptr(values), _ptr(parents),
+                                _ptr(masks), _ptr(level_off), _ptr(terms), term_cap, _ptr(cls), _ptr(lo), _ptr(hi)),
+           "dsm_reach_fate")
+    return _fate_result(info, finfo, values, parents, masks, level_off, terms, kind, cls, lo, hi, nth)
+
+
+def fate_seal_point(parents, cls, state):
+    """dsm_fate_seal_point -> (the first state of `state`'s witness, root first, that is not OPEN, or
+    None; its depth, or the depth of `state`)."""
+    parents = np.ascontiguousarray(parents, dtype=np.uint32)
+    cls = np.ascontiguousarray(cls, dtype=np.uint8)
+    if not 0 <= state < min(len(parents), len(cls)):
+        raise DsmError(E_INVAL, "fate_seal_point: state")
+    s, d = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    _check(lib().dsm_fate_seal_point(_ptr(parents), _ptr(cls), state, ctypes.byref(s), ctypes.byref(d)),
+           "dsm_fate_seal_point")
+    return (None if s.value == FATE_NO_EDGE else s.value), d.value
+
+
 def _reach_terminals_result(info, terms, kind):
     d = reach_info_to_dict(info)
     nt = min(d["terminals"], len(terms))
@@ -946,6 +1052,57 @@ class Engine:
         terms = d_term.cpu().numpy().view(REACH_TERMINAL_DTYPE)
         term_mass = d_tm.cpu().numpy().view(np.uint64).reshape(nth, term_cap)
         return _dist_result(_reach_terminals_result(info, terms, kind), kind, dinfo, term_mass, round_mass)
+
+    def reach_fate_device(self, d_trace, d_counts, opts, fopts, thresh, rinfo, finfo, values, d_parents, d_masks,
+                          level_off, d_terminals, term_cap, d_cls, d_lo, d_hi, stream=0):
+        """dsm_reach_fate_device: device pointers or tensors for the trace, counts, parents, masks,
+        terminals, cls, lo and hi; thresh (uint32), rinfo, finfo, values and level_off numpy arrays
+        (host); each output may be None.  Synchronous."""
+        n = 0 if thresh is None else len(thresh)
+        return lib().dsm_reach_fate_device(self.ctx, _dptr(d_trace), _dptr(d_counts),
+                                           None if opts is None else ctypes.byref(opts),
+                                           None if fopts is None else ctypes.byref(fopts),
+                                           _ptr(thresh) if n else None, n, _ptr(rinfo), _ptr(finfo),
+                                           _ptr(values), _dptr(d_parents), _dptr(d_masks), _ptr(level_off),
+                                           _dptr(d_terminals), term_cap, _dptr(d_cls), _dptr(d_lo), _dptr(d_hi),
+                                           ctypes.c_void_p(stream))
+
+    def reach_fate(self, traces, counts, target="deadlocked", thresh=(0x8000,), max_sweeps=0, inbox_limit=16,
+                   kind=CENSUS_DUMPS, max_states=1 << 22, max_depth=0, chunk=0, term_cap=None):
+        """The fate of ONE system's reach graph for a target set, on the GPU -> the dict of
+        pydsm.reach_fate."""
+        import torch
+        tr, cn = np.array(traces, dtype=np.uint16), np.array(counts, dtype=np.uint32)
+        if tr.shape != (self.np, self.max_instr) or cn.shape != (self.np,):
+            raise DsmError(E_INVAL, "reach_fate: one system of the engine's np and max_instr")
+        kind = CENSUS_KINDS.get(kind, kind)
+        th = np.ascontiguousarray(thresh, dtype=np.uint32).reshape(-1)
+        mask, key = fate_target(target)
+        dev = torch.device("cuda", self.device)
+        d_tr = torch.from_numpy(tr.view(np.int16).reshape(-1)).to(dev)
+        d_cn = torch.from_numpy(cn.view(np.int32)).to(dev)
+        n = max_states if 0 < max_states <= 1 << 31 else 1
+        term_cap = max(min(n, 1 << 20) if term_cap is None else term_cap, 1)
+        nth = len(th)
+        d_par = torch.zeros(n, dtype=torch.int32, device=dev)
+        d_msk = torch.zeros(n, dtype=torch.uint8, device=dev)
+        d_cls = torch.zeros(n, dtype=torch.uint8, device=dev)
+        d_lo = torch.zeros(max(nth, 1) * n, dtype=torch.int64, device=dev)
+        d_hi = torch.zeros(max(nth, 1) * n, dtype=torch.int64, device=dev)
+        d_term = torch.zeros(5 * term_cap, dtype=torch.int64, device=dev)
+        info = np.zeros(len(REACH_INFO_FIELDS), dtype=np.uint64)
+        finfo = np.zeros(len(FATE_INFO_FIELDS), dtype=np.uint64)
+        values = np.zeros((max(nth, 1), len(FATE_VALUE_FIELDS)), dtype=np.uint64)
+        level_off = np.zeros(REACH_MAX_LEVELS + 1, dtype=np.uint64)
+        opts = ReachOpts(inbox_limit, kind, max_states, max_depth, chunk)
+        fopts = FateOpts(mask, max_sweeps, key)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _check(self.reach_fate_device(d_tr, d_cn, opts, fopts, th, info, finfo, values, d_par, d_msk, level_off, d_term,
+                                      term_cap, d_cls, d_lo, d_hi, st), "dsm_reach_fate_device")
+        return _fate_result(info, finfo, values, d_par.cpu().numpy().view(np.uint32), d_msk.cpu().numpy(), level_off,
+                            d_term.cpu().numpy().view(REACH_TERMINAL_DTYPE), kind, d_cls.cpu().numpy(),
+                            d_lo.cpu().numpy().view(np.uint64).reshape(max(nth, 1), n),
+                            d_hi.cpu().numpy().view(np.uint64).reshape(max(nth, 1), n), nth)
 
     def explore(self, traces, counts, k, seed, thresh=0x8000, kind=CENSUS_DUMPS, audit=False):
         """k seeded interleavings of ONE system (traces [np, max_instr] u16, counts [np]) in

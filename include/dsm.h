@@ -56,7 +56,9 @@ extern "C" {
                              5 (+reach): additive -- the exhaustive exploration (dsm_reach*,
                                 dsm_census_insert) likewise;
                              5 (+dist): additive -- the outcome distribution (dsm_sched_prob,
-                                dsm_reach_dist*) likewise */
+                                dsm_reach_dist*) likewise;
+                             5 (+fate): additive -- the outcome fate (dsm_reach_fate*,
+                                dsm_fate_seal_point) likewise */
 
 #define DSM_MAX_NP 8             /* bitVector is one byte (README.md:51)                  */
 #define DSM_CACHE_SIZE 4         /* CACHE_SIZE      assignment.c:10                        */
@@ -803,6 +805,118 @@ int dsm_reach_dist_device(dsm_ctx *ctx, const uint16_t *d_trace, const uint32_t 
                           uint32_t max_rounds, dsm_reach_info *rinfo, dsm_dist_info *dinfo,
                           dsm_reach_terminal *d_terminals, uint64_t *d_term_mass, uint64_t term_cap,
                           uint64_t *round_mass, void *stream);
+
+/* ---- outcome fate: where a reachable outcome becomes inevitable ---------------------------- *
+ * The reach graph read backwards, for a chosen set of outcomes: from which states the set is still
+ * avoidable, from which it is certain, and with which probability it is reached from every state.
+ *
+ * Graph: dsm_reach's, with the edge list dsm_reach_dist defines.  Every expanded running state u
+ * with enabled set A has one edge per non-empty subset of A in ascending order of the mask: the
+ * edge of rank j = 1 .. 2^|A| - 1 has the mask j deposited into A's set bits, and its target is
+ * found by fingerprint (else it is a missing edge).  States are running, escaped (running, but of
+ * the unexpanded last level of a truncated search) or terminal, as in the outcome distribution.
+ *
+ * Target set T: the terminal states whose status (low 8 bits) has its bit set in status_mask and,
+ * when key != 0, whose dsm_outcome_key(opts->kind, &res) equals key.  status_mask holds bits 0..4
+ * (1 << DSM_COMPLETED .. 1 << DSM_ROUND_LIMIT); 0, or any higher bit, is DSM_E_INVAL.  T may be
+ * empty.
+ *
+ * Class byte of a state: the least fixed point of two reachability bits.  DSM_FATE_CAN_TARGET:
+ * the state is in T, or some edge leads to a state with the bit.  DSM_FATE_CAN_OTHER: the state is
+ * a terminal not in T, or some edge leads to a state with the bit.  An escaped state has both
+ * bits, and so has the source of a missing edge: anything may follow them, so DOOMED and SAFE stay
+ * sound under truncation.  DSM_FATE_DOOMED: only T can follow; DSM_FATE_SAFE: T cannot follow;
+ * DSM_FATE_OPEN: both can; DSM_FATE_NONE: a running state from which no path ends (on a cycle
+ * only).
+ *
+ * Decisive edges: a sealing edge goes from an OPEN state to a DOOMED one, an averting edge from an
+ * OPEN state to a SAFE one.  The info counts both kinds and names the first of each: lowest source
+ * id, then lowest rank (all four fields ~0 when there is none).
+ *
+ * Values per threshold t, P = dsm_sched_prob(t, ., .), the least fixed points of
+ *   lo(u)   = DSM_DIST_ONE for u in T, 0 for any other terminal or escaped state, and for a
+ *             running state the sum over its edges of umul64hi(lo(dst), P[k, m]), a missing edge
+ *             contributing 0;
+ *   rest(u) = the same with the roles of T and the other terminals exchanged;
+ *   hi(u)   = DSM_DIST_ONE - rest(u).
+ * The sums cannot overflow (sum P <= 2^64, values <= 2^63).  Both iterations are monotone from 0,
+ * so any order of updates reaches the same fixed point: host and device agree bit for bit.
+ * lo(u) <= p_T(u) <= hi(u) for the true probability of ending in T from u, at every moment of the
+ * iteration; hi - lo (slack) covers the rounding loss and, in a truncated search, what escapes.
+ *
+ * max_sweeps (0 = 4096) caps the updates of the whole state set, for the classes and for the
+ * values each.  A cap that bites sets DSM_FATE_F_UNCONVERGED (in the info for the classes, in a
+ * value for its threshold): classes and values are then still sound (a class is a subset of the
+ * true bits, lo and hi bounds) but host and device are not comparable.  The `sweeps` fields are
+ * implementation-defined. */
+#define DSM_FATE_CAN_TARGET 1u
+#define DSM_FATE_CAN_OTHER 2u
+#define DSM_FATE_NONE 0u
+#define DSM_FATE_DOOMED 1u
+#define DSM_FATE_SAFE 2u
+#define DSM_FATE_OPEN 3u
+#define DSM_FATE_F_TRUNCATED 1u    /* DSM_REACH_F_STATES or DSM_REACH_F_DEPTH                   */
+#define DSM_FATE_F_INEXACT 2u      /* DSM_REACH_F_COLLISION, or missing_edges != 0              */
+#define DSM_FATE_F_UNCONVERGED 4u  /* max_sweeps reached before a sweep changed nothing         */
+#define DSM_FATE_STATUS_ALL 0x1Fu
+typedef struct dsm_fate_opts {
+    uint32_t status_mask;      /* bit s: terminals of status s are targets                    */
+    uint32_t max_sweeps;       /* 0 = 4096                                                    */
+    uint64_t key;              /* 0 = any outcome of those statuses                           */
+} dsm_fate_opts;
+typedef struct dsm_fate_edge {
+    uint64_t src, rank, mask, dst;
+} dsm_fate_edge;
+typedef struct dsm_fate_info {
+    uint64_t targets;          /* states in T                                                 */
+    uint64_t by_class[4];      /* states per class byte                                       */
+    uint64_t seal_edges, avert_edges;
+    dsm_fate_edge first_seal, first_avert;
+    uint64_t edges;            /* successors of every expanded state, duplicates included     */
+    uint64_t missing_edges;
+    uint64_t sweeps;           /* class sweeps made                                           */
+    uint64_t flags;            /* DSM_FATE_F_*                                                */
+    uint64_t reserved[2];      /* zero                                                        */
+} dsm_fate_info;
+typedef struct dsm_fate_value {
+    uint64_t thresh;
+    uint64_t root_lo, root_hi; /* lo and hi of state 0                                        */
+    uint64_t max_slack;        /* the largest hi - lo of any state                            */
+    uint64_t sweeps;           /* value sweeps made                                           */
+    uint64_t flags;            /* DSM_FATE_F_*                                                */
+    uint64_t reserved[2];      /* zero                                                        */
+} dsm_fate_value;
+/* The host reference (no GPU needed): dsm_reach, the edge list as dsm_reach_dist builds it, then
+ * plain in-place sweeps in descending id order.  thresh[n_thresh], 0 <= n_thresh <=
+ * DSM_DIST_MAX_THRESH, each 1..65536; with n_thresh == 0 only classes are computed and thresh may
+ * be NULL.  rinfo, level_off, parents, masks and terminals are dsm_reach's, passed through.
+ * cls[max_states]; lo and hi [n_thresh][max_states]: lo[j * max_states + id].  Every output may
+ * be NULL; entries at and after rinfo->states are not written.  A bad argument is DSM_E_INVAL
+ * with nothing written. */
+int dsm_reach_fate(int np, const uint16_t *trace, const uint32_t *counts, uint32_t stride,
+                   const dsm_reach_opts *opts, const dsm_fate_opts *fopts, const uint32_t *thresh,
+                   uint32_t n_thresh, dsm_reach_info *rinfo, dsm_fate_info *finfo,
+                   dsm_fate_value *values, uint32_t *parents, uint8_t *masks, uint64_t *level_off,
+                   dsm_reach_terminal *terminals, uint64_t term_cap, uint8_t *cls, uint64_t *lo,
+                   uint64_t *hi);
+/* The same on the GPU (dsm_reach_device's search, the edge list of dsm_reach_dist_device, then
+ * fate_*_kernel).  d_parents, d_masks, d_terminals, d_cls, d_lo and d_hi are device buffers
+ * (d_terminals, d_lo and d_hi 8-byte aligned, d_parents 4-byte); thresh, rinfo, finfo, values and
+ * level_off host memory.  SYNCHRONOUS like dsm_reach_dist_device; everything it allocates is freed
+ * before it returns: DSM_E_NOMEM with nothing leaked when it does not fit. */
+int dsm_reach_fate_device(dsm_ctx *ctx, const uint16_t *d_trace, const uint32_t *d_counts,
+                          const dsm_reach_opts *opts, const dsm_fate_opts *fopts,
+                          const uint32_t *thresh, uint32_t n_thresh, dsm_reach_info *rinfo,
+                          dsm_fate_info *finfo, dsm_fate_value *values, uint32_t *d_parents,
+                          uint8_t *d_masks, uint64_t *level_off, dsm_reach_terminal *d_terminals,
+                          uint64_t term_cap, uint8_t *d_cls, uint64_t *d_lo, uint64_t *d_hi,
+                          void *stream);
+/* Where a state's witness was decided (host only): the first state on the path from the root to
+ * `id` over parents, root first, whose class is not DSM_FATE_OPEN.  *state = that state and
+ * *depth = its depth; when every state of the path is OPEN, *state = ~0 and *depth = the depth of
+ * id.  DSM_E_INVAL for arrays that are not a search's (a parent not below its child). */
+int dsm_fate_seal_point(const uint32_t *parents, const uint8_t *cls, uint64_t id, uint64_t *state,
+                        uint64_t *depth);
 
 /* ---- multi-GPU group: RCCL over xGMI --------------------------------------- *
  * Systems are independent, so an ensemble shards over GPUs with no data-path exchange; the
