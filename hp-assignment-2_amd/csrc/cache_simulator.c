@@ -121,6 +121,16 @@
  *                        ROUND MASK STATE CLASS [LO per threshold]
  *                    (the root's mask is 00).  Without --fate, --reach prints what it printed
  *                    before.
+ *   --reach-batch    a screen of many tests: every positional argument is a test directory (one
+ *                    or more), all read with one dsm_parse_traces call and all searched with one
+ *                    dsm_reach_batch_device call.  Takes --reach-states (default 65536, at most
+ *                    1048576 per test), --reach-depth, --reach-inbox and --explore-kind dumps|final;
+ *                    any other mode flag is a usage error.  Per directory, in argument order:
+ *                        <dir>: reached S states, T transitions, K outcomes (exhaustive) completed a deadlocked b ring_overflow c assert_failed d
+ *                    (or --reach's `(truncated at ...: not exhaustive)` text; a .. d count
+ *                    terminal states), then
+ *                        screened N tests: D can deadlock, X exhaustive
+ *                    Exits 2 when D > 0, else 3 when any search was truncated, else 0.
  */
 #include <errno.h>
 #include <stdio.h>
@@ -140,7 +150,10 @@ static void usage(const char *argv0) {
                     "          [--reach [--reach-states N] [--reach-depth D] [--reach-inbox L] [--reach-prob T[,T...]]\n"
                     "          [--fate completed|deadlocked|ring_overflow|assert_failed|round_limit|0xKEY]\n"
                     "          [--explore-dir DIR]\n"
-                    "          [--explore-kind dumps|final] [--check DIR]] <test_directory>\n", argv0);
+                    "          [--explore-kind dumps|final] [--check DIR]] <test_directory>\n"
+                    "       %s [--np 4|8] [--max-instr N] [--device D] [--quiet] --reach-batch [--reach-states N]\n"
+                    "          [--reach-depth D] [--reach-inbox L] [--explore-kind dumps|final] <test_directory>...\n",
+            argv0, argv0);
 }
 
 static const char *const status_names[5] = {"COMPLETED", "DEADLOCKED", "RING_OVERFLOW", "ASSERT_FAILED",
@@ -691,8 +704,139 @@ fail:
     return code;
 }
 
+/* tests/<dir>/core_<n>.txt appended to *text at *len (:794-800: a missing file ends the program) */
+static int append_core_file(const char *dir, int n, char **text, uint64_t *len) {
+    char path[256];
+    snprintf(path, sizeof path, "tests/%s/core_%d.txt", dir, n);   /* :794 */
+    FILE *f = fopen(path, "rb");
+    if (!f) {                                                      /* :796-800 */
+        fprintf(stderr, "Error: could not open file %s\n", path);
+        perror("fopen");
+        exit(EXIT_FAILURE);
+    }
+    char buf[1 << 16];
+    size_t k;
+    while ((k = fread(buf, 1, sizeof buf, f)) > 0) {
+        char *t = (char *)realloc(*text, *len + k);
+        if (!t) { fclose(f); return -1; }
+        *text = t;
+        memcpy(*text + *len, buf, k);
+        *len += k;
+    }
+    fclose(f);
+    return 0;
+}
+
+/* --reach-batch: the tests of dirs read with one dsm_parse_traces call and searched with one
+ * dsm_reach_batch_device call; a line per test and the screen's summary.  Returns the process
+ * exit code. */
+static int reach_batch(int np, uint32_t max_instr, int device, char **dirs, int n_dirs,
+                       unsigned long long max_states, uint32_t max_depth, uint32_t inbox, int kind) {
+    const uint32_t stride = (max_instr + 7u) & ~7u;
+    const uint64_t n_files = (uint64_t)n_dirs * (uint64_t)np;
+    const uint64_t term_cap = max_states < (DSM_CENSUS_MAX_CAP / 2) ? max_states : (DSM_CENSUS_MAX_CAP / 2);
+    const size_t tr_bytes = (size_t)n_files * stride * sizeof(uint16_t), cn_bytes = (size_t)n_files * sizeof(uint32_t);
+    char *text = NULL;
+    uint64_t *off = (uint64_t *)calloc((size_t)n_files + 1, sizeof(uint64_t));
+    uint16_t *traces = (uint16_t *)calloc((size_t)n_files * stride, sizeof(uint16_t)), *d_tr = NULL;
+    uint32_t *counts = (uint32_t *)calloc((size_t)n_files, sizeof(uint32_t)), *d_cn = NULL;
+    int32_t *pst = (int32_t *)calloc((size_t)n_files, sizeof(int32_t));
+    dsm_reach_info *info = (dsm_reach_info *)calloc((size_t)n_dirs, sizeof *info), *d_info = NULL;
+    dsm_reach_terminal *term = (dsm_reach_terminal *)malloc((size_t)term_cap * sizeof *term), *d_term = NULL;
+    uint64_t *cen = NULL;
+    dsm_ctx *ctx = NULL;
+    dsm_reach_opts opts;
+    dsm_config cfg;
+    int rc = DSM_OK, code = EXIT_FAILURE;
+    const char *what = "out of memory";
+    if (!off || !traces || !counts || !pst || !info || !term) goto fail;
+    for (uint64_t f = 0; f < n_files; ++f) {
+        uint64_t len = off[f];
+        if (append_core_file(dirs[f / (uint64_t)np], (int)(f % (uint64_t)np), &text, &len)) goto fail;
+        off[f + 1] = len;
+    }
+    memset(&cfg, 0, sizeof cfg);
+    cfg.np = np;
+    cfg.max_instr = stride;
+    what = "dsm_open";
+    if ((rc = dsm_open(device, &cfg, &ctx))) goto fail;
+    what = "dsm_parse_traces";
+    if ((rc = dsm_parse_traces(ctx, text ? text : "", off, n_files, max_instr, traces, counts, pst))) goto fail;
+    for (uint64_t f = 0; f < n_files; ++f) {
+        if (pst[f]) {
+            fprintf(stderr, "Error: tests/%s/core_%d.txt: %s (instruction %u)\n", dirs[f / (uint64_t)np], (int)(f % (uint64_t)np),
+                    dsm_strerror(pst[f]), counts[f]);
+            what = NULL;
+            rc = DSM_OK;
+            goto fail;
+        }
+    }
+    memset(&opts, 0, sizeof opts);
+    opts.inbox_limit = inbox; opts.kind = (uint32_t)kind; opts.max_states = max_states; opts.max_depth = max_depth;
+    what = "device memory";
+    rc = DSM_OK;
+    if (hipMalloc((void **)&d_tr, tr_bytes) != hipSuccess || hipMalloc((void **)&d_cn, cn_bytes) != hipSuccess ||
+        hipMalloc((void **)&d_info, (size_t)n_dirs * sizeof *info) != hipSuccess ||
+        hipMalloc((void **)&d_term, (size_t)n_dirs * (size_t)term_cap * sizeof *term) != hipSuccess ||
+        hipMemcpy(d_tr, traces, tr_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_cn, counts, cn_bytes, hipMemcpyHostToDevice) != hipSuccess)
+        goto fail;
+    what = "dsm_reach_batch_device";
+    if ((rc = dsm_reach_batch_device(ctx, d_tr, d_cn, (uint64_t)n_dirs, &opts, 0, d_info, d_term, term_cap, NULL, NULL, NULL)))
+        goto fail;
+    what = "read-back";
+    if (hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(info, d_info, (size_t)n_dirs * sizeof *info, hipMemcpyDeviceToHost) != hipSuccess)
+        goto fail;
+    uint64_t n_dead = 0, n_exh = 0;
+    for (int s = 0; s < n_dirs; ++s) {
+        const dsm_reach_info *r = &info[s];
+        uint32_t cap = DSM_CENSUS_MIN_CAP;
+        uint64_t k = 0;
+        if (r->terminals > term_cap) { what = "too many terminal states for one census"; goto fail; }
+        while (cap < 2 * r->terminals) cap <<= 1;
+        free(cen);
+        what = "out of memory";
+        if (!(cen = (uint64_t *)calloc(DSM_CENSUS_WORDS(cap), sizeof(uint64_t)))) goto fail;
+        what = "read-back";
+        if (r->terminals && hipMemcpy(term, d_term + (size_t)s * term_cap, (size_t)r->terminals * sizeof *term,
+                                      hipMemcpyDeviceToHost) != hipSuccess)
+            goto fail;
+        what = "dsm_census_insert";
+        for (uint64_t t = 0; t < r->terminals; ++t)
+            if ((rc = dsm_census_insert(cen, cap, dsm_outcome_key(kind, &term[t].res), term[t].state))) goto fail;
+        k = cen[1];                                     /* the header's distinct keys */
+        const int truncated = (r->flags & (DSM_REACH_F_STATES | DSM_REACH_F_DEPTH)) != 0;
+        printf("%s: reached %llu states, %llu transitions, %llu outcomes ", dirs[s], (unsigned long long)r->states,
+               (unsigned long long)r->transitions, (unsigned long long)k);
+        if (truncated) printf("(truncated at %llu states / depth %u: not exhaustive)", max_states, max_depth);
+        else printf("(exhaustive)");
+        printf(" completed %llu deadlocked %llu ring_overflow %llu assert_failed %llu\n",
+               (unsigned long long)r->by_status[DSM_COMPLETED], (unsigned long long)r->by_status[DSM_DEADLOCKED],
+               (unsigned long long)r->by_status[DSM_RING_OVERFLOW], (unsigned long long)r->by_status[DSM_ASSERT_FAILED]);
+        if (r->flags & DSM_REACH_F_COLLISION)
+            printf("warning: %llu fingerprint collisions: the result is not exact\n", (unsigned long long)r->fp_collisions);
+        n_dead += r->by_status[DSM_DEADLOCKED] != 0;
+        n_exh += !truncated;
+    }
+    printf("screened %d tests: %llu can deadlock, %llu exhaustive\n", n_dirs, (unsigned long long)n_dead,
+           (unsigned long long)n_exh);
+    code = n_dead ? 2 : n_exh != (uint64_t)n_dirs ? 3 : 0;
+    what = NULL;
+    rc = DSM_OK;
+fail:
+    if (what) fprintf(stderr, "Error: reach batch: %s%s%s\n", what, rc ? ": " : "", rc ? dsm_strerror(rc) : "");
+    if (d_tr) (void)hipFree(d_tr);
+    if (d_cn) (void)hipFree(d_cn);
+    if (d_info) (void)hipFree(d_info);
+    if (d_term) (void)hipFree(d_term);
+    if (ctx) dsm_close(ctx);
+    free(text); free(off); free(traces); free(counts); free(pst); free(info); free(term); free(cen);
+    return code;
+}
+
 int main(int argc, char **argv) {
-    int np = 4, device = 0, quiet = 0, audit = 0, do_reach = 0;
+    int np = 4, device = 0, quiet = 0, audit = 0, do_reach = 0, do_batch = 0, n_dirs = 0, states_set = 0;
     long long reach_states = 1ll << 22, reach_depth = 0, reach_inbox = 16;
     int reach_opts = 0;
     uint32_t prob_t[DSM_DIST_MAX_THRESH], n_prob = 0;
@@ -722,7 +866,8 @@ int main(int argc, char **argv) {
             if (explore_n < 1 || explore_n > (long long)DSM_CENSUS_MAX_CAP) { usage(argv[0]); return EXIT_FAILURE; }
         }
         else if (!strcmp(argv[i], "--reach")) do_reach = 1;
-        else if (!strcmp(argv[i], "--reach-states") && i + 1 < argc) { reach_states = atoll(argv[++i]); reach_opts = 1; }
+        else if (!strcmp(argv[i], "--reach-batch")) do_batch = 1;
+        else if (!strcmp(argv[i], "--reach-states") && i + 1 < argc) { reach_states = atoll(argv[++i]); reach_opts = states_set = 1; }
         else if (!strcmp(argv[i], "--reach-depth") && i + 1 < argc) { reach_depth = atoll(argv[++i]); reach_opts = 1; }
         else if (!strcmp(argv[i], "--reach-inbox") && i + 1 < argc) { reach_inbox = atoll(argv[++i]); reach_opts = 1; }
         else if (!strcmp(argv[i], "--reach-prob") && i + 1 < argc) {
@@ -772,12 +917,24 @@ int main(int argc, char **argv) {
             else { usage(argv[0]); return EXIT_FAILURE; }
         }
         else if (argv[i][0] == '-' && argv[i][1] == '-') { usage(argv[0]); return EXIT_FAILURE; }
-        else dir = argv[i];
+        else { dir = argv[i]; argv[1 + n_dirs++] = argv[i]; }          /* the positionals, in order, at argv[1 ..] */
     }
     if (!dir) { usage(argv[0]); return EXIT_FAILURE; }                 /* :119-122 */
     if ((np != 4 && np != 8) || max_instr == 0 || max_instr > DSM_MAX_INSTR) {
         usage(argv[0]);
         return EXIT_FAILURE;
+    }
+    if (do_batch) {
+        if (!states_set) reach_states = 1ll << 16;
+        if (do_reach || explore_n || have_sched || events_file || events_opts || issue_file || audit || explore_dir ||
+            check_dir || n_prob || fate_name || explore_kind == DSM_CENSUS_FULL || reach_states < 1 ||
+            reach_states > (long long)DSM_REACH_BATCH_MAX_STATES || reach_depth < 0 ||
+            reach_depth >= (long long)DSM_REACH_MAX_LEVELS || reach_inbox < 1 || reach_inbox > 16) {
+            usage(argv[0]);
+            return EXIT_FAILURE;
+        }
+        return reach_batch(np, max_instr, device, argv + 1, n_dirs, (unsigned long long)reach_states,
+                           (uint32_t)reach_depth, (uint32_t)reach_inbox, explore_kind);
     }
     if ((explore_n && issue_file) || (!explore_n && !do_reach && explore_opts)) { usage(argv[0]); return EXIT_FAILURE; }
     if ((reach_opts && !do_reach) ||
@@ -797,25 +954,8 @@ int main(int argc, char **argv) {
     char *text = NULL;
     uint64_t off[DSM_MAX_NP + 1] = {0};
     for (int n = 0; n < np; ++n) {
-        char path[256];
-        snprintf(path, sizeof path, "tests/%s/core_%d.txt", dir, n);   /* :794 */
-        FILE *f = fopen(path, "rb");
-        if (!f) {                                                      /* :796-800 */
-            fprintf(stderr, "Error: could not open file %s\n", path);
-            perror("fopen");
-            exit(EXIT_FAILURE);
-        }
-        char buf[1 << 16];
-        size_t k;
         uint64_t len = off[n];
-        while ((k = fread(buf, 1, sizeof buf, f)) > 0) {
-            char *t = (char *)realloc(text, len + k);
-            if (!t) { fclose(f); return EXIT_FAILURE; }
-            text = t;
-            memcpy(text + len, buf, k);
-            len += k;
-        }
-        fclose(f);
+        if (append_core_file(dir, n, &text, &len)) return EXIT_FAILURE;
         off[n + 1] = len;
     }
     dsm_config cfg;

@@ -13,6 +13,8 @@
  *                    the exclusive scan
  *   dsm_dist.hip     outcome distribution: the rounds over the edge list, the host reference
  *   dsm_fate.hip     outcome fate: the class and value sweeps over the edge list, the host reference
+ *   dsm_reach_batch.hip  reach batch: the search of many small systems, one workgroup each, in
+ *                    one asynchronous launch; its host loop
  * The last four replay ONE system a round at a time: the round is dsm_step.h's st_round, once,
  * under dsm_events.h's and dsm_reach.h's inbox and log policies, the hashes are dsm_hash.h's,
  * dsm_reach_dev.h holds the device plumbing dsm_reach.hip, dsm_dist.hip and dsm_fate.hip share, and
@@ -102,6 +104,11 @@ struct dsm_ctx {
     /* dsm_events.hip */
     uint32_t *d_ev_scratch;          /* replay_kernel: per-lane system state (dsm_events.h)   */
     size_t ev_scratch_cap;
+    /* dsm_reach_batch.hip */
+    unsigned char *d_rb_scratch;     /* reach_batch_kernel: one slab per workgroup in flight   */
+    size_t rb_scratch_cap;
+    unsigned long long *d_rb_claim;  /*   and the claim counter, zeroed on the stream per call */
+    uint64_t rb_in_flight;           /* workgroups of the last call                           */
 };
 
 #define HIPCK(x) do { if ((x) != hipSuccess) return DSM_E_DEVICE; } while (0)
@@ -149,6 +156,10 @@ extern "C" int dsm_debug_dist_times(double *ms);
  * value sweeps any threshold took. */
 extern "C" int dsm_debug_fate_times(double *ms, uint64_t *sweeps);
 
+/* Measurement-only view of the last dsm_reach_batch_device call (not part of the ABI;
+ * tools/reach_batch_time.py): the systems it kept in flight and the bytes of the ctx's scratch. */
+extern "C" int dsm_debug_reach_batch_state(dsm_ctx *c, uint64_t *in_flight, uint64_t *scratch_bytes);
+
 /* Test-only (not part of the ABI): dsm_exscan_launch with tile sums of its own, waited for --
  * d_out[0 .. n] = the exclusive scan of d_in[0 .. n) in 64 bits, d_out[n] the total. */
 extern "C" int dsm_debug_exscan_device(dsm_ctx *c, const uint32_t *d_in, uint64_t n, uint64_t *d_out, void *stream);
@@ -157,6 +168,8 @@ extern "C" int dsm_debug_exscan_device(dsm_ctx *c, const uint32_t *d_in, uint64_
 void dsm_text_release(dsm_ctx *c);
 /* dsm_events.hip: called by dsm_close */
 void dsm_events_release(dsm_ctx *c);
+/* dsm_reach_batch.hip: called by dsm_close */
+void dsm_reach_batch_release(dsm_ctx *c);
 
 /* dsm_sim.hip: the transition kernel of a launch -- the fast kernel of (ring, mode), nullptr
  * where the dispatch has none, and the 256-deep re-run kernel; its resident workgroups per CU

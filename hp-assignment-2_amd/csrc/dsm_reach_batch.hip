@@ -1,0 +1,454 @@
+/*
+ * dsm_reach_batch.hip -- the reach batch (include/dsm.h, dsm_reach_batch*): the exhaustive
+ * exploration of MANY small systems in one asynchronous launch.
+ *
+ * dsm_reach.hip searches one system with a handful of launches and a host wait per level and per
+ * chunk; a system of a few thousand states is then all launches and waits.  Here the whole
+ * breadth-first search of a system runs inside ONE workgroup of RT lanes, and the kernel
+ * boundaries of dsm_reach.hip become barriers:
+ *
+ *   reach_batch_kernel<NP>    a grid of W persistent workgroups, each with a slab of device memory
+ *                             of its own.  A workgroup claims the next system id with one atomic
+ *                             add (agent scope) on a counter the stream zeroed, searches the system
+ *                             to its end, writes info[s] and the system's rows of the outputs, and
+ *                             claims again until the ids run out.  No workgroup waits for another.
+ *
+ * Per level, in the workgroup (the algorithm and the numbering are dsm_reach.hip's):
+ *   count       a lane per state of the level, a tile of RT at a time: enabled set, successor
+ *               count, terminal flag, deepest inbox; one workgroup scan of the tile carries both
+ *               the successor offsets (low word) and the terminal ranks (high word), so the
+ *               terminals are written in id order in the same pass
+ *   per chunk of the level's candidates, in order:
+ *   expand      a lane per candidate: dsm_reach_dev.h's successor (rs_round in place in the chunk
+ *               buffer, the micro-op table in LDS), the fingerprint, and the insert into the
+ *               visited table (compare-and-swap on the key, max on meta with ~candidate)
+ *   resolve     a candidate is new exactly when it owns its slot; a non-owner whose owner is in
+ *               the same chunk compares the two full states (the collision count)
+ *   settle      a tile of RT candidates at a time: a workgroup scan of the new-flags gives the
+ *               ids; owners write meta = settled | id and move to the store with parent and mask
+ * Everything between two barriers touches the slab of this workgroup alone, so the table's atomics
+ * are workgroup scope and __syncthreads orders the phases.
+ *
+ * Slab reuse: the visited table is RE-ZEROED, whole, by the workgroup when it claims a system (so
+ * the scratch needs no initialisation either); every other array of the slab is written before it
+ * is read within one system.
+ *
+ * Every loop is bounded: levels by DSM_REACH_MAX_LEVELS, probes by the slot count, chunks by the
+ * level's total, claims by n_sys (a workgroup stops at its first id >= n_sys).
+ *
+ * Host side of the same unit: dsm_reach_batch (a plain loop of dsm_reach), the slab's layout, and
+ * the ctx-owned scratch.
+ */
+#include <stdint.h>
+#include <string.h>
+
+#include "dsm_reach_dev.h"
+
+namespace {
+
+constexpr u64 SETTLED = 1ull << 63;
+constexpr uint32_t BATCH_DEFAULT_CHUNK = 1024;   /* measured: DESIGN.md, "Reach batch" */
+constexpr uint32_t NO_SLOT = 0xFFFFFFFFu;
+constexpr int WAVE = 64;
+
+DSM_HD u64 pending_of(u64 j) { return ~j & ~SETTLED; }
+
+/* one system's slab: byte offsets of its arrays (each a multiple of 16) */
+struct Slab {
+    u64 slots;                    /* of the visited table, a power of two >= 2 (max_states + chunk) */
+    u64 o_table;                  /* slots x {key, meta}                                            */
+    u64 o_offs;                   /* max_states + 1 x u64: the level's successor offsets            */
+    u64 o_store;                  /* RS_WORDS rows of max_states words: the numbered states         */
+    u64 o_cand;                   /* RS_WORK rows of chunk words: the chunk's candidates            */
+    u64 o_cpar, o_cslot;          /* chunk x u32: a candidate's parent, its slot                    */
+    u64 o_A;                      /* max_states x u8: the level's enabled sets                      */
+    u64 o_cmask, o_new;           /* chunk x u8: a candidate's mask, its new-flag                   */
+    u64 bytes;
+};
+
+inline u64 up16(u64 x) { return (x + 15u) & ~(u64)15u; }
+
+/* the batch's conditions on top of dsm_reach's */
+int batch_opts_ok(int np, const dsm_reach_opts *o, uint32_t *L) {
+    if ((np != 4 && np != 8) || !opts_ok(o, L)) return 0;
+    return o->max_states <= DSM_REACH_BATCH_MAX_STATES && o->chunk <= DSM_REACH_BATCH_MAX_CHUNK;
+}
+
+Slab slab_of(int np, const dsm_reach_opts *o) {
+    const u64 cap = o->max_states, chunk = o->chunk ? o->chunk : BATCH_DEFAULT_CHUNK;
+    Slab s;
+    s.slots = 64;
+    while (s.slots < 2 * (cap + chunk)) s.slots <<= 1;
+    u64 at = 0;
+    s.o_table = at; at = up16(at + s.slots * 16);
+    s.o_offs = at;  at = up16(at + (cap + 1) * 8);
+    s.o_store = at; at = up16(at + (u64)RS_WORDS(np) * cap * 4);
+    s.o_cand = at;  at = up16(at + (u64)RS_WORK(np) * chunk * 4);
+    s.o_cpar = at;  at = up16(at + chunk * 4);
+    s.o_cslot = at; at = up16(at + chunk * 4);
+    s.o_A = at;     at = up16(at + cap);
+    s.o_cmask = at; at = up16(at + chunk);
+    s.o_new = at;   at = up16(at + chunk);
+    s.bytes = at;
+    return s;
+}
+
+struct BatchArgs {
+    StepArgs step;                /* trace and counts: system 0's; the kernel offsets them */
+    u64 n_sys, cap, chunk;
+    uint32_t max_depth;
+    Slab slab;
+    unsigned char *slabs;         /* gridDim.x slabs */
+    u64 *claim;
+    u64 *info;                    /* dsm_reach_info: 14 words a system */
+    u64 *terminals;               /* dsm_reach_terminal: 5 words each */
+    u64 term_cap;
+    uint32_t *parents;
+    uint8_t *masks;
+};
+
+constexpr int INFO_WORDS = 14;
+static_assert(sizeof(dsm_reach_info) == INFO_WORDS * 8, "the kernel writes dsm_reach_info as words");
+static_assert(sizeof(dsm_reach_terminal) == 40, "the kernel writes dsm_reach_terminal as five words");
+
+/* exclusive scan of one value per lane over the workgroup; *total = the sum.  Every lane calls it. */
+__device__ __forceinline__ u64 wg_exscan(u64 v, u64 *s_w, u64 *total) {
+    const uint32_t lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
+    u64 x = v;
+#pragma unroll
+    for (int off = 1; off < WAVE; off <<= 1) {
+        const u64 y = __shfl_up(x, off, WAVE);
+        if (lane >= (uint32_t)off) x += y;
+    }
+    __syncthreads();                          /* the last call's readers of s_w are done */
+    if (lane == WAVE - 1) s_w[w] = x;
+    __syncthreads();
+    u64 before = 0, tot = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < (uint32_t)(RT / WAVE); ++k) {
+        const u64 s = s_w[k];
+        before += k < w ? s : 0;
+        tot += s;
+    }
+    *total = tot;
+    return before + x - v;
+}
+
+/* dsm_reach.hip's stop_before_expand */
+__device__ __forceinline__ bool stop_level(uint32_t max_depth, u64 depth, u64 total, u64 *flags) {
+    if (total == 0) return true;
+    if ((max_depth && depth >= max_depth) || depth + 1 >= DSM_REACH_MAX_LEVELS) {
+        *flags |= DSM_REACH_F_DEPTH;
+        return true;
+    }
+    return false;
+}
+
+template <int NP>
+__global__ void __launch_bounds__(RT) reach_batch_kernel(const BatchArgs a) {
+    __shared__ uint32_t s_tab[DT_TABLE_WORDS];
+    __shared__ u64 s_w[RT / WAVE];
+    __shared__ u64 s_sys;
+    __shared__ uint32_t s_by[8], s_fill, s_coll;
+    const uint32_t t = threadIdx.x;
+    table_to_lds(s_tab, a.step.table);
+
+    unsigned char *slab = a.slabs + (size_t)blockIdx.x * a.slab.bytes;
+    u64 *table = reinterpret_cast<u64 *>(slab + a.slab.o_table);
+    u64 *offs = reinterpret_cast<u64 *>(slab + a.slab.o_offs);
+    uint32_t *store = reinterpret_cast<uint32_t *>(slab + a.slab.o_store);
+    uint32_t *cand = reinterpret_cast<uint32_t *>(slab + a.slab.o_cand);
+    uint32_t *cpar = reinterpret_cast<uint32_t *>(slab + a.slab.o_cpar);
+    uint32_t *cslot = reinterpret_cast<uint32_t *>(slab + a.slab.o_cslot);
+    uint8_t *A = slab + a.slab.o_A;
+    uint8_t *cmask = slab + a.slab.o_cmask;
+    uint8_t *newflag = slab + a.slab.o_new;
+    const u64 cap = a.cap, chunk = a.chunk, slots = a.slab.slots;
+
+    for (;;) {
+        __syncthreads();                      /* the last system's info has been written */
+        if (t == 0) {
+            s_sys = __hip_atomic_fetch_add(a.claim, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (int k = 0; k < 8; ++k) s_by[k] = 0;
+            s_fill = 0;
+            s_coll = 0;
+        }
+        __syncthreads();
+        const u64 sys = s_sys;
+        if (sys >= a.n_sys) break;
+        StepArgs step = a.step;
+        step.trace += (size_t)sys * NP * step.stride;
+        step.counts += (size_t)sys * NP;
+        u64 *terminals = a.terminals ? a.terminals + (size_t)sys * a.term_cap * 5 : nullptr;
+        uint32_t *parents = a.parents ? a.parents + (size_t)sys * cap : nullptr;
+        uint8_t *masks = a.masks ? a.masks + (size_t)sys * cap : nullptr;
+
+        /* the slab's table, emptied; then the root */
+        {
+            uint4 *t4 = reinterpret_cast<uint4 *>(table);
+            for (u64 i = t; i < slots; i += RT) t4[i] = make_uint4(0u, 0u, 0u, 0u);
+        }
+        __syncthreads();
+        if (t == 0) {
+            const StMem m = {store, (size_t)cap};
+            rs_init<NP>(m);
+            const u64 fp = rs_fingerprint<NP>(m);
+            table[2 * (fp & (slots - 1))] = fp;
+            table[2 * (fp & (slots - 1)) + 1] = SETTLED;
+            if (parents) parents[0] = 0u;
+            if (masks) masks[0] = 0u;
+        }
+        __syncthreads();
+
+        u64 states = 1, lo = 0, hi = 1, depth = 0, transitions = 0, nterm = 0, max_frontier = 0, flags = 0;
+        uint32_t fillmax = 0, coll = 0;
+        for (;;) {
+            const u64 nf = hi - lo;
+            if (nf > max_frontier) max_frontier = nf;
+            /* count, offsets and terminals of the level, a tile at a time */
+            u64 total = 0;
+            for (u64 base = 0; base < nf; base += RT) {
+                const u64 i = base + t;
+                const bool valid = i < nf;
+                const StMem m = {store + lo + (valid ? i : 0), (size_t)cap};
+                uint32_t cnt = 0;
+                bool term = false;
+                if (valid) {
+                    const uint32_t en = rs_enabled<NP>(m, step.counts, step.stride);
+                    term = rs_terminal<NP>(m, en, nullptr);
+                    A[i] = (uint8_t)en;
+                    cnt = term ? 0u : (1u << __builtin_popcount(en)) - 1u;
+                    const uint32_t f = rs_max_fill<NP>(m);
+                    fillmax = f > fillmax ? f : fillmax;
+                }
+                u64 tile;
+                const u64 ex = wg_exscan((u64)cnt | ((u64)(term ? 1u : 0u) << 32), s_w, &tile);
+                if (valid) offs[i] = total + (ex & 0xFFFFFFFFull);
+                if (term) {
+                    dsm_sys_result res;
+                    (void)rs_terminal<NP>(m, 0u, &res);
+                    atomicAdd(&s_by[res.status & 7u], 1u);
+                    const u64 k = nterm + (ex >> 32);
+                    if (terminals && k < a.term_cap) {
+                        u64 *o = terminals + 5 * k;
+                        o[0] = lo + i;
+                        o[1] = (u64)res.status;          /* rounds 0 */
+                        o[2] = 0;                        /* msgs, instrs 0 */
+                        o[3] = res.dump_hash;
+                        o[4] = res.final_hash;
+                    }
+                }
+                total += tile & 0xFFFFFFFFull;
+                nterm += tile >> 32;
+            }
+            if (t == 0) offs[nf] = total;
+            __syncthreads();
+            if (stop_level(a.max_depth, depth, total, &flags)) break;
+            transitions += total;
+
+            u64 fresh = states;
+            for (u64 c0 = 0; c0 < total && fresh <= cap; c0 += chunk) {
+                const u64 n = total - c0 < chunk ? total - c0 : chunk;
+                /* expand and insert */
+                for (u64 j = t; j < n; j += RT) {
+                    u64 p;
+                    uint32_t mask;
+                    const StMem m = successor<NP>(store + lo, (size_t)cap, nf, offs, A, c0 + j, cand + j, (size_t)chunk,
+                                                  s_tab, step, &p, &mask);
+                    const u64 fp = rs_fingerprint<NP>(m);
+                    cpar[j] = (uint32_t)(lo + p);
+                    cmask[j] = (uint8_t)mask;
+                    u64 s = fp & (slots - 1);
+                    uint32_t found = NO_SLOT;
+                    for (u64 q = 0; q < slots; ++q, s = (s + 1) & (slots - 1)) {
+                        u64 k = __hip_atomic_load(&table[2 * s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        if (k == 0) {
+                            if (__hip_atomic_compare_exchange_strong(&table[2 * s], &k, fp, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                                     __HIP_MEMORY_SCOPE_WORKGROUP))
+                                k = fp;
+                        }
+                        if (k == fp) {
+                            __hip_atomic_fetch_max(&table[2 * s + 1], pending_of(j), __ATOMIC_RELAXED,
+                                                   __HIP_MEMORY_SCOPE_WORKGROUP);
+                            found = (uint32_t)s;
+                            break;
+                        }
+                    }
+                    cslot[j] = found;         /* NO_SLOT cannot happen: slots >= 2 (max_states + chunk) */
+                }
+                __syncthreads();
+                /* resolve */
+                for (u64 j = t; j < n; j += RT) {
+                    const uint32_t s = cslot[j];
+                    uint8_t isnew = 0;
+                    if (s != NO_SLOT) {
+                        const u64 meta = __hip_atomic_load(&table[2 * (u64)s + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        if (meta == pending_of(j)) {
+                            isnew = 1;
+                        } else if (!(meta & SETTLED)) {   /* the owner is candidate o of this chunk, o < j */
+                            const u64 o = ~meta & ~SETTLED;
+                            bool same = true;
+                            for (uint32_t i = 0; i < RS_WORDS(NP); ++i)
+                                same = same && cand[(size_t)i * chunk + j] == cand[(size_t)i * chunk + o];
+                            if (!same) ++coll;
+                        }
+                    }
+                    newflag[j] = isnew;
+                }
+                __syncthreads();
+                /* settle, in id order */
+                for (u64 base = 0; base < n; base += RT) {
+                    const u64 j = base + t;
+                    const uint32_t f = j < n ? newflag[j] : 0u;
+                    u64 tile;
+                    const u64 id = fresh + wg_exscan(f, s_w, &tile);
+                    if (f && id < cap) {      /* past max_states the level is dropped whole */
+                        __hip_atomic_store(&table[2 * (u64)cslot[j] + 1], SETTLED | id, __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_WORKGROUP);
+                        for (uint32_t i = 0; i < RS_WORDS(NP); ++i) store[(size_t)i * cap + id] = cand[(size_t)i * chunk + j];
+                        if (parents) parents[id] = cpar[j];
+                        if (masks) masks[id] = cmask[j];
+                    }
+                    fresh += tile;
+                }
+                __syncthreads();
+            }
+            if (fresh > cap) { flags |= DSM_REACH_F_STATES; break; }
+            if (fresh == states) break;
+            lo = states; hi = fresh; states = fresh;
+            ++depth;
+        }
+
+        atomicMax(&s_fill, fillmax);
+        atomicAdd(&s_coll, coll);
+        __syncthreads();
+        if (t == 0 && a.info) {
+            u64 *o = a.info + (size_t)sys * INFO_WORDS;
+            o[0] = states;
+            o[1] = transitions;
+            o[2] = nterm;
+            o[3] = depth + 1;
+            o[4] = max_frontier;
+            o[5] = s_fill;
+            for (int k = 0; k < 5; ++k) o[6 + k] = s_by[k];
+            o[11] = s_coll;
+            o[12] = flags | (s_coll ? DSM_REACH_F_COLLISION : 0u);
+            o[13] = 0;
+        }
+    }
+}
+
+template <int NP>
+int batch_launch(dsm_ctx *c, const BatchArgs &a, u64 budget, bool shrink, hipStream_t st) {
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reach_batch_kernel<NP>, RT, 0) != hipSuccess || per_cu < 1)
+        return DSM_E_DEVICE;
+    u64 w = (u64)per_cu * (u64)(c->cus > 0 ? c->cus : 1);
+    if (w > a.n_sys) w = a.n_sys;
+    if (w > budget / a.slab.bytes) w = budget / a.slab.bytes;
+    if (shrink && w > DSM_REACH_BATCH_DEFAULT_IN_FLIGHT) w = DSM_REACH_BATCH_DEFAULT_IN_FLIGHT;
+    /* Grow the scratch where it is too small.  An earlier call on the stream may still run in the old
+     * one, so growing waits for the device first; a call the scratch already holds waits for nothing.
+     * The default budget is a wish: where the device cannot give it, take what it can. */
+    while (!c->d_rb_scratch || c->rb_scratch_cap < w * a.slab.bytes) {
+        if (c->d_rb_scratch) {
+            HIPCK(hipDeviceSynchronize());
+            (void)hipFree(c->d_rb_scratch);
+            c->d_rb_scratch = nullptr;
+            c->rb_scratch_cap = 0;
+        }
+        if (hipMalloc((void **)&c->d_rb_scratch, (size_t)(w * a.slab.bytes)) == hipSuccess) {
+            c->rb_scratch_cap = (size_t)(w * a.slab.bytes);
+            break;
+        }
+        c->d_rb_scratch = nullptr;
+        (void)hipGetLastError();
+        if (!shrink || w <= 1) return DSM_E_NOMEM;
+        w /= 2;
+    }
+    if (!c->d_rb_claim && hipMalloc((void **)&c->d_rb_claim, 8) != hipSuccess) {
+        c->d_rb_claim = nullptr;
+        (void)hipGetLastError();
+        return DSM_E_NOMEM;
+    }
+    c->rb_in_flight = w;
+    BatchArgs b = a;
+    b.slabs = c->d_rb_scratch;
+    b.claim = reinterpret_cast<u64 *>(c->d_rb_claim);
+    HIPCK(hipMemsetAsync(c->d_rb_claim, 0, 8, st));
+    hipLaunchKernelGGL(reach_batch_kernel<NP>, dim3((unsigned)w), dim3(RT), 0, st, b);
+    HIPCK(hipGetLastError());
+    return DSM_OK;
+}
+
+}  // namespace
+
+void dsm_reach_batch_release(dsm_ctx *c) {
+    if (c->d_rb_scratch) (void)hipFree(c->d_rb_scratch);
+    if (c->d_rb_claim) (void)hipFree(c->d_rb_claim);
+    c->d_rb_scratch = nullptr;
+    c->d_rb_claim = nullptr;
+    c->rb_scratch_cap = 0;
+    c->rb_in_flight = 0;
+}
+
+extern "C" int dsm_debug_reach_batch_state(dsm_ctx *c, uint64_t *in_flight, uint64_t *scratch_bytes) {
+    if (!c || !in_flight || !scratch_bytes) return DSM_E_INVAL;
+    *in_flight = c->rb_in_flight;
+    *scratch_bytes = c->rb_scratch_cap;
+    return DSM_OK;
+}
+
+extern "C" uint64_t dsm_reach_batch_slab_bytes(int np, const dsm_reach_opts *opts) {
+    uint32_t L;
+    return batch_opts_ok(np, opts, &L) ? slab_of(np, opts).bytes : 0;
+}
+
+extern "C" int dsm_reach_batch(int np, const uint16_t *traces, const uint32_t *counts, uint32_t stride, uint64_t n_sys,
+                               const dsm_reach_opts *opts, dsm_reach_info *info, dsm_reach_terminal *terminals,
+                               uint64_t term_cap, uint32_t *parents, uint8_t *masks) {
+    uint32_t L;
+    if (!batch_opts_ok(np, opts, &L) || stride == 0 || stride > DSM_MAX_INSTR || (n_sys && (!traces || !counts)))
+        return DSM_E_INVAL;
+    for (uint64_t s = 0; s < n_sys; ++s) {
+        const int rc = dsm_reach(np, traces + (size_t)s * np * stride, counts + (size_t)s * np, stride, opts,
+                                 info ? info + s : nullptr, parents ? parents + (size_t)s * opts->max_states : nullptr,
+                                 masks ? masks + (size_t)s * opts->max_states : nullptr, nullptr, nullptr,
+                                 terminals ? terminals + (size_t)s * term_cap : nullptr, term_cap);
+        if (rc) return rc;
+    }
+    return DSM_OK;
+}
+
+extern "C" int dsm_reach_batch_device(dsm_ctx *c, const uint16_t *d_traces, const uint32_t *d_counts, uint64_t n_sys,
+                                      const dsm_reach_opts *opts, uint64_t scratch_bytes, dsm_reach_info *d_info,
+                                      dsm_reach_terminal *d_terminals, uint64_t term_cap, uint32_t *d_parents,
+                                      uint8_t *d_masks, void *stream) {
+    uint32_t L;
+    if (!c || !batch_opts_ok(c->cfg.np, opts, &L) || (n_sys && (!d_traces || !d_counts))) return DSM_E_INVAL;
+    if (((uintptr_t)d_info & 7u) || ((uintptr_t)d_terminals & 7u) || ((uintptr_t)d_parents & 3u)) return DSM_E_INVAL;
+    if (n_sys == 0) return DSM_OK;
+    BatchArgs a;
+    memset(&a, 0, sizeof a);
+    a.slab = slab_of(c->cfg.np, opts);
+    const u64 budget = scratch_bytes ? scratch_bytes : DSM_REACH_BATCH_DEFAULT_SCRATCH;
+    if (budget < a.slab.bytes) return DSM_E_NOMEM;
+    HIPCK(hipSetDevice(c->device));
+    a.step.trace = d_traces;
+    a.step.counts = d_counts;
+    a.step.table = reinterpret_cast<const uint32_t *>(c->d_table);
+    a.step.stride = c->cfg.max_instr;
+    a.step.L = L;
+    a.n_sys = n_sys;
+    a.cap = opts->max_states;
+    a.chunk = opts->chunk ? opts->chunk : BATCH_DEFAULT_CHUNK;
+    a.max_depth = opts->max_depth;
+    a.info = reinterpret_cast<u64 *>(d_info);
+    a.terminals = reinterpret_cast<u64 *>(d_terminals);
+    a.term_cap = term_cap;
+    a.parents = d_parents;
+    a.masks = d_masks;
+    const hipStream_t st = (hipStream_t)stream;
+    return c->cfg.np == 4 ? batch_launch<4>(c, a, budget, scratch_bytes == 0, st)
+                          : batch_launch<8>(c, a, budget, scratch_bytes == 0, st);
+}

@@ -184,6 +184,11 @@ def lib():
             # ABI 5 (+reach): the exhaustive exploration
             "dsm_reach": (i32, [i32, vp, vp, u32, ctypes.POINTER(ReachOpts), vp, vp, vp, vp, vp, vp, u64]),
             "dsm_reach_device": (i32, [vp, vp, vp, ctypes.POINTER(ReachOpts), vp, vp, vp, vp, vp, vp, u64, vp]),
+            # ABI 5 (+reach batch): a whole ensemble searched in one launch
+            "dsm_reach_batch_slab_bytes": (u64, [i32, ctypes.POINTER(ReachOpts)]),
+            "dsm_reach_batch": (i32, [i32, vp, vp, u32, u64, ctypes.POINTER(ReachOpts), vp, vp, u64, vp, vp]),
+            "dsm_reach_batch_device": (i32, [vp, vp, vp, u64, ctypes.POINTER(ReachOpts), u64, vp, vp, u64, vp, vp, vp]),
+            "dsm_debug_reach_batch_state": (i32, [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
             "dsm_reach_path": (i32, [vp, vp, u64, vp, u64, ctypes.POINTER(u64)]),
             "dsm_reach_replay": (i32, [i32, vp, vp, u32, u32, vp, u64, vp, vp, vp]),
             "dsm_census_insert": (i32, [vp, u32, u64, u64]),
@@ -541,6 +546,58 @@ def reach(np_, traces, counts, inbox_limit=16, kind=CENSUS_DUMPS, max_states=1 <
                            _ptr(parents), _ptr(masks), _ptr(fps), _ptr(level_off), _ptr(terms), term_cap),
            "dsm_reach")
     return _reach_result(info, parents, masks, fps, level_off, terms, kind)
+
+
+# -- reach batch (ABI 5 +reach batch) ---------------------------------------------------------
+REACH_BATCH_MAX_STATES = 1 << 20             # DSM_REACH_BATCH_MAX_STATES
+REACH_BATCH_MAX_CHUNK = 1 << 16              # DSM_REACH_BATCH_MAX_CHUNK
+REACH_INFO_DTYPE = np.dtype([("states", "<u8"), ("transitions", "<u8"), ("terminals", "<u8"), ("levels", "<u8"),
+                             ("max_frontier", "<u8"), ("max_fill", "<u8"), ("by_status", "<u8", (5,)),
+                             ("fp_collisions", "<u8"), ("flags", "<u8"), ("reserved", "<u8")])
+assert REACH_INFO_DTYPE.itemsize == 8 * len(REACH_INFO_FIELDS)
+
+
+def reach_batch_slab_bytes(np_, inbox_limit=16, kind=CENSUS_DUMPS, max_states=1 << 16, max_depth=0, chunk=0):
+    """dsm_reach_batch_slab_bytes: the device scratch one system in flight needs (0: bad options)."""
+    opts = ReachOpts(inbox_limit, CENSUS_KINDS.get(kind, kind), max_states, max_depth, chunk)
+    return int(lib().dsm_reach_batch_slab_bytes(np_, ctypes.byref(opts)))
+
+
+def _reach_many_result(info, terms, term_cap, parents, masks, max_states):
+    """The dict of reach_many from the batch's flat arrays."""
+    n = len(info)
+    terms = terms[:n * term_cap].reshape(n, term_cap)
+    out = {"info": info,
+           "terminals": [terms[s, :min(term_cap, int(info["terminals"][s]))] for s in range(n)],
+           "can_deadlock": info["by_status"][:, 1] > 0 if n else np.zeros(0, bool),
+           "exhaustive": (info["flags"] & (REACH_F_STATES | REACH_F_DEPTH)) == 0}
+    if parents is not None:
+        out["parents"] = [parents[s * max_states: s * max_states + int(info["states"][s])] for s in range(n)]
+        out["masks"] = [masks[s * max_states: s * max_states + int(info["states"][s])] for s in range(n)]
+    return out
+
+
+def reach_many(np_, traces, counts, inbox_limit=16, kind=CENSUS_DUMPS, max_states=1 << 16, max_depth=0, term_cap=None,
+               witnesses=False):
+    """dsm_reach_batch (the host reference; no GPU): pydsm.reach over every system of traces
+    [n, np, stride] u16, counts [n, np] -> a dict: info (REACH_INFO_DTYPE, one per system),
+    terminals (a list of REACH_TERMINAL_DTYPE arrays), can_deadlock and exhaustive (bool arrays),
+    and with witnesses the lists parents and masks."""
+    traces = np.ascontiguousarray(traces, dtype=np.uint16)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    assert traces.ndim == 3 and traces.shape[1] == np_ and counts.shape == traces.shape[:2]
+    n = traces.shape[0]
+    opts = ReachOpts(inbox_limit, CENSUS_KINDS.get(kind, kind), max_states, max_depth, 0)
+    ok = 0 < max_states <= REACH_BATCH_MAX_STATES
+    cap = max_states if ok else 1
+    term_cap = min(cap, 4096) if term_cap is None else term_cap
+    info = np.zeros(n, dtype=REACH_INFO_DTYPE)
+    terms = np.zeros(max(n * term_cap, 1), dtype=REACH_TERMINAL_DTYPE)
+    parents = np.zeros(max(n * cap, 1), np.uint32) if witnesses else None
+    masks = np.zeros(max(n * cap, 1), np.uint8) if witnesses else None
+    _check(lib().dsm_reach_batch(np_, _ptr(traces), _ptr(counts), traces.shape[2], n, ctypes.byref(opts), _ptr(info),
+                                 _ptr(terms), term_cap, _ptr(parents), _ptr(masks)), "dsm_reach_batch")
+    return _reach_many_result(info, terms[:n * term_cap], term_cap, parents, masks, cap)
 
 
 def reach_path(parents, masks, state):
@@ -1013,6 +1070,50 @@ class Engine:
         return _reach_result(info, d_par.cpu().numpy().view(np.uint32), d_msk.cpu().numpy(),
                              d_fps.cpu().numpy().view(np.uint64),
                              level_off, d_term.cpu().numpy().view(REACH_TERMINAL_DTYPE), kind)
+
+    def reach_batch_device(self, d_traces, d_counts, n_sys, opts, d_info, d_terminals, term_cap, d_parents, d_masks,
+                           scratch_bytes=0, stream=0):
+        """dsm_reach_batch_device: device pointers or tensors, each output may be None.
+        ASYNCHRONOUS on `stream`; returns the error code."""
+        return lib().dsm_reach_batch_device(self.ctx, _dptr(d_traces), _dptr(d_counts), n_sys, ctypes.byref(opts),
+                                            scratch_bytes, _dptr(d_info), _dptr(d_terminals), term_cap,
+                                            _dptr(d_parents), _dptr(d_masks), ctypes.c_void_p(stream))
+
+    def reach_batch_state(self):
+        """(systems the last reach_batch_device call kept in flight, bytes of the ctx's scratch)."""
+        w, b = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _check(lib().dsm_debug_reach_batch_state(self.ctx, ctypes.byref(w), ctypes.byref(b)), "dsm_debug_reach_batch_state")
+        return w.value, b.value
+
+    def reach_many(self, traces, counts, inbox_limit=16, kind=CENSUS_DUMPS, max_states=1 << 16, max_depth=0, chunk=0,
+                   term_cap=None, witnesses=False, scratch_bytes=0):
+        """Every state each of n systems (traces [n, np, max_instr] u16, counts [n, np]) can reach,
+        all searched by one asynchronous launch on the GPU -> the dict of pydsm.reach_many."""
+        import torch
+        tr, cn = np.ascontiguousarray(traces, dtype=np.uint16), np.ascontiguousarray(counts, dtype=np.uint32)
+        if tr.ndim != 3 or tr.shape[1:] != (self.np, self.max_instr) or cn.shape != tr.shape[:2]:
+            raise DsmError(E_INVAL, "reach_many: systems of the engine's np and max_instr")
+        n = tr.shape[0]
+        dev = torch.device("cuda", self.device)
+        d_tr = torch.from_numpy(tr.view(np.int16).reshape(-1)).to(dev)
+        d_cn = torch.from_numpy(cn.view(np.int32).reshape(-1)).to(dev)
+        ok = 0 < max_states <= REACH_BATCH_MAX_STATES
+        cap = max_states if ok else 1
+        term_cap = min(cap, 4096) if term_cap is None else term_cap
+        nw = len(REACH_INFO_FIELDS)
+        d_info = torch.zeros(max(n, 1) * nw, dtype=torch.int64, device=dev)
+        d_term = torch.zeros(5 * max(n * term_cap, 1), dtype=torch.int64, device=dev)
+        d_par = torch.zeros(max(n * cap, 1), dtype=torch.int32, device=dev) if witnesses else None
+        d_msk = torch.zeros(max(n * cap, 1), dtype=torch.uint8, device=dev) if witnesses else None
+        opts = ReachOpts(inbox_limit, CENSUS_KINDS.get(kind, kind), max_states, max_depth, chunk)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _check(self.reach_batch_device(d_tr, d_cn, n, opts, d_info, d_term, term_cap, d_par, d_msk, scratch_bytes, st),
+               "dsm_reach_batch_device")
+        info = d_info.cpu().numpy().view(REACH_INFO_DTYPE)[:n]          # .cpu() waits for the stream
+        terms = d_term.cpu().numpy().view(REACH_TERMINAL_DTYPE)[:n * term_cap]
+        return _reach_many_result(info, terms, term_cap,
+                                  d_par.cpu().numpy().view(np.uint32) if witnesses else None,
+                                  d_msk.cpu().numpy() if witnesses else None, cap)
 
     def reach_dist_device(self, d_trace, d_counts, opts, thresh, max_rounds, rinfo, dinfo, d_terminals, d_term_mass,
                           term_cap, round_mass, stream=0):

@@ -58,7 +58,9 @@ extern "C" {
                              5 (+dist): additive -- the outcome distribution (dsm_sched_prob,
                                 dsm_reach_dist*) likewise;
                              5 (+fate): additive -- the outcome fate (dsm_reach_fate*,
-                                dsm_fate_seal_point) likewise */
+                                dsm_fate_seal_point) likewise;
+                             5 (+reach batch): additive -- the search of a whole ensemble in one
+                                asynchronous launch (dsm_reach_batch*) likewise */
 
 #define DSM_MAX_NP 8             /* bitVector is one byte (README.md:51)                  */
 #define DSM_CACHE_SIZE 4         /* CACHE_SIZE      assignment.c:10                        */
@@ -715,6 +717,54 @@ int dsm_reach_device(dsm_ctx *ctx, const uint16_t *d_trace, const uint32_t *d_co
                      const dsm_reach_opts *opts, dsm_reach_info *info, uint32_t *d_parents,
                      uint8_t *d_masks, uint64_t *d_fps, uint64_t *level_off,
                      dsm_reach_terminal *d_terminals, uint64_t term_cap, void *stream);
+/* ---- reach batch: the search of a whole ensemble of small systems in one launch ------------- *
+ * dsm_reach_device waits on the host level by level; a system of a few thousand states is then
+ * all launches and waits.  The batch searches n_sys systems with ONE asynchronous launch: every
+ * system's whole search runs inside one workgroup, which then claims the next system.  Inputs are
+ * laid out as dsm_run_packed_device's: traces [n_sys][np][max_instr], counts [n_sys][np] (device
+ * traces are not validated, counts are clamped to the stride).  Outputs, each may be NULL:
+ *   info[s];
+ *   terminals[s * term_cap + i] for i < min(term_cap, info[s].terminals), ascending state id;
+ *   parents[s * max_states + id] and masks[s * max_states + id] for id < info[s].states.
+ * Entries of a system's own row at and after those bounds are unspecified; nothing outside the
+ * rows is written.  For every s, every written value equals what dsm_reach gives for that system
+ * alone under the same opts -- numbering, DSM_REACH_F_STATES (the level dropped whole),
+ * DSM_REACH_F_DEPTH, transitions, max_fill and by_status included -- but fp_collisions, which on
+ * the device counts the unequal fingerprint-equal pairs met among the candidates of one chunk, as
+ * dsm_reach_device does (a non-zero count still sets DSM_REACH_F_COLLISION).
+ * opts->max_states is per system, 1..DSM_REACH_BATCH_MAX_STATES; opts->chunk the candidates a
+ * workgroup takes per step, at most DSM_REACH_BATCH_MAX_CHUNK, 0 = a default (1024); every other
+ * option, and every error, as in dsm_reach.  Results never depend on chunk, on scratch_bytes or
+ * on how many systems are in flight. */
+#define DSM_REACH_BATCH_MAX_STATES (1u << 20)   /* per system */
+#define DSM_REACH_BATCH_MAX_CHUNK  (1u << 16)
+/* scratch_bytes 0: slabs for DSM_REACH_BATCH_DEFAULT_IN_FLIGHT systems, within 16 GiB (less where
+ * the device cannot give it).  Measured, 256 systems in flight give the time of 401 and 128 cost
+ * about 15 % ("Reach batch"); at max_states 2^16 a slab is 39 MiB (np 4) or 72 MiB
+ * (np 8), so the default holds 9.8 GiB (256 slabs) or 16 GiB (225). */
+#define DSM_REACH_BATCH_DEFAULT_IN_FLIGHT 256u
+#define DSM_REACH_BATCH_DEFAULT_SCRATCH (16ull << 30)
+/* host only: device scratch one system in flight needs under these options (0 for bad options) */
+uint64_t dsm_reach_batch_slab_bytes(int np, const dsm_reach_opts *opts);
+/* the host reference (no GPU): dsm_reach over systems 0 .. n_sys-1, a plain loop */
+int dsm_reach_batch(int np, const uint16_t *traces, const uint32_t *counts, uint32_t stride,
+                    uint64_t n_sys, const dsm_reach_opts *opts, dsm_reach_info *info,
+                    dsm_reach_terminal *terminals, uint64_t term_cap,
+                    uint32_t *parents, uint8_t *masks);
+/* The same on the GPU, ASYNCHRONOUS on `stream`: no host wait anywhere.  All pointers are device
+ * memory (d_info and d_terminals 8-byte aligned, d_parents 4-byte).  The scratch is the ctx's, like
+ * the event replay's: allocated or grown at the call (growing waits for the device; a call the
+ * scratch already holds waits for nothing), freed by dsm_close, and covered by the "one run at a
+ * time, one stream" convention.  The call keeps W = min(n_sys, resident workgroups,
+ * scratch_bytes / slab) systems in flight.  DSM_E_NOMEM, with nothing enqueued, when not one slab
+ * fits in scratch_bytes or the allocation fails; n_sys == 0 is a no-op; a bad argument (a
+ * misaligned output, max_states or chunk above the batch limits, NULL traces or counts with
+ * n_sys > 0) is DSM_E_INVAL with nothing written. */
+int dsm_reach_batch_device(dsm_ctx *ctx, const uint16_t *d_traces, const uint32_t *d_counts,
+                           uint64_t n_sys, const dsm_reach_opts *opts, uint64_t scratch_bytes,
+                           dsm_reach_info *d_info, dsm_reach_terminal *d_terminals,
+                           uint64_t term_cap, uint32_t *d_parents, uint8_t *d_masks, void *stream);
+
 /* The witness of state id (host only): the masks of the rounds from the root to it, root first.
  * *n = their number (the state's depth); DSM_E_INVAL when it exceeds cap (nothing written) or the
  * arrays are not a search's (a parent not below its child). */
