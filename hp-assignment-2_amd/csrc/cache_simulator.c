@@ -80,7 +80,7 @@
  *   --reach          exhaustive exploration instead of a sample: every state the system can reach
  *                    when, in each round, any non-empty subset of the nodes that have an action
  *                    takes it (dsm_reach_device) -- the closure of every --schedule.  Not valid
- *                    with --explore, --schedule, --events, --issue-order or --audit.  Prints
+ *                    with --explore, --schedule, --events or --issue-order.  Prints
  *                        reached S states, T transitions, K outcomes (exhaustive)
  *                    or, when a limit stopped the search,
  *                        reached S states, T transitions, K outcomes (truncated at N states / depth D: not exhaustive)
@@ -121,6 +121,20 @@
  *                        ROUND MASK STATE CLASS [LO per threshold]
  *                    (the root's mask is 00).  Without --fate, --reach prints what it printed
  *                    before.
+ *   --audit          with --reach: the coherence audit of EVERY reachable state
+ *                    (dsm_reach_audit_device, in place of the plain search; beside --fate, a call
+ *                    of its own).  Every `outcome k:` line is followed by
+ *                        outcome k audit: ...
+ *                    in --audit's format, the word of the outcome's first terminal state, and
+ *                    after --reach's other lines come, for the sets all, quiescent (nothing in
+ *                    flight), terminal and completed,
+ *                        reach audit <set>: V of N states
+ *                        reach audit <set> class <NAME>: C states, first F depth D
+ *                    the second per class that occurs in the set: F is the lowest state id with
+ *                    the class, so its witness is a shortest one.  With --explore-dir every class
+ *                    of the set `all` also gets D/audit_<NAME>/: the witness of state F as an
+ *                    outcome's is written (schedule.txt, core_<n>_output.txt for the nodes that
+ *                    have dumped by then) and audit.txt, the state's audit line.
  *   --reach-batch    a screen of many tests: every positional argument is a test directory (one
  *                    or more), all read with one dsm_parse_traces call and all searched with one
  *                    dsm_reach_batch_device call.  Takes --reach-states (default 65536, at most
@@ -147,7 +161,7 @@ static void usage(const char *argv0) {
                     "          [--schedule SEED:THRESH] [--explore N [--explore-dir DIR]\n"
                     "          [--explore-kind dumps|final|full] [--check DIR]] [--audit]\n"
                     "          [--events FILE [--events-kind instr|msg|all]]\n"
-                    "          [--reach [--reach-states N] [--reach-depth D] [--reach-inbox L] [--reach-prob T[,T...]]\n"
+                    "          [--reach [--audit] [--reach-states N] [--reach-depth D] [--reach-inbox L] [--reach-prob T[,T...]]\n"
                     "          [--fate completed|deadlocked|ring_overflow|assert_failed|round_limit|0xKEY]\n"
                     "          [--explore-dir DIR]\n"
                     "          [--explore-kind dumps|final] [--check DIR]] <test_directory>\n"
@@ -160,15 +174,18 @@ static const char *const status_names[5] = {"COMPLETED", "DEADLOCKED", "RING_OVE
                                             "ROUND_LIMIT"};
 static const char *const fate_targets[5] = {"completed", "deadlocked", "ring_overflow", "assert_failed", "round_limit"};
 static const char *const fate_classes[4] = {"NONE", "DOOMED", "SAFE", "OPEN"};
+static const char *const raudit_sets[DSM_RAUDIT_NSETS] = {"all", "quiescent", "terminal", "completed"};
 
 /* "coherent", or "0x0c DIR_EM,DIR_S lines 3 first 0x15 bad 0" */
-static void print_audit_word(const char *prefix, uint32_t w) {
-    if (w == DSM_AUDIT_COHERENT) { printf("%s: coherent\n", prefix); return; }
-    printf("%s: 0x%02x ", prefix, w & 0xFFu);
+static void fprint_audit_word(FILE *f, const char *prefix, uint32_t w) {
+    if (w == DSM_AUDIT_COHERENT) { fprintf(f, "%s: coherent\n", prefix); return; }
+    fprintf(f, "%s: 0x%02x ", prefix, w & 0xFFu);
     for (int b = 0, k = 0; b < DSM_AUDIT_NCLASS; ++b)
-        if ((w >> b) & 1u) printf("%s%s", k++ ? "," : "", dsm_audit_class_name(b));
-    printf(" lines %u first 0x%02x bad %u\n", (w >> 8) & 0xFFu, (w >> 16) & 0xFFu, w >> 24);
+        if ((w >> b) & 1u) fprintf(f, "%s%s", k++ ? "," : "", dsm_audit_class_name(b));
+    fprintf(f, " lines %u first 0x%02x bad %u\n", (w >> 8) & 0xFFu, (w >> 16) & 0xFFu, w >> 24);
 }
+
+static void print_audit_word(const char *prefix, uint32_t w) { fprint_audit_word(stdout, prefix, w); }
 
 /* --events: systems ids[0 .. k) of the device ensemble replayed with a log under the ctx's
  * schedule; the text of system j goes to file (k == 1, dir NULL) or to dir/outcome_<j>/file.  A
@@ -440,7 +457,7 @@ static void print_mass(uint64_t mass) {
 static int reach(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces, const uint32_t *counts,
                  unsigned long long max_states, uint32_t max_depth, uint32_t inbox, int kind, const char *out_dir,
                  const char *check_dir, const uint32_t *prob_t, uint32_t n_prob, const dsm_fate_opts *fate,
-                 const char *fate_name) {
+                 const char *fate_name, int audit) {
     const size_t tr_bytes = (size_t)np * stride * sizeof(uint16_t);
     uint64_t *d_tmass = NULL, *tmass = NULL, *omass = NULL;
     dsm_dist_info dinfo[DSM_DIST_MAX_THRESH];
@@ -456,6 +473,8 @@ static int reach(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces, 
     uint64_t *d_lo = NULL, *lo = NULL, *loff = NULL;
     dsm_fate_info finfo;
     dsm_fate_value fval[DSM_DIST_MAX_THRESH];
+    uint32_t *d_words = NULL, *d_tw = NULL, *tw = NULL;
+    dsm_reach_audit_info ainfo;
     dsm_reach_info info;
     dsm_reach_opts opts;
     int rc = DSM_OK, code = EXIT_FAILURE;
@@ -492,9 +511,21 @@ static int reach(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces, 
         if ((rc = dsm_reach_fate_device(ctx, d_tr, d_cn, &opts, fate, prob_t, n_prob, &info, &finfo, fval, d_par, d_msk, loff,
                                         d_term, term_cap, d_cls, d_lo, NULL, NULL)))
             goto fail;
-    } else {
+    } else if (!audit) {
         what = "dsm_reach_device";
         if ((rc = dsm_reach_device(ctx, d_tr, d_cn, &opts, &info, d_par, d_msk, NULL, NULL, d_term, term_cap, NULL))) goto fail;
+    }
+    if (audit) {                                        /* the search and its audit in one call; beside --fate, again */
+        dsm_reach_info again;
+        what = "device memory";
+        if (hipMalloc((void **)&d_words, (size_t)max_states * sizeof(uint32_t)) != hipSuccess ||
+            hipMalloc((void **)&d_tw, (size_t)term_cap * sizeof(uint32_t)) != hipSuccess)
+            goto fail;
+        what = "dsm_reach_audit_device";
+        if ((rc = dsm_reach_audit_device(ctx, d_tr, d_cn, &opts, fate ? &again : &info, &ainfo, fate ? NULL : d_par,
+                                         fate ? NULL : d_msk, NULL, d_term, term_cap, d_words, NULL, d_tw, NULL)))
+            goto fail;
+        if (fate && (again.states != info.states || again.terminals != info.terminals)) { rc = DSM_E_STATE; goto fail; }
     }
     if (info.terminals > term_cap) { what = "too many terminal states for one census"; goto fail; }
     if (n_prob) {                                       /* the same search again, then the rounds */
@@ -527,6 +558,13 @@ static int reach(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces, 
             if (hipMemcpy(lo + (size_t)j * info.states, d_lo + (size_t)j * max_states, (size_t)info.states * sizeof(uint64_t),
                           hipMemcpyDeviceToHost) != hipSuccess)
                 goto fail;
+        what = "out of memory";
+    }
+    if (audit) {
+        tw = (uint32_t *)malloc((size_t)(info.terminals ? info.terminals : 1) * sizeof(uint32_t));
+        if (!tw) goto fail;
+        what = "read-back";
+        if (hipMemcpy(tw, d_tw, (size_t)info.terminals * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) goto fail;
         what = "out of memory";
     }
     if (n_prob) {
@@ -586,6 +624,11 @@ static int reach(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces, 
             print_mass(omass[o * n_prob + j]);
         }
         printf("\n");
+        if (audit) {
+            char prefix[64];
+            snprintf(prefix, sizeof prefix, "outcome %llu audit", (unsigned long long)o);
+            print_audit_word(prefix, tw[t - term]);
+        }
         if (out_dir) {                                  /* the witness, replayed on the host */
             char dir[512], file[600];
             dsm_node_state dump[DSM_MAX_NP];
@@ -661,6 +704,49 @@ static int reach(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces, 
             printf("\n");
         }
     }
+    if (audit) {
+        for (int k = 0; k < DSM_RAUDIT_NSETS; ++k) {
+            const dsm_audit *a = &ainfo.set[k];
+            printf("reach audit %s: %llu of %llu states\n", raudit_sets[k], (unsigned long long)a->violating,
+                   (unsigned long long)a->systems);
+            for (int b = 0; b < DSM_AUDIT_NCLASS; ++b)
+                if (a->by_class[b])
+                    printf("reach audit %s class %s: %llu states, first %llu depth %llu\n", raudit_sets[k],
+                           dsm_audit_class_name(b), (unsigned long long)a->by_class[b], (unsigned long long)~a->inv_first[b],
+                           (unsigned long long)ainfo.first_depth[k][b]);
+        }
+        for (int b = 0; out_dir && b < DSM_AUDIT_NCLASS; ++b) {     /* the shortest witness of every class */
+            const dsm_audit *a = &ainfo.set[DSM_RAUDIT_ALL];
+            char dir[512], file[600];
+            dsm_node_state dump[DSM_MAX_NP];
+            dsm_sys_result res;
+            uint64_t n = 0;
+            uint32_t w = 0;
+            if (!a->by_class[b]) continue;
+            const uint64_t id = ~a->inv_first[b];
+            what = "audit witness";
+            if ((rc = dsm_reach_path(par, msk, id, path, DSM_REACH_MAX_LEVELS, &n))) goto fail;
+            if ((rc = dsm_reach_replay(np, traces, counts, stride, inbox, path, n, dump, NULL, &res))) goto fail;
+            rc = DSM_E_IO;
+            if (hipMemcpy(&w, d_words + id, sizeof w, hipMemcpyDeviceToHost) != hipSuccess) goto fail;
+            if (snprintf(dir, sizeof dir, "%s/audit_%s", out_dir, dsm_audit_class_name(b)) >= (int)sizeof dir ||
+                (mkdir(dir, 0777) != 0 && errno != EEXIST)) goto fail;
+            for (int c = 0; c < np; ++c)
+                if (((res.status >> (8 + c)) & 1u) && (rc = dsm_write_dump(c, &dump[c], dir))) goto fail;
+            rc = DSM_E_IO;
+            snprintf(file, sizeof file, "%s/schedule.txt", dir);
+            FILE *f = fopen(file, "w");
+            if (!f) goto fail;
+            for (uint64_t r = 0; r < n; ++r) fprintf(f, "%02x\n", path[r]);
+            if (fclose(f) != 0) goto fail;
+            snprintf(file, sizeof file, "%s/audit.txt", dir);
+            if (!(f = fopen(file, "w"))) goto fail;
+            snprintf(dir, sizeof dir, "state %llu audit", (unsigned long long)id);
+            fprint_audit_word(f, dir, w);
+            if (fclose(f) != 0) goto fail;
+            rc = DSM_OK;
+        }
+    }
     code = 0;
     if (check_dir) {
         /* the DUMPS key of DIR's files: the dumped mask and the sum of the node hashes are known,
@@ -698,7 +784,9 @@ fail:
     if (d_tmass) (void)hipFree(d_tmass);
     if (d_cls) (void)hipFree(d_cls);
     if (d_lo) (void)hipFree(d_lo);
-    free(cls); free(lo); free(loff);
+    if (d_words) (void)hipFree(d_words);
+    if (d_tw) (void)hipFree(d_tw);
+    free(cls); free(lo); free(loff); free(tw);
     free(tmass); free(omass);
     free(par); free(msk); free(path); free(term); free(cen); free(outc);
     return code;
@@ -938,7 +1026,7 @@ int main(int argc, char **argv) {
     }
     if ((explore_n && issue_file) || (!explore_n && !do_reach && explore_opts)) { usage(argv[0]); return EXIT_FAILURE; }
     if ((reach_opts && !do_reach) ||
-        (do_reach && (explore_n || have_sched || events_file || issue_file || audit || explore_kind == DSM_CENSUS_FULL ||
+        (do_reach && (explore_n || have_sched || events_file || issue_file || explore_kind == DSM_CENSUS_FULL ||
                       (check_dir && explore_kind != DSM_CENSUS_DUMPS) || reach_states < 1 ||
                       reach_states > (long long)DSM_REACH_MAX_STATES || reach_depth < 0 ||
                       reach_depth >= (long long)DSM_REACH_MAX_LEVELS || reach_inbox < 1 || reach_inbox > 16))) {
@@ -993,7 +1081,7 @@ int main(int argc, char **argv) {
     if (do_reach) {
         const int code = reach(ctx, np, stride, traces, counts, (unsigned long long)reach_states, (uint32_t)reach_depth,
                                (uint32_t)reach_inbox, explore_kind, explore_dir, check_dir, prob_t, n_prob,
-                               fate_name ? &fate_opts : NULL, fate_name);
+                               fate_name ? &fate_opts : NULL, fate_name, audit);
         dsm_close(ctx);
         free(traces);
         return code;

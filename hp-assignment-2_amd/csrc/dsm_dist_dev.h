@@ -19,8 +19,10 @@
  *                             the table look-up; src, dst and the probability index are stored
  *
  * The edges are in source order, a source's in ascending order of the mask: state id's are
- * [offs[id], offs[id + 1]), edge offs[id] + j - 1 the one of rank j.  Internal to those two units;
- * everything is in an unnamed namespace, so each unit holds its own instantiations.
+ * [offs[id], offs[id + 1]), edge offs[id] + j - 1 the one of rank j.  The build is two functions,
+ * dist_graph_states (search, store, classes) and dist_graph_edges (table, edges): the reach audit
+ * (dsm_raudit.hip) needs the states alone.  Internal to those three units; everything is in an
+ * unnamed namespace, so each unit holds its own instantiations.
  */
 #ifndef DSM_DIST_DEV_H
 #define DSM_DIST_DEV_H
@@ -198,26 +200,29 @@ struct DistGraph {
     u64 n = 0, n_exp = 0, n_edges = 0, missing = 0;
 };
 
-/* search, rebuild (with the class kernel and the scan), table, edges: tm gets a mark before each
- * and one after the last */
+/* Phases 1 and 2 alone: the search, then the state store and the class bytes; g keeps the search's
+ * parents and masks, the store and cls.  With for_edges also the fingerprints, the enabled sets and
+ * the edge offsets (the scan) that dist_graph_edges goes on from, tm getting a mark before the
+ * search, after it and after phase 2; without, neither the fingerprints nor the scan, and tm gets one
+ * more mark between the rebuild and the class kernel. */
 template <int NP>
-int dist_graph_build(dsm_ctx *c, const uint16_t *d_trace, const uint32_t *d_counts, const dsm_reach_opts *o, uint32_t L,
-                     dsm_reach_terminal *d_terminals, u64 term_cap, bool own_term, bool keep, PhaseTimer &tm,
-                     hipStream_t st, DistGraph &g) {
+int dist_graph_states(dsm_ctx *c, const uint16_t *d_trace, const uint32_t *d_counts, const dsm_reach_opts *o, uint32_t L,
+                      dsm_reach_terminal *d_terminals, u64 term_cap, bool own_term, bool for_edges, PhaseTimer &tm,
+                      hipStream_t st, DistGraph &g) {
     const u64 cap = o->max_states;
-    const u64 chunk = o->chunk ? o->chunk : DEFAULT_CHUNK;
     const uint32_t stride = c->cfg.max_instr;
     const StepArgs step = {d_trace, d_counts, reinterpret_cast<const uint32_t *>(c->d_table), stride, L};
     int rc;
 
     /* 1. the search */
-    if ((rc = g.par.alloc(cap * 4)) || (rc = g.msk.alloc(cap)) || (rc = g.fps.alloc(cap * 8))) return rc;
+    if ((rc = g.par.alloc(cap * 4)) || (rc = g.msk.alloc(cap)) || (for_edges && (rc = g.fps.alloc(cap * 8)))) return rc;
     if (own_term && (rc = g.term.alloc(term_cap * sizeof(dsm_reach_terminal)))) return rc;
     g.terms = own_term ? g.term.as<u64>() : reinterpret_cast<const u64 *>(d_terminals);
     g.loff.assign(DSM_REACH_MAX_LEVELS + 1, 0);
     tm.mark();
-    if ((rc = dsm_reach_device(c, d_trace, d_counts, o, &g.ri, g.par.as<uint32_t>(), g.msk.as<uint8_t>(), g.fps.as<uint64_t>(),
-                               g.loff.data(), own_term ? g.term.as<dsm_reach_terminal>() : d_terminals, term_cap, st)))
+    if ((rc = dsm_reach_device(c, d_trace, d_counts, o, &g.ri, g.par.as<uint32_t>(), g.msk.as<uint8_t>(),
+                               for_edges ? g.fps.as<uint64_t>() : nullptr, g.loff.data(),
+                               own_term ? g.term.as<dsm_reach_terminal>() : d_terminals, term_cap, st)))
         return rc;
     const dsm_reach_info &ri = g.ri;
     const u64 n = g.n = ri.states;
@@ -225,13 +230,11 @@ int dist_graph_build(dsm_ctx *c, const uint16_t *d_trace, const uint32_t *d_coun
     tm.mark();
 
     /* 2. the state store, the classes, the edge offsets */
-    DevBuf b_cnt, b_bsum, b_ctr;
+    DevBuf b_cnt, b_bsum;
     const u64 nb = (n + DSM_EXSCAN_TILE - 1) / DSM_EXSCAN_TILE;
     if ((rc = g.store.alloc((size_t)RS_WORK(NP) * n * 4)) || (rc = g.cls.alloc(n)) || (rc = g.A.alloc(n)) ||
-        (rc = b_cnt.alloc(n * 4)) || (rc = g.offs.alloc((n + 1) * 8)) || (rc = b_bsum.alloc(nb * 8)) ||
-        (rc = b_ctr.alloc(sizeof(DistCtr))))
+        (rc = b_cnt.alloc(n * 4)) || (for_edges && ((rc = g.offs.alloc((n + 1) * 8)) || (rc = b_bsum.alloc(nb * 8)))))
         return rc;
-    HIPCK(hipMemsetAsync(b_ctr.p, 0, sizeof(DistCtr), st));
     hipLaunchKernelGGL(dist_root_kernel<NP>, dim3(1), dim3(64), 0, st, g.store.as<uint32_t>(), n);
     for (u64 d = 1; d < ri.levels; ++d) {
         RebuildArgs ra;
@@ -239,16 +242,32 @@ int dist_graph_build(dsm_ctx *c, const uint16_t *d_trace, const uint32_t *d_coun
         ra.parents = g.par.as<uint32_t>(); ra.masks = g.msk.as<uint8_t>(); ra.step = step;
         hipLaunchKernelGGL(dist_rebuild_kernel<NP>, dim3(grid_cap(ra.cnt)), dim3(RT), 0, st, ra);
     }
+    if (!for_edges) tm.mark();
     hipLaunchKernelGGL(dist_class_kernel<NP>, dim3(grid_cap(n)), dim3(RT), 0, st, g.store.as<uint32_t>(), n, n_exp, d_counts,
                        stride, g.cls.as<uint8_t>(), g.A.as<uint8_t>(), b_cnt.as<uint32_t>());
-    dsm_exscan_launch(b_cnt.as<uint32_t>(), n, b_bsum.as<u64>(), g.offs.as<u64>(), st);
     u64 n_edges = 0;
-    HIPCK(hipMemcpyAsync(&n_edges, g.offs.as<u64>() + n, 8, hipMemcpyDeviceToHost, st));
+    if (for_edges) {
+        dsm_exscan_launch(b_cnt.as<uint32_t>(), n, b_bsum.as<u64>(), g.offs.as<u64>(), st);
+        HIPCK(hipMemcpyAsync(&n_edges, g.offs.as<u64>() + n, 8, hipMemcpyDeviceToHost, st));
+    }
     HIPCK(hipStreamSynchronize(st));
     g.n_edges = n_edges;
-    if (!keep) { g.par.release(); g.msk.release(); }
-    b_cnt.release(); b_bsum.release();
     tm.mark();
+    return DSM_OK;
+}
+
+/* Phases 3 and 4 over what dist_graph_states left: the fingerprint table and the edges, a mark after
+ * each.  Without keep the state store, the offsets and the enabled sets are released. */
+template <int NP>
+int dist_graph_edges(dsm_ctx *c, const uint16_t *d_trace, const uint32_t *d_counts, const dsm_reach_opts *o, uint32_t L,
+                     bool keep, PhaseTimer &tm, hipStream_t st, DistGraph &g) {
+    const u64 chunk = o->chunk ? o->chunk : DEFAULT_CHUNK;
+    const StepArgs step = {d_trace, d_counts, reinterpret_cast<const uint32_t *>(c->d_table), c->cfg.max_instr, L};
+    const u64 n = g.n, n_edges = g.n_edges;
+    int rc;
+    DevBuf b_ctr;
+    if ((rc = b_ctr.alloc(sizeof(DistCtr)))) return rc;
+    HIPCK(hipMemsetAsync(b_ctr.p, 0, sizeof(DistCtr), st));
 
     /* 3. fingerprint -> id */
     u64 slots = 64;
@@ -288,6 +307,17 @@ int dist_graph_build(dsm_ctx *c, const uint16_t *d_trace, const uint32_t *d_coun
     return DSM_OK;
 }
 
+/* search, rebuild (with the class kernel and the scan), table, edges: tm gets a mark before each
+ * and one after the last */
+template <int NP>
+int dist_graph_build(dsm_ctx *c, const uint16_t *d_trace, const uint32_t *d_counts, const dsm_reach_opts *o, uint32_t L,
+                     dsm_reach_terminal *d_terminals, u64 term_cap, bool own_term, bool keep, PhaseTimer &tm,
+                     hipStream_t st, DistGraph &g) {
+    if (int rc = dist_graph_states<NP>(c, d_trace, d_counts, o, L, d_terminals, term_cap, own_term, true, tm, st, g)) return rc;
+    if (!keep) { g.par.release(); g.msk.release(); }
+    return dist_graph_edges<NP>(c, d_trace, d_counts, o, L, keep, tm, st, g);
+}
+
 /* ---- the same graph on the host -------------------------------------------------------------- */
 /* host memory freed when the call returns; malloc, so nothing of it is touched before its use */
 template <typename T>
@@ -311,22 +341,24 @@ struct HostGraph {
     u64 n = 0, n_exp = 0, missing = 0;
 };
 
-/* dsm_reach, the states again from the round that first made each, then classes and edges in one
- * pass of the shared round step; may throw std::bad_alloc */
+/* Phases 1 and 2 alone on the host: dsm_reach, then the states again from the round that first made
+ * each (g.S).  with_fps: keep the fingerprints for dist_host_graph's look-ups.  May throw
+ * std::bad_alloc. */
 template <int NP>
-int dist_host_graph(const uint16_t *trace, const uint32_t *counts, uint32_t stride, const dsm_reach_opts *o, uint32_t L,
-                    dsm_reach_terminal *terminals, uint64_t term_cap, HostGraph &g) {
+int dist_host_states(const uint16_t *trace, const uint32_t *counts, uint32_t stride, const dsm_reach_opts *o, uint32_t L,
+                     dsm_reach_terminal *terminals, uint64_t term_cap, bool with_fps, HostGraph &g) {
     constexpr uint32_t W = RS_WORDS(NP);
     const u64 cap = o->max_states;
     uint32_t tab[DT_TABLE_WORDS];
     if (dt_build(tab) > DT_ENTRIES) return DSM_E_INVAL;
     int rc;
-    if ((rc = g.parents.alloc(cap)) || (rc = g.masks.alloc(cap)) || (rc = g.fps.alloc(cap))) return rc;
+    if ((rc = g.parents.alloc(cap)) || (rc = g.masks.alloc(cap)) || (with_fps && (rc = g.fps.alloc(cap)))) return rc;
     g.loff.assign(DSM_REACH_MAX_LEVELS + 1, 0);
     if ((rc = dsm_reach(NP, trace, counts, stride, o, &g.ri, g.parents.p, g.masks.p, g.fps.p, g.loff.data(), terminals,
                         term_cap)))
         return rc;
-    const u64 n = g.n = g.ri.states, n_exp = g.n_exp = expanded_states(g.ri, g.loff.data());
+    const u64 n = g.n = g.ri.states;
+    g.n_exp = expanded_states(g.ri, g.loff.data());
 
     std::vector<uint32_t> &S = g.S;
     S.resize((size_t)n * W);
@@ -342,6 +374,21 @@ int dist_host_graph(const uint16_t *trace, const uint32_t *counts, uint32_t stri
         (void)rs_round<NP>(m, tab, trace, counts, stride, g.masks.p[id], L, nullptr);
         memcpy(&S[(size_t)id * W], tmp, W * 4);
     }
+    return DSM_OK;
+}
+
+/* dsm_reach and the states (dist_host_states), then classes and edges in one pass of the shared
+ * round step; may throw std::bad_alloc */
+template <int NP>
+int dist_host_graph(const uint16_t *trace, const uint32_t *counts, uint32_t stride, const dsm_reach_opts *o, uint32_t L,
+                    dsm_reach_terminal *terminals, uint64_t term_cap, HostGraph &g) {
+    constexpr uint32_t W = RS_WORDS(NP);
+    uint32_t tab[DT_TABLE_WORDS];
+    if (dt_build(tab) > DT_ENTRIES) return DSM_E_INVAL;
+    if (int rc = dist_host_states<NP>(trace, counts, stride, o, L, terminals, term_cap, true, g)) return rc;
+    const u64 n = g.n, n_exp = g.n_exp;
+    std::vector<uint32_t> &S = g.S;
+    uint32_t tmp[RS_WORK(NP)];
     std::unordered_map<uint64_t, uint32_t> by_fp;
     by_fp.reserve((size_t)n);
     for (u64 id = 0; id < n; ++id) by_fp.emplace(g.fps.p[id], (uint32_t)id);   /* the lower id stays */

@@ -15,10 +15,14 @@
  *   dsm_fate.hip     outcome fate: the class and value sweeps over the edge list, the host reference
  *   dsm_reach_batch.hip  reach batch: the search of many small systems, one workgroup each, in
  *                    one asynchronous launch; its host loop
+ *   dsm_raudit.hip   reach audit: the coherence audit word of every state of the reach graph, one
+ *                    lane per state over the rebuilt store; its host reference
  * The last four replay ONE system a round at a time: the round is dsm_step.h's st_round, once,
  * under dsm_events.h's and dsm_reach.h's inbox and log policies, the hashes are dsm_hash.h's,
  * dsm_reach_dev.h holds the device plumbing dsm_reach.hip, dsm_dist.hip and dsm_fate.hip share, and
- * dsm_dist_dev.h the edge list (its kernels and its host twin) of the last two.
+ * dsm_dist_dev.h the edge list (its kernels and its host twin) of the last two; dsm_raudit.hip uses
+ * the first half of that build (search, state store, classes) and dsm_audit_fn.h, the audit's
+ * arithmetic, with dsm_audit.hip.
  * Each kernel is launched from the unit that defines or instantiates it.  Not part of the ABI.
  */
 #ifndef DSM_INTERNAL_H
@@ -155,6 +159,15 @@ extern "C" int dsm_debug_dist_times(double *ms);
  * sweeps, value sweeps, the rest -- and, in sweeps[2] (may be NULL), the class sweeps and the most
  * value sweeps any threshold took. */
 extern "C" int dsm_debug_fate_times(double *ms, uint64_t *sweeps);
+
+/* The same of the last dsm_reach_audit_device call that ran with DSM_RAUDIT_TIMING=1 in the
+ * environment (tools/reach_audit_time.py): four phases -- search, rebuild, class, audit -- and, in
+ * *bytes (may be NULL), the bytes the audit kernel of the last call read and wrote, timed or not. */
+extern "C" int dsm_debug_raudit_times(double *ms, uint64_t *bytes);
+/* Test-only (not part of the ABI): reach_audit_kernel's lane body run on the host over ONE state --
+ * state[DSM_REACH_WORDS(np)] in that order, cls its class byte (dsm_dist.h: 0 running, 1 escaped,
+ * 2 + status terminal) -> the audit word and the set byte.  The body is one function for both. */
+extern "C" int dsm_debug_raudit_lane(int np, const uint32_t *state, uint32_t cls, uint32_t *word, uint32_t *set);
 
 /* Measurement-only view of the last dsm_reach_batch_device call (not part of the ABI;
  * tools/reach_batch_time.py): the systems it kept in flight and the bytes of the ctx's scratch. */

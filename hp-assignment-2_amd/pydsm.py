@@ -203,7 +203,14 @@ def lib():
             "dsm_reach_fate_device": (i32, [vp, vp, vp, ctypes.POINTER(ReachOpts), ctypes.POINTER(FateOpts), vp, u32,
                                             vp, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, vp]),
             "dsm_fate_seal_point": (i32, [vp, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+            # ABI 5 (+reach audit): the coherence of every reachable state
+            "dsm_reach_audit": (i32, [i32, vp, vp, u32, ctypes.POINTER(ReachOpts), vp, vp, vp, vp, vp, vp, u64, vp, vp,
+                                      vp]),
+            "dsm_reach_audit_device": (i32, [vp, vp, vp, ctypes.POINTER(ReachOpts), vp, vp, vp, vp, vp, vp, u64, vp, vp,
+                                             vp, vp]),
             # test-only (csrc/dsm_internal.h, not in include/dsm.h)
+            "dsm_debug_raudit_times": (i32, [vp, ctypes.POINTER(u64)]),
+            "dsm_debug_raudit_lane": (i32, [i32, vp, u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]),
             "dsm_debug_fate_times": (i32, [vp, vp]),
             "dsm_debug_dist_edges": (i32, [i32, vp, vp, u32, ctypes.POINTER(ReachOpts), vp, vp, vp, u64,
                                            ctypes.POINTER(u64)]),
@@ -804,6 +811,54 @@ def fate_seal_point(parents, cls, state):
     return (None if s.value == FATE_NO_EDGE else s.value), d.value
 
 
+# -- reach audit (ABI 5 +reach audit) ---------------------------------------------------------
+RAUDIT_ALL, RAUDIT_QUIESCENT, RAUDIT_TERMINAL, RAUDIT_COMPLETED = range(4)
+RAUDIT_NSETS = 4
+RAUDIT_SET_NAMES = ["all", "quiescent", "terminal", "completed"]
+RAUDIT_F_TRUNCATED, RAUDIT_F_INEXACT = 1, 2
+RAUDIT_NONE = (1 << 64) - 1                  # first_depth of a class that does not occur
+RAUDIT_INFO_DTYPE = np.dtype([("set", AUDIT_DTYPE, (RAUDIT_NSETS,)), ("first_depth", "<u8", (RAUDIT_NSETS, 8)),
+                              ("flags", "<u8"), ("reserved", "<u8", (3,))])
+assert RAUDIT_INFO_DTYPE.itemsize == RAUDIT_NSETS * NAUDIT * 8 + RAUDIT_NSETS * 64 + 32
+
+
+def _raudit_result(info, ainfo, parents, masks, level_off, terms, words, sets, term_words, term_cap):
+    d = reach_info_to_dict(info)
+    n, nt = d["states"], min(d["terminals"], term_cap)
+    a = ainfo[0]
+    return {"info": d, "parents": parents[:n], "masks": masks[:n], "level_off": level_off[:d["levels"] + 1],
+            "terminals": terms[:nt], "words": words[:n], "sets": sets[:n], "term_words": term_words[:nt],
+            "audit": a["set"].copy(), "flags": int(a["flags"]), "reserved": [int(x) for x in a["reserved"]],
+            "first_depth": a["first_depth"].copy(),
+            **{name: audit_to_dict(a["set"][k]) for k, name in enumerate(RAUDIT_SET_NAMES)}}
+
+
+def reach_audit(np_, traces, counts, inbox_limit=16, kind=CENSUS_DUMPS, max_states=1 << 22, max_depth=0, term_cap=None):
+    """dsm_reach_audit (the host reference; no GPU) of ONE system -> a dict: info (the search's),
+    parents, masks, level_off, terminals, words (the audit word of every state), sets (its set
+    byte), term_words (the words of the terminals), the four summaries as audit_to_dict gives them
+    ("all", "quiescent", "terminal", "completed"; ids are state ids) and raw ("audit": AUDIT_DTYPE
+    [4]), first_depth (uint64 [4, 8]; RAUDIT_NONE where the class does not occur) and flags."""
+    traces = np.ascontiguousarray(traces, dtype=np.uint16)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+    assert traces.ndim == 2 and traces.shape[0] == np_ and counts.shape == (np_,)
+    kind = CENSUS_KINDS.get(kind, kind)
+    opts = ReachOpts(inbox_limit, kind, max_states, max_depth, 0)
+    n = max_states if 0 < max_states <= 1 << 31 else 1
+    term_cap = min(n, 1 << 20) if term_cap is None else term_cap
+    info = np.zeros(len(REACH_INFO_FIELDS), dtype=np.uint64)
+    ainfo = np.zeros(1, dtype=RAUDIT_INFO_DTYPE)
+    parents, masks = np.zeros(n, np.uint32), np.zeros(n, np.uint8)
+    words, sets = np.zeros(n, np.uint32), np.zeros(n, np.uint8)
+    level_off = np.zeros(REACH_MAX_LEVELS + 1, dtype=np.uint64)
+    terms = np.zeros(max(term_cap, 1), dtype=REACH_TERMINAL_DTYPE)
+    term_words = np.zeros(max(term_cap, 1), np.uint32)
+    _check(lib().dsm_reach_audit(np_, _ptr(traces), _ptr(counts), traces.shape[1], ctypes.byref(opts), _ptr(info),
+                                 _ptr(ainfo), _ptr(parents), _ptr(masks), _ptr(level_off), _ptr(terms), term_cap,
+                                 _ptr(words), _ptr(sets), _ptr(term_words)), "dsm_reach_audit")
+    return _raudit_result(info, ainfo, parents, masks, level_off, terms, words, sets, term_words, term_cap)
+
+
 def _reach_terminals_result(info, terms, kind):
     d = reach_info_to_dict(info)
     nt = min(d["terminals"], len(terms))
@@ -1204,6 +1259,48 @@ class Engine:
                             d_term.cpu().numpy().view(REACH_TERMINAL_DTYPE), kind, d_cls.cpu().numpy(),
                             d_lo.cpu().numpy().view(np.uint64).reshape(max(nth, 1), n),
                             d_hi.cpu().numpy().view(np.uint64).reshape(max(nth, 1), n), nth)
+
+    def reach_audit_device(self, d_trace, d_counts, opts, rinfo, ainfo, d_parents, d_masks, level_off, d_terminals,
+                           term_cap, d_words, d_sets, d_term_words, stream=0):
+        """dsm_reach_audit_device: device pointers or tensors for the trace, counts, parents, masks,
+        terminals, words, sets and term_words; rinfo, ainfo (RAUDIT_INFO_DTYPE) and level_off numpy
+        arrays (host); each output may be None.  Synchronous; returns the error code."""
+        return lib().dsm_reach_audit_device(self.ctx, _dptr(d_trace), _dptr(d_counts),
+                                            None if opts is None else ctypes.byref(opts), _ptr(rinfo), _ptr(ainfo),
+                                            _dptr(d_parents), _dptr(d_masks), _ptr(level_off), _dptr(d_terminals),
+                                            term_cap, _dptr(d_words), _dptr(d_sets), _dptr(d_term_words),
+                                            ctypes.c_void_p(stream))
+
+    def reach_audit(self, traces, counts, inbox_limit=16, kind=CENSUS_DUMPS, max_states=1 << 22, max_depth=0, chunk=0,
+                    term_cap=None):
+        """The coherence audit of every state ONE system can reach, on the GPU -> the dict of
+        pydsm.reach_audit."""
+        import torch
+        tr, cn = np.array(traces, dtype=np.uint16), np.array(counts, dtype=np.uint32)
+        if tr.shape != (self.np, self.max_instr) or cn.shape != (self.np,):
+            raise DsmError(E_INVAL, "reach_audit: one system of the engine's np and max_instr")
+        kind = CENSUS_KINDS.get(kind, kind)
+        dev = torch.device("cuda", self.device)
+        d_tr = torch.from_numpy(tr.view(np.int16).reshape(-1)).to(dev)
+        d_cn = torch.from_numpy(cn.view(np.int32)).to(dev)
+        n = max_states if 0 < max_states <= 1 << 31 else 1
+        term_cap = min(n, 1 << 20) if term_cap is None else term_cap
+        d_par = torch.zeros(n, dtype=torch.int32, device=dev)
+        d_msk = torch.zeros(n, dtype=torch.uint8, device=dev)
+        d_words = torch.zeros(n, dtype=torch.int32, device=dev)
+        d_sets = torch.zeros(n, dtype=torch.uint8, device=dev)
+        d_term = torch.zeros(5 * max(term_cap, 1), dtype=torch.int64, device=dev)
+        d_tw = torch.zeros(max(term_cap, 1), dtype=torch.int32, device=dev)
+        info = np.zeros(len(REACH_INFO_FIELDS), dtype=np.uint64)
+        ainfo = np.zeros(1, dtype=RAUDIT_INFO_DTYPE)
+        level_off = np.zeros(REACH_MAX_LEVELS + 1, dtype=np.uint64)
+        opts = ReachOpts(inbox_limit, kind, max_states, max_depth, chunk)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _check(self.reach_audit_device(d_tr, d_cn, opts, info, ainfo, d_par, d_msk, level_off, d_term, term_cap, d_words,
+                                       d_sets, d_tw, st), "dsm_reach_audit_device")
+        return _raudit_result(info, ainfo, d_par.cpu().numpy().view(np.uint32), d_msk.cpu().numpy(), level_off,
+                              d_term.cpu().numpy().view(REACH_TERMINAL_DTYPE), d_words.cpu().numpy().view(np.uint32),
+                              d_sets.cpu().numpy(), d_tw.cpu().numpy().view(np.uint32), term_cap)
 
     def explore(self, traces, counts, k, seed, thresh=0x8000, kind=CENSUS_DUMPS, audit=False):
         """k seeded interleavings of ONE system (traces [np, max_instr] u16, counts [np]) in

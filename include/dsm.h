@@ -60,7 +60,9 @@ extern "C" {
                              5 (+fate): additive -- the outcome fate (dsm_reach_fate*,
                                 dsm_fate_seal_point) likewise;
                              5 (+reach batch): additive -- the search of a whole ensemble in one
-                                asynchronous launch (dsm_reach_batch*) likewise */
+                                asynchronous launch (dsm_reach_batch*) likewise;
+                             5 (+reach audit): additive -- the coherence of every reachable state
+                                (dsm_reach_audit*) likewise */
 
 #define DSM_MAX_NP 8             /* bitVector is one byte (README.md:51)                  */
 #define DSM_CACHE_SIZE 4         /* CACHE_SIZE      assignment.c:10                        */
@@ -967,6 +969,64 @@ int dsm_reach_fate_device(dsm_ctx *ctx, const uint16_t *d_trace, const uint32_t 
  * id.  DSM_E_INVAL for arrays that are not a search's (a parent not below its child). */
 int dsm_fate_seal_point(const uint32_t *parents, const uint8_t *cls, uint64_t id, uint64_t *state,
                         uint64_t *depth);
+
+/* ---- reach audit: the coherence of every reachable state ------------------------------------ *
+ * The coherence audit over the reach graph: which invariants a test can break under ANY
+ * interleaving, and the shortest schedule that shows it.  The audit word of a state is exactly the
+ * dsm_audit_states word of its np node records, the first 16 np words of the state in
+ * DSM_REACH_WORDS order; every definition of the coherence audit applies unchanged
+ * (DSM_AUDIT_BAD_RECORD cannot occur on a state the step produced and is still evaluated).
+ *
+ * Four sets of states are summarised, each in a dsm_audit whose ids are STATE ids and whose
+ * `systems` is the set's size.  The set byte of a state has bit k set when it belongs to set k:
+ *   DSM_RAUDIT_ALL        every numbered state;
+ *   DSM_RAUDIT_QUIESCENT  status word 0, every inbox empty, no node waitingForReply (flags bit 0):
+ *                         nothing is in flight, so the directory classes are meant to hold there;
+ *                         in a transient state they are not;
+ *   DSM_RAUDIT_TERMINAL   the terminal states by dsm_reach's definition, with any status (a running
+ *                         state of the unexpanded last level of a truncated search is not one);
+ *   DSM_RAUDIT_COMPLETED  the terminals whose status is DSM_COMPLETED.
+ * Ids ascend with depth (the numbering is breadth first), so ~inv_first[c] is a shallowest state
+ * with class c and dsm_reach_path gives a shortest witness of it; first_depth[k][c] is its level
+ * (slot 7: any class; ~0 where inv_first is 0).
+ *
+ * Flags: DSM_RAUDIT_F_TRUNCATED when the search set DSM_REACH_F_STATES or DSM_REACH_F_DEPTH (a clean
+ * audit then covers the numbered states only), DSM_RAUDIT_F_INEXACT on DSM_REACH_F_COLLISION.
+ * Every summary slot is an integer sum or a max, so host and device agree bit for bit. */
+enum { DSM_RAUDIT_ALL = 0, DSM_RAUDIT_QUIESCENT = 1, DSM_RAUDIT_TERMINAL = 2, DSM_RAUDIT_COMPLETED = 3 };
+#define DSM_RAUDIT_NSETS 4
+#define DSM_RAUDIT_F_TRUNCATED 1u
+#define DSM_RAUDIT_F_INEXACT 2u
+typedef struct dsm_reach_audit_info {
+    dsm_audit set[DSM_RAUDIT_NSETS];              /* ids are STATE ids; systems = the set's size   */
+    uint64_t  first_depth[DSM_RAUDIT_NSETS][8];   /* level of the state inv_first names; ~0: none  */
+    uint64_t  flags;                              /* DSM_RAUDIT_F_TRUNCATED, DSM_RAUDIT_F_INEXACT  */
+    uint64_t  reserved[3];                        /* zero                                          */
+} dsm_reach_audit_info;
+/* The host reference (no GPU needed): dsm_reach, the states again from the round that first made
+ * each, dsm_audit_states on each.  rinfo, parents, masks, level_off and terminals are dsm_reach's,
+ * passed through.  words[max_states] and sets[max_states]; term_words[i] = words[terminals[i].state]
+ * for i < min(term_cap, terminals), so outcomes are audited without a second look-up (it does not
+ * need `terminals` itself).  Every output may be NULL; entries at and after rinfo->states
+ * (term_words: at and after min(term_cap, terminals)) are not written.  A bad argument is
+ * DSM_E_INVAL with nothing written. */
+int dsm_reach_audit(int np, const uint16_t *trace, const uint32_t *counts, uint32_t stride,
+                    const dsm_reach_opts *opts, dsm_reach_info *rinfo, dsm_reach_audit_info *ainfo,
+                    uint32_t *parents, uint8_t *masks, uint64_t *level_off,
+                    dsm_reach_terminal *terminals, uint64_t term_cap, uint32_t *words,
+                    uint8_t *sets, uint32_t *term_words);
+/* The same on the GPU (dsm_reach_device's search, the state store and the class bytes of
+ * dsm_reach_dist_device, then reach_audit_kernel: one lane per state).  d_parents, d_masks,
+ * d_terminals, d_words, d_sets and d_term_words are device buffers (d_terminals 8-byte aligned,
+ * d_parents, d_words and d_term_words 4-byte; a misaligned output is DSM_E_INVAL); rinfo, ainfo and
+ * level_off host memory.  SYNCHRONOUS like dsm_reach_fate_device; everything it allocates is freed
+ * before it returns: DSM_E_NOMEM with nothing leaked when it does not fit.  Every written value
+ * equals the host reference's bit for bit. */
+int dsm_reach_audit_device(dsm_ctx *ctx, const uint16_t *d_trace, const uint32_t *d_counts,
+                           const dsm_reach_opts *opts, dsm_reach_info *rinfo,
+                           dsm_reach_audit_info *ainfo, uint32_t *d_parents, uint8_t *d_masks,
+                           uint64_t *level_off, dsm_reach_terminal *d_terminals, uint64_t term_cap,
+                           uint32_t *d_words, uint8_t *d_sets, uint32_t *d_term_words, void *stream);
 
 /* ---- multi-GPU group: RCCL over xGMI --------------------------------------- *
  * Systems are independent, so an ensemble shards over GPUs with no data-path exchange; the
