@@ -80,7 +80,10 @@ struct SimArgs {
 };
 /* the argument blocks of one run, written to device memory by args_kernel (stream-ordered:
  * no pinned staging whose reuse would need a host wait) */
-struct SimArgsPack { SimArgs a[3]; };
+struct SimArgsPack { SimArgs a[4]; };
+#define ARGS_SERX 3         /* ser_kernel's block: the resume pass's, but for ffsel = 1 and scan = the two
+                             * words at CTRL_SERX, where ser_multi_kernel says that ser_kernel has nothing
+                             * to do (dsm_ser.hip); dsm_plan.h's ARGS_* name the first three */
 
 /* counter slots (dsm_counters order) */
 enum { K_MSGS = 13, K_INSTRS = 14, K_ROUNDS = 15, K_SYSTEMS = 16, K_STATUS = 17, K_DHASH = 22,
@@ -92,7 +95,8 @@ enum { K_MSGS = 13, K_INSTRS = 14, K_ROUNDS = 15, K_SYSTEMS = 16, K_STATUS = 17,
 static_assert(sizeof(dsm_counters) == DSM_NCOUNTERS * 8 && K_SERMAC < DSM_NCOUNTERS, "dsm_counters slots");
 
 /* dsm_ctx.d_ctrl: CTRL_WORDS words, zeroed per run -- the claim shards of the fast, re-run and
- * resume launches (8 shard counters, 32 words apart), then single counts */
+ * resume launches (8 shard counters, 32 words apart; the serial pass's kernels claim from the
+ * resume launch's words 0, 32 and 64), then single counts */
 #define CTRL_WORDS 2048
 #define CTRL_FAST 0
 #define CTRL_FB 256
@@ -102,6 +106,7 @@ static_assert(sizeof(dsm_counters) == DSM_NCOUNTERS * 8 && K_SERMAC < DSM_NCOUNT
 #define CTRL_SUSPL 1568     /* order_kernel: ... lone, of the long class, listed from the top down */
 #define CTRL_SUSPS 1600     /* order_kernel: ... lone, of the other, listed from the bottom up */
 #define CTRL_SUSPM 1632     /* order_kernel: ... multi-node, listed in the buffer's second half */
+#define CTRL_SERX 1664      /* ser_multi_kernel: ser_kernel's verdict words (ARGS_SERX) */
 #define CTRL_SCAN 1792      /* ffscan_kernel's sample counts */
 
 #endif

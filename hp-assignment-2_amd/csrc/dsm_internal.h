@@ -134,6 +134,14 @@ extern "C" int dsm_debug_order_state(dsm_ctx *c, uint32_t *counts, uint32_t *lis
                                      uint64_t cap, uint64_t sys, uint32_t *rec, uint32_t rec_cap,
                                      uint32_t *rec_words, int *host_long);
 
+/* Test-only view of the serial pass's claim counters after the last run (not part of the ABI;
+ * tests/test_gpu_ser_multi.py).  out[0]: 1 when ser_multi_kernel told ser_kernel to exit (it
+ * took the pass, or the fast-forward resume had it); out[1]: claims made by ser_kernel;
+ * out[2], out[3]: by ser_multi_kernel, from the counter of the lone classes and from the
+ * multi-node class's.  A lane claims until its counter passes the class, so a counter ends at
+ * its class's size or above. */
+extern "C" int dsm_debug_ser_claims(dsm_ctx *c, uint32_t *out);
+
 /* Measurement-only view of the last dsm_reach_device call that ran with DSM_REACH_TIMING=1 in the
  * environment (not part of the ABI; tools/reach_time.py): device milliseconds summed per kernel
  * class -- count (with its scans), expand, insert, resolve (with its scan), settle -- and the
@@ -197,7 +205,8 @@ DSM_LOCAL void dsm_sim_launch(sim_fn f, unsigned grid, unsigned threads, hipStre
 DSM_LOCAL int dsm_sim_lds_bytes(int ring, int waves);
 /* dsm_ser.hip: order_kernel and ser_kernel<np, cap> */
 DSM_LOCAL void dsm_order_launch(int np, unsigned blocks, hipStream_t st, const SimArgs *a);
-DSM_LOCAL void dsm_ser_launch(int np, bool cap, unsigned blocks, hipStream_t st, const SimArgs *a);
+DSM_LOCAL void dsm_ser_launch(int np, bool cap, unsigned blocks, hipStream_t st, const SimArgs *a,
+                              const SimArgs *ax, uint32_t *took);
 /* dsm_kernels.hip: args_kernel (a run's argument blocks to device memory, in stream order),
  * ffscan_kernel and digest_kernel */
 DSM_LOCAL void dsm_args_launch(const SimArgsPack &pk, SimArgs *dst, hipStream_t st);

@@ -56,6 +56,16 @@
                                against 3,156 per iteration (SER_PROBE 2, C3; round 8: 12,188 / 3,568 and
                                4).  Kernel ms 4 / 3 / 2: C3 30.86 / 30.88 / 30.54, C5 19.62 / 19.60 / 19.58 */
 #endif
+/* the multi-node class's dedicated waves (dsm_ser_body.h, ser_multi_kernel) */
+#ifndef SER_MW_SHARE
+#define SER_MW_SHARE 8      /* the class is spread over up to 1 / SER_MW_SHARE of the grid's waves (a
+                               class beyond that packs them, up to 64 to a wave).  C3, 46 multi-node
+                               systems, SIM_TAILPROBE 2 builds, last end of a dedicated wave / kernel ms:
+                               64 to a wave 9.3-10.1 / 31.3-32.6, 8 to a wave 8.9-9.4 / 30.7-31.4, one
+                               each 5.6-5.7 / 27.9-28.3; the parent's mixed wave 9.0 / 30.9-31.0
+                               (profiles/r10/tail_variants.txt).  Not kept: runs in such a wave only
+                               when every running lane is eligible (64 to a wave: 10.6-11.1) */
+#endif
 /* what ser_macro (a lone node's whole transaction in one step) covers besides hits and misses */
 #ifndef SER_DEAD_FWD
 #define SER_DEAD_FWD 1      /* a system's dead-end forward */

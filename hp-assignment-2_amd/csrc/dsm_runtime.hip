@@ -276,6 +276,16 @@ extern "C" int dsm_debug_order_state(dsm_ctx *c, uint32_t *counts, uint32_t *lis
     return pl.order ? 1 : 0;
 }
 
+extern "C" int dsm_debug_ser_claims(dsm_ctx *c, uint32_t *out) {
+    if (!c || !out) return DSM_E_INVAL;
+    HIPCK(hipSetDevice(c->device));
+    HIPCK(hipStreamSynchronize(c->last_st ? c->last_st : c->stream));
+    const unsigned int at[4] = {CTRL_SERX, CTRL_RES, CTRL_RES + 32, CTRL_RES + 64};
+    for (int i = 0; i < 4; ++i)
+        HIPCK(hipMemcpy(&out[i], c->d_ctrl + at[i], sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return DSM_OK;
+}
+
 /* the schedule's scalar fields of an argument block, from the plan */
 static void put_sched(SimArgs &a, const PlanArgs &s) {
     a.rsh = s.rsh; a.budget = s.budget; a.resume = s.resume; a.ffsel = s.ffsel;
@@ -394,6 +404,10 @@ static int run_engine(dsm_ctx *c, bool gen, const dsm_gen *g, uint64_t first_sys
     C.claim = c->d_ctrl + CTRL_RES;
     A.scan = C.scan = c->d_ctrl + CTRL_SCAN;
     for (int i = 0; i < 3; ++i) put_sched(pk.a[i], p.args[i]);
+    SimArgs &X = pk.a[ARGS_SERX];     /* ser_kernel's: its verdict is ser_multi_kernel's word */
+    X = C;
+    X.ffsel = 1;
+    X.scan = c->d_ctrl + CTRL_SERX;
     dsm_args_launch(pk, c->d_args, st);
     HIPCK(hipGetLastError());
 
@@ -417,7 +431,7 @@ static int run_engine(dsm_ctx *c, bool gen, const dsm_gen *g, uint64_t first_sys
             dsm_order_launch(np, p.order_blocks, st, a);
             break;
         case PK_SER:
-            dsm_ser_launch(np, L.mode != 0, p.ser_blocks, st, a);
+            dsm_ser_launch(np, L.mode != 0, p.ser_blocks, st, a, c->d_args + ARGS_SERX, c->d_ctrl + CTRL_SERX);
             break;
         case PK_RERUN:
             if (timed) {

@@ -221,6 +221,7 @@ def lib():
             "dsm_debug_exscan_device": (i32, [vp, vp, u64, vp, vp]),
             "dsm_debug_order_state": (i32, [vp, vp, vp, vp, u64, u64, vp, u32, ctypes.POINTER(u32),
                                             ctypes.POINTER(i32)]),
+            "dsm_debug_ser_claims": (i32, [vp, vp]),
         }
         for name, (res, args) in sig.items():
             if os.environ.get("DSM_LIB") and not hasattr(L, name):
@@ -1556,6 +1557,14 @@ class Engine:
             d["order_long"] = np.concatenate([order[n:n + nm], order[n - (nl - nm):n][::-1]])
             d["order_short"] = order[:ns][::-1].copy()
         return d
+
+    def ser_claims(self):
+        """Test-only: the serial pass's claim counters after the last run -- `took` (1:
+        ser_multi_kernel told ser_kernel to exit), `plain` (claims made by ser_kernel), `rest` and
+        `multi` (by ser_multi_kernel: the lone classes' counter, the multi-node class's)."""
+        out = np.zeros(4, dtype=np.uint32)
+        _check(lib().dsm_debug_ser_claims(self.ctx, _ptr(out)), "dsm_debug_ser_claims")
+        return dict(zip(("took", "plain", "rest", "multi"), (int(x) for x in out)))
 
     def launch_info(self):
         """dsm_launch_info of the last run, plus `kernels`: the kernels that did its work

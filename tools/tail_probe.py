@@ -3,7 +3,9 @@
 SIM_TAILPROBE build (DSM_LIB=ab/libdsm_tail.so; results exact, timing not the default's):
 a histogram of wave end times (ms after the wave started) that the probe build leaves in the
 counter slots msgs_by_type 0-11, and the mean wave lifetime (slot 12, 10-ns ticks); the
-serial pass's wave end times in slots 34-39 and its wave iterations (ser_iterations, slot 33).  A wide
+serial pass's wave end times in slots 34-39 and its wave iterations (ser_iterations, slot 33); from a
+SIM_TAILPROBE=2 build also the serial pass's longest and last system, which waves held the
+multi-node systems and when those and the other waves ended (slots 0-12).  A wide
 spread of end times is the budget pass's tail: SIMDs idle while its last waves finish."""
 import json
 import os
@@ -51,4 +53,11 @@ with pydsm.Engine(8, 4096, timing=True) as eng:
                           "ser_systems_over_4000_iters": int(raw[2]),
                           "ser_nonlone_iters": int(raw[3]), "ser_all_iters": int(raw[4]),
                           "ser_nonlone_systems": int(raw[5]),
+                          # ... which waves hold the multi-node systems and what ends the pass:
+                          # the waves that held one, the latest wave end (ms after the wave
+                          # started) among them and among the others, the ends in 1-ms bins
+                          "ser_multi_waves": int(raw[8]),
+                          "ser_multi_wave_last_end_ms": round(int(raw[6]) / 1e5, 3),
+                          "ser_other_wave_last_end_ms": round(int(raw[7]) / 1e5, 3),
+                          "ser_end_ms_bins": {f"{k}-{k + 1}": int(raw[7 + k]) for k in range(2, 6)},
                           "final_hash": hex(int(raw[23]))}), flush=True)
