@@ -42,7 +42,6 @@
 #include <string.h>
 
 #include <algorithm>
-#include <new>
 #include <unordered_map>
 #include <vector>
 
@@ -114,10 +113,10 @@ __global__ void __launch_bounds__(RT) dist_finish_kernel(const u64 *sink, const 
     }
 }
 
-/* terminals: dsm_reach_terminal records, five 64-bit words, the state id first */
+/* terminals: dsm_reach_terminal records as the search wrote them */
 __global__ void __launch_bounds__(RT) dist_gather_kernel(const u64 *sink, u64 n, const u64 *terminals, u64 nt, u64 *out) {
     for (u64 i = (u64)blockIdx.x * RT + threadIdx.x; i < nt; i += (u64)gridDim.x * RT) {
-        const u64 id = terminals[5 * i];
+        const u64 id = rs_terminal_state(terminals, i);
         out[i] = id < n ? sink[id] : 0;
     }
 }
@@ -307,15 +306,10 @@ int host_entry(int np, const uint16_t *trace, const uint32_t *counts, uint32_t s
     if ((np != 4 && np != 8) || !trace || !counts || stride == 0 || stride > DSM_MAX_INSTR || !opts_ok(opts, &L) ||
         !args_ok(thresh, n_thresh, max_rounds, &R))
         return DSM_E_INVAL;
-    try {
-        if (np == 4)
-            return dist_host<4>(trace, counts, stride, opts, L, thresh, n_thresh, R, rinfo, dinfo, terminals, term_mass, term_cap,
-                                round_mass, dump);
-        return dist_host<8>(trace, counts, stride, opts, L, thresh, n_thresh, R, rinfo, dinfo, terminals, term_mass, term_cap,
-                            round_mass, dump);
-    } catch (const std::bad_alloc &) {
-        return DSM_E_NOMEM;
-    }
+    return by_np(np, [&](auto n) {
+        return dist_host<decltype(n)::value>(trace, counts, stride, opts, L, thresh, n_thresh, R, rinfo, dinfo, terminals, term_mass,
+                                             term_cap, round_mass, dump);
+    });
 }
 
 int device_entry(dsm_ctx *c, const uint16_t *d_trace, const uint32_t *d_counts, const dsm_reach_opts *opts,
@@ -327,15 +321,10 @@ int device_entry(dsm_ctx *c, const uint16_t *d_trace, const uint32_t *d_counts, 
         ((uintptr_t)d_term_mass & 7u) || ((uintptr_t)d_terminals & 7u))
         return DSM_E_INVAL;
     HIPCK(hipSetDevice(c->device));
-    try {
-        if (c->cfg.np == 4)
-            return dist_device<4>(c, d_trace, d_counts, opts, L, thresh, n_thresh, R, rinfo, dinfo, d_terminals, (u64 *)d_term_mass,
-                                  term_cap, round_mass, dump, (hipStream_t)stream);
-        return dist_device<8>(c, d_trace, d_counts, opts, L, thresh, n_thresh, R, rinfo, dinfo, d_terminals, (u64 *)d_term_mass,
-                              term_cap, round_mass, dump, (hipStream_t)stream);
-    } catch (const std::bad_alloc &) {
-        return DSM_E_NOMEM;
-    }
+    return by_np(c->cfg.np, [&](auto n) {
+        return dist_device<decltype(n)::value>(c, d_trace, d_counts, opts, L, thresh, n_thresh, R, rinfo, dinfo, d_terminals,
+                                               (u64 *)d_term_mass, term_cap, round_mass, dump, (hipStream_t)stream);
+    });
 }
 
 }  // namespace

@@ -1,7 +1,7 @@
 /*
  * dsm_dist_dev.h -- the reach graph as an edge list in device memory, built once for the outcome
- * distribution (dsm_dist.hip) and the outcome fate (dsm_fate.hip): the search (dsm_reach_device),
- * then
+ * distribution (dsm_dist.hip) and the outcome fate (dsm_fate.hip), and its first half for the reach
+ * audit (dsm_raudit.hip): the search (dsm_reach_device), then
  *
  *   dist_rebuild_kernel<NP>   level by level, one lane per state: state[id] = rs_round(state[
  *                             parents[id]], masks[id]) in a word-major store (word i of state id at
@@ -21,8 +21,9 @@
  * The edges are in source order, a source's in ascending order of the mask: state id's are
  * [offs[id], offs[id + 1]), edge offs[id] + j - 1 the one of rank j.  The build is two functions,
  * dist_graph_states (search, store, classes) and dist_graph_edges (table, edges): the reach audit
- * (dsm_raudit.hip) needs the states alone.  Internal to those three units; everything is in an
- * unnamed namespace, so each unit holds its own instantiations.
+ * (dsm_raudit.hip) needs the states alone.  Internal to the three units that include it --
+ * dsm_dist.hip, dsm_fate.hip, dsm_raudit.hip -- and they get dsm_reach_dev.h through it; everything
+ * is in an unnamed namespace, so each unit holds its own instantiations.
  */
 #ifndef DSM_DIST_DEV_H
 #define DSM_DIST_DEV_H
@@ -81,7 +82,7 @@ __global__ void __launch_bounds__(RT) dist_class_kernel(const uint32_t *store, u
         const uint32_t c = dist_class<NP>(m, a, id < n_exp);
         cls[id] = (uint8_t)c;
         A[id] = (uint8_t)(c == DIST_RUNNING ? a : 0u);
-        cnt[id] = c == DIST_RUNNING ? (1u << __builtin_popcount(a)) - 1u : 0u;
+        cnt[id] = c == DIST_RUNNING ? rs_succ_count(a) : 0u;
     }
 }
 
@@ -270,8 +271,7 @@ int dist_graph_edges(dsm_ctx *c, const uint16_t *d_trace, const uint32_t *d_coun
     HIPCK(hipMemsetAsync(b_ctr.p, 0, sizeof(DistCtr), st));
 
     /* 3. fingerprint -> id */
-    u64 slots = 64;
-    while (slots < 2 * n) slots <<= 1;
+    const u64 slots = visit_slots(n);
     DevBuf b_keys, b_vals;
     if ((rc = b_keys.alloc(slots * 8)) || (rc = b_vals.alloc(slots * 4))) return rc;
     HIPCK(hipMemsetAsync(b_keys.p, 0, slots * 8, st));
@@ -403,7 +403,7 @@ int dist_host_graph(const uint16_t *trace, const uint32_t *counts, uint32_t stri
         g.cls[id] = (uint8_t)dist_class<NP>(s, a, id < n_exp);
         if (g.cls[id] != DIST_RUNNING) continue;
         g.A[id] = (uint8_t)a;
-        const uint32_t k = (uint32_t)__builtin_popcount(a), cnt = (1u << k) - 1u;
+        const uint32_t k = (uint32_t)__builtin_popcount(a), cnt = rs_succ_count(a);
         for (uint32_t j = 1; j <= cnt; ++j) {
             const uint32_t mask = rs_deposit(j, a);
             memcpy(tmp, &S[(size_t)id * W], W * 4);

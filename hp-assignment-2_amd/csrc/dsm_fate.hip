@@ -45,7 +45,6 @@
 #include <string.h>
 
 #include <algorithm>
-#include <new>
 #include <vector>
 
 #include "dsm_dist_dev.h"
@@ -669,15 +668,10 @@ extern "C" int dsm_reach_fate(int np, const uint16_t *trace, const uint32_t *cou
     if ((np != 4 && np != 8) || !trace || !counts || stride == 0 || stride > DSM_MAX_INSTR || !opts_ok(opts, &L) ||
         !fate_args_ok(fopts, thresh, n_thresh, &S))
         return DSM_E_INVAL;
-    try {
-        if (np == 4)
-            return fate_host<4>(trace, counts, stride, opts, L, fopts, S, thresh, n_thresh, rinfo, finfo, values, parents, masks,
-                                level_off, terminals, term_cap, cls, lo, hi);
-        return fate_host<8>(trace, counts, stride, opts, L, fopts, S, thresh, n_thresh, rinfo, finfo, values, parents, masks,
-                            level_off, terminals, term_cap, cls, lo, hi);
-    } catch (const std::bad_alloc &) {
-        return DSM_E_NOMEM;
-    }
+    return by_np(np, [&](auto n) {
+        return fate_host<decltype(n)::value>(trace, counts, stride, opts, L, fopts, S, thresh, n_thresh, rinfo, finfo, values, parents,
+                                             masks, level_off, terminals, term_cap, cls, lo, hi);
+    });
 }
 
 extern "C" int dsm_reach_fate_device(dsm_ctx *c, const uint16_t *d_trace, const uint32_t *d_counts,
@@ -691,15 +685,11 @@ extern "C" int dsm_reach_fate_device(dsm_ctx *c, const uint16_t *d_trace, const 
         ((uintptr_t)d_terminals & 7u) || ((uintptr_t)d_lo & 7u) || ((uintptr_t)d_hi & 7u) || ((uintptr_t)d_parents & 3u))
         return DSM_E_INVAL;
     HIPCK(hipSetDevice(c->device));
-    try {
-        if (c->cfg.np == 4)
-            return fate_device<4>(c, d_trace, d_counts, opts, L, fopts, S, thresh, n_thresh, rinfo, finfo, values, d_parents,
-                                  d_masks, level_off, d_terminals, term_cap, d_cls, (u64 *)d_lo, (u64 *)d_hi, (hipStream_t)stream);
-        return fate_device<8>(c, d_trace, d_counts, opts, L, fopts, S, thresh, n_thresh, rinfo, finfo, values, d_parents, d_masks,
-                              level_off, d_terminals, term_cap, d_cls, (u64 *)d_lo, (u64 *)d_hi, (hipStream_t)stream);
-    } catch (const std::bad_alloc &) {
-        return DSM_E_NOMEM;
-    }
+    return by_np(c->cfg.np, [&](auto n) {
+        return fate_device<decltype(n)::value>(c, d_trace, d_counts, opts, L, fopts, S, thresh, n_thresh, rinfo, finfo, values,
+                                               d_parents, d_masks, level_off, d_terminals, term_cap, d_cls, (u64 *)d_lo, (u64 *)d_hi,
+                                               (hipStream_t)stream);
+    });
 }
 
 extern "C" int dsm_fate_seal_point(const uint32_t *parents, const uint8_t *cls, uint64_t id, uint64_t *state,

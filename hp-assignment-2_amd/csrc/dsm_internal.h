@@ -17,12 +17,14 @@
  *                    one asynchronous launch; its host loop
  *   dsm_raudit.hip   reach audit: the coherence audit word of every state of the reach graph, one
  *                    lane per state over the rebuilt store; its host reference
- * The last four replay ONE system a round at a time: the round is dsm_step.h's st_round, once,
- * under dsm_events.h's and dsm_reach.h's inbox and log policies, the hashes are dsm_hash.h's,
- * dsm_reach_dev.h holds the device plumbing dsm_reach.hip, dsm_dist.hip and dsm_fate.hip share, and
- * dsm_dist_dev.h the edge list (its kernels and its host twin) of the last two; dsm_raudit.hip uses
- * the first half of that build (search, state store, classes) and dsm_audit_fn.h, the audit's
- * arithmetic, with dsm_audit.hip.
+ * The last six replay ONE system a round at a time: the round is dsm_step.h's st_round, once,
+ * under dsm_events.h's and dsm_reach.h's inbox and log policies, and the hashes are dsm_hash.h's.
+ * The last five are the reach family.  dsm_reach.h holds the search's state and the rules of a
+ * level (host and device), dsm_reach_dev.h the device plumbing all five share: the successor of a
+ * level, the visited table's protocol of the two searches, the np dispatch of the entry points.
+ * dsm_dist_dev.h is the edge list (its kernels and its host twin) of dsm_dist.hip and dsm_fate.hip;
+ * dsm_raudit.hip uses the first half of that build (search, state store, classes) and
+ * dsm_audit_fn.h, the audit's arithmetic, with dsm_audit.hip.
  * Each kernel is launched from the unit that defines or instantiates it.  Not part of the ABI.
  */
 #ifndef DSM_INTERNAL_H
@@ -176,6 +178,13 @@ extern "C" int dsm_debug_raudit_times(double *ms, uint64_t *bytes);
  * state[DSM_REACH_WORDS(np)] in that order, cls its class byte (dsm_dist.h: 0 running, 1 escaped,
  * 2 + status terminal) -> the audit word and the set byte.  The body is one function for both. */
 extern "C" int dsm_debug_raudit_lane(int np, const uint32_t *state, uint32_t cls, uint32_t *word, uint32_t *set);
+
+/* Test-only (not part of the ABI): dsm_reach_dev.h's visit_resolve on the host -- what candidate j
+ * of a chunk is, whose slot of the visited table holds meta after the insert phase: 0 new, 1 seen,
+ * 2 a fingerprint collision.  cand: the chunk's candidates, word i of candidate j at
+ * cand[i * cs + j], words words each.  DSM_E_INVAL where j, or the candidate a pending meta names,
+ * is not below cs. */
+extern "C" int dsm_debug_visit_resolve(uint64_t meta, uint64_t j, const uint32_t *cand, uint64_t cs, uint32_t words);
 
 /* Measurement-only view of the last dsm_reach_batch_device call (not part of the ABI;
  * tools/reach_batch_time.py): the systems it kept in flight and the bytes of the ctx's scratch. */

@@ -34,7 +34,6 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <new>
 #include <vector>
 
 /* this unit instantiates the first half of dsm_dist_dev.h only: its table and edge kernels stay unused */
@@ -52,7 +51,6 @@ constexpr int RA_PER_CU8 = 3;                /* the audit kernel's at np 8: it h
 constexpr int RA_PHASES = 4;                 /* search, rebuild, class, audit */
 constexpr int RA_COUNTERS = A_CLASS + DSM_AUDIT_NCLASS;   /* systems, violating, lines, bad, 7 classes */
 
-static_assert(sizeof(dsm_reach_terminal) == 40, "raudit_gather_kernel reads a terminal as five 64-bit words");
 static_assert(sizeof(dsm_audit) == DSM_NAUDIT * 8, "the summaries are DSM_NAUDIT slots each");
 static_assert(DSM_RAUDIT_NSETS * DSM_NAUDIT <= RT, "one thread per summary slot");
 
@@ -213,11 +211,11 @@ __global__ void __launch_bounds__(RT) raudit_sum_kernel(const uint32_t *words, c
     }
 }
 
-/* terms: dsm_reach_terminal records, the state id their first 64-bit word */
+/* terms: dsm_reach_terminal records as the search wrote them */
 __global__ void __launch_bounds__(RT) raudit_gather_kernel(const u64 *terms, u64 cnt, const uint32_t *words, u64 n,
                                                            uint32_t *out) {
     for (u64 i = (u64)blockIdx.x * RT + threadIdx.x; i < cnt; i += (u64)gridDim.x * RT) {
-        const u64 s = terms[5 * i];
+        const u64 s = rs_terminal_state(terms, i);
         out[i] = s < n ? words[s] : 0u;           /* a search's terminals are numbered states */
     }
 }
@@ -374,15 +372,10 @@ extern "C" int dsm_reach_audit(int np, const uint16_t *trace, const uint32_t *co
     uint32_t L;
     if ((np != 4 && np != 8) || !trace || !counts || stride == 0 || stride > DSM_MAX_INSTR || !opts_ok(opts, &L))
         return DSM_E_INVAL;
-    try {
-        if (np == 4)
-            return raudit_host<4>(trace, counts, stride, opts, L, rinfo, ainfo, parents, masks, level_off, terminals, term_cap,
-                                  words, sets, term_words);
-        return raudit_host<8>(trace, counts, stride, opts, L, rinfo, ainfo, parents, masks, level_off, terminals, term_cap, words,
-                              sets, term_words);
-    } catch (const std::bad_alloc &) {
-        return DSM_E_NOMEM;
-    }
+    return by_np(np, [&](auto n) {
+        return raudit_host<decltype(n)::value>(trace, counts, stride, opts, L, rinfo, ainfo, parents, masks, level_off, terminals,
+                                               term_cap, words, sets, term_words);
+    });
 }
 
 extern "C" int dsm_reach_audit_device(dsm_ctx *c, const uint16_t *d_trace, const uint32_t *d_counts,
@@ -395,15 +388,10 @@ extern "C" int dsm_reach_audit_device(dsm_ctx *c, const uint16_t *d_trace, const
         ((uintptr_t)d_words & 3u) || ((uintptr_t)d_term_words & 3u))
         return DSM_E_INVAL;
     HIPCK(hipSetDevice(c->device));
-    try {
-        if (c->cfg.np == 4)
-            return raudit_device<4>(c, d_trace, d_counts, opts, L, rinfo, ainfo, d_parents, d_masks, level_off, d_terminals,
-                                    term_cap, d_words, d_sets, d_term_words, (hipStream_t)stream);
-        return raudit_device<8>(c, d_trace, d_counts, opts, L, rinfo, ainfo, d_parents, d_masks, level_off, d_terminals, term_cap,
-                                d_words, d_sets, d_term_words, (hipStream_t)stream);
-    } catch (const std::bad_alloc &) {
-        return DSM_E_NOMEM;
-    }
+    return by_np(c->cfg.np, [&](auto n) {
+        return raudit_device<decltype(n)::value>(c, d_trace, d_counts, opts, L, rinfo, ainfo, d_parents, d_masks, level_off,
+                                                 d_terminals, term_cap, d_words, d_sets, d_term_words, (hipStream_t)stream);
+    });
 }
 
 /* test only (dsm_internal.h): the kernel's lane body on the host */

@@ -1,6 +1,7 @@
 /*
  * dsm_reach.h -- the exhaustive exploration's state and what is the search's own around its
- * one-round step, shared by the gfx950 kernels and the host (dsm_reach.hip, dsm_dist.hip).
+ * one-round step -- the rules of a level, the terminal record, the end of a search -- shared by
+ * the gfx950 kernels and the host of the whole reach family (dsm_reach_dev.h lists its units).
  *
  * A state of ONE system under inbox limit L <= RS_RING: RS_WORDS(np) words behind an StMem:
  *
@@ -155,6 +156,55 @@ DSM_HD bool rs_terminal(const StMem &m, uint32_t enabled, dsm_sys_result *res) {
         res->final_hash = st_final_hash<NP>(m);
     }
     return true;
+}
+
+/* ---- the rules of a level, the same for the host search, the search kernels and the batch ------ */
+/* the successors of a state with enabled set A: A's non-empty subsets */
+DSM_HD uint32_t rs_succ_count(uint32_t A) { return (1u << __builtin_popcount(A)) - 1u; }
+
+/* one state of a level: its enabled set, its successor count (0 for a terminal state), its
+ * terminal flag, its deepest inbox */
+struct RsItem { uint32_t A, cnt, fill; bool terminal; };
+template <int NP>
+DSM_HD RsItem rs_level_item(const StMem &m, const uint32_t *counts, uint32_t stride) {
+    const uint32_t A = rs_enabled<NP>(m, counts, stride);
+    const bool t = rs_terminal<NP>(m, A, nullptr);
+    return {A, t ? 0u : rs_succ_count(A), rs_max_fill<NP>(m), t};
+}
+
+/* the end of a level: does the search stop before expanding level `depth`, which has `total`
+ * successors?  max_depth 0 = none */
+DSM_HD bool rs_stop_before_expand(uint32_t max_depth, uint64_t depth, uint64_t total, uint64_t *flags) {
+    if (total == 0) return true;
+    if ((max_depth && depth >= max_depth) || depth + 1 >= DSM_REACH_MAX_LEVELS) {
+        *flags |= DSM_REACH_F_DEPTH;
+        return true;
+    }
+    return false;
+}
+
+/* A terminal record in device memory is dsm_reach_terminal as five 64-bit words: the state id,
+ * {status, rounds}, {msgs, instrs}, dump_hash, final_hash. */
+static_assert(sizeof(dsm_reach_terminal) == 40, "the kernels read and write dsm_reach_terminal as five 64-bit words");
+DSM_HD unsigned long long *rs_terminal_at(unsigned long long *terms, uint64_t k) { return terms + 5 * k; }
+DSM_HD uint64_t rs_terminal_state(const unsigned long long *terms, uint64_t i) { return terms[5 * i]; }
+DSM_HD void rs_put_terminal(unsigned long long *t, uint64_t id, const dsm_sys_result &res) {
+    t[0] = id;
+    t[1] = (uint64_t)res.status;             /* rounds 0 */
+    t[2] = 0;                                /* msgs, instrs 0 */
+    t[3] = res.dump_hash;
+    t[4] = res.final_hash;
+}
+
+/* The end of a search: loff[0 .. levels) the first ids of its levels.  *r gets states, levels and
+ * the collision count with its flag, then goes to info, and level_off gets the levels + 1 offsets
+ * (either may be null). */
+DSM_HD void rs_close(dsm_reach_info *r, const uint64_t *loff, uint64_t levels, uint64_t states, uint64_t collisions,
+                     dsm_reach_info *info, uint64_t *level_off) {
+    r->states = states; r->levels = levels; r->fp_collisions = collisions;
+    if (collisions) r->flags |= DSM_REACH_F_COLLISION;
+    if (info) *info = *r;
+    for (uint64_t d = 0; level_off && d <= levels; ++d) level_off[d] = d < levels ? loff[d] : states;
 }
 
 #endif

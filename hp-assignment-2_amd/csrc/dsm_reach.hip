@@ -18,17 +18,13 @@
  *                             copied into the chunk buffer (word-major across the chunk), one
  *                             rs_round in place with the micro-op table in LDS (dsm_reach_dev.h
  *                             successor), the fingerprint
- *   reach_insert_kernel       the fingerprint into the visited table (open addressing, {key,
- *                             meta} slots): compare-and-swap on the key, then an unconditional max
- *                             on meta with a pending value that encodes ~candidate index.  A
- *                             settled slot's meta (top bit, state id) compares above every pending
- *                             value, so after the kernel a slot's owner is the lowest candidate
- *                             of the chunk, or an earlier state.
- *   reach_resolve_kernel      a candidate is new exactly when it owns its slot; a non-owner whose
- *                             owner is in the same chunk compares the two full states (the
- *                             collision count); then a scan of the new-flags gives the ids
- *   reach_settle_kernel       owners write meta = settled | id; new states move to the store in
- *                             id order with their parent, mask and fingerprint
+ *   reach_insert_kernel       the fingerprint into the visited table (visit_insert)
+ *   reach_resolve_kernel      new, seen or a collision (visit_resolve, the collision count); then a
+ *                             scan of the new-flags gives the ids
+ *   reach_settle_kernel       new states move to the store in id order with their parent, mask
+ *                             and fingerprint (visit_settle)
+ * The table's protocol -- and why a slot's owner is the lowest candidate of the chunk, or an
+ * earlier state -- is dsm_reach_dev.h's, "the visited table"; a level's rules are dsm_reach.h's.
  * The scans are three small kernels of this unit (tile sums, one workgroup over the sums, tile
  * scans; dsm_exscan_launch, which dsm_dist.hip uses too): integers, so deterministic, and no
  * workgroup ever waits for another.  Atomics are
@@ -46,7 +42,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <new>
 #include <unordered_map>
 #include <vector>
 
@@ -54,13 +49,9 @@
 
 namespace {
 
-constexpr u64 SETTLED = 1ull << 63;
-
 struct ReachCtr {                            /* device counters of one call */
     u64 coll, table_full, max_fill, by_status[5];
 };
-
-DSM_HD u64 pending_of(u64 j) { return ~j & ~SETTLED; }
 
 /* ---- exclusive scan of n uint32 into n + 1 uint64 (out[n] = the total) --------------------- */
 constexpr int SCAN_ITEMS = 8;
@@ -142,12 +133,11 @@ __global__ void __launch_bounds__(RT) reach_count_kernel(const uint32_t *store, 
     const u64 i = (u64)blockIdx.x * RT + threadIdx.x;
     if (i >= n) return;
     const StMem m = {const_cast<uint32_t *>(store) + lo + i, (size_t)cap};
-    const uint32_t a = rs_enabled<NP>(m, counts, stride);
-    const bool t = rs_terminal<NP>(m, a, nullptr);
-    A[i] = a;
-    cnt[i] = t ? 0u : (1u << __builtin_popcount(a)) - 1u;
-    term[i] = t ? 1u : 0u;
-    const u64 f = rs_max_fill<NP>(m);
+    const RsItem it = rs_level_item<NP>(m, counts, stride);
+    A[i] = it.A;
+    cnt[i] = it.cnt;
+    term[i] = it.terminal ? 1u : 0u;
+    const u64 f = it.fill;
     if (f > __hip_atomic_load(&ctr->max_fill, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
         __hip_atomic_fetch_max(&ctr->max_fill, f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -163,14 +153,7 @@ __global__ void __launch_bounds__(RT) reach_term_kernel(const uint32_t *store, u
     (void)rs_terminal<NP>(m, 0u, &res);
     __hip_atomic_fetch_add(&ctr->by_status[res.status & 7u], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const u64 k = tbase + toff[i];
-    if (terminals && k < term_cap) {         /* dsm_reach_terminal: five 64-bit words */
-        u64 *t = terminals + 5 * k;
-        t[0] = lo + i;
-        t[1] = (u64)res.status;              /* rounds 0 */
-        t[2] = 0;                            /* msgs, instrs 0 */
-        t[3] = res.dump_hash;
-        t[4] = res.final_hash;
-    }
+    if (terminals && k < term_cap) rs_put_terminal(rs_terminal_at(terminals, k), lo + i, res);
 }
 
 /* ---- per chunk ------------------------------------------------------------------------------ */
@@ -207,24 +190,9 @@ __global__ void __launch_bounds__(RT) reach_insert_kernel(const u64 *cfp, u64 n,
                                                           ReachCtr *ctr) {
     const u64 j = (u64)blockIdx.x * RT + threadIdx.x;
     if (j >= n) return;
-    const u64 fp = cfp[j];
-    u64 s = fp & (slots - 1);
-    u64 found = ~0ull;
-    for (u64 p = 0; p < slots; ++p, s = (s + 1) & (slots - 1)) {
-        u64 k = __hip_atomic_load(&table[2 * s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (k == 0) {
-            if (__hip_atomic_compare_exchange_strong(&table[2 * s], &k, fp, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                     __HIP_MEMORY_SCOPE_AGENT))
-                k = fp;
-        }
-        if (k == fp) {
-            __hip_atomic_fetch_max(&table[2 * s + 1], pending_of(j), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            found = s;
-            break;
-        }
-    }
+    const u64 found = visit_insert<__HIP_MEMORY_SCOPE_AGENT>(table, slots, cfp[j], j);
     cslot[j] = found;
-    if (found == ~0ull) __hip_atomic_fetch_add(&ctr->table_full, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (found == NO_SLOT) __hip_atomic_fetch_add(&ctr->table_full, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 __global__ void __launch_bounds__(RT) reach_resolve_kernel(const uint32_t *cand, u64 cs, uint32_t words, u64 n,
@@ -233,19 +201,9 @@ __global__ void __launch_bounds__(RT) reach_resolve_kernel(const uint32_t *cand,
     const u64 j = (u64)blockIdx.x * RT + threadIdx.x;
     if (j >= n) return;
     const u64 s = cslot[j];
-    uint32_t isnew = 0;
-    if (s != ~0ull) {
-        const u64 meta = table[2 * s + 1];
-        if (meta == pending_of(j)) {
-            isnew = 1;
-        } else if (!(meta & SETTLED)) {       /* the owner is candidate o of this chunk, o < j */
-            const u64 o = ~meta & ~SETTLED;
-            bool same = true;
-            for (uint32_t i = 0; i < words; ++i) same = same && cand[(size_t)i * cs + j] == cand[(size_t)i * cs + o];
-            if (!same) __hip_atomic_fetch_add(&ctr->coll, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    newflag[j] = isnew;
+    const int v = s != NO_SLOT ? visit_resolve(table[2 * s + 1], j, cand, (size_t)cs, words) : VISIT_SEEN;
+    if (v == VISIT_COLLISION) __hip_atomic_fetch_add(&ctr->coll, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    newflag[j] = v == VISIT_NEW ? 1u : 0u;
 }
 
 struct SettleArgs {
@@ -271,11 +229,8 @@ __global__ void __launch_bounds__(RT) reach_settle_kernel(const SettleArgs a) {
     if (j >= a.n || !a.newflag[j]) return;
     const u64 id = a.base + a.newoff[j];
     if (id >= a.max_states) return;           /* the level is dropped whole; the search ends */
-    a.table[2 * a.cslot[j] + 1] = SETTLED | id;
-    for (uint32_t i = 0; i < a.words; ++i) a.store[(size_t)i * a.cap + id] = a.cand[(size_t)i * a.cs + j];
-    if (a.parents) a.parents[id] = a.cpar[j];
-    if (a.masks) a.masks[id] = (uint8_t)a.cmask[j];
-    if (a.fps) a.fps[id] = a.cfp[j];
+    visit_settle(a.table, a.cslot[j], id, a.store, (size_t)a.cap, a.cand, (size_t)a.cs, j, a.words, a.parents, a.cpar, a.masks,
+                 a.cmask, a.fps, a.cfp);
 }
 
 /* the root into the store and the (zeroed) table */
@@ -333,25 +288,13 @@ struct SpanTimer {
     }
 };
 
-/* the end of a level, the same on both sides: does the search stop before expanding level
- * `depth` (which has `total` successors)? */
-bool stop_before_expand(const dsm_reach_opts *o, u64 depth, u64 total, uint64_t *flags) {
-    if (total == 0) return true;
-    if ((o->max_depth && depth >= o->max_depth) || depth + 1 >= DSM_REACH_MAX_LEVELS) {
-        *flags |= DSM_REACH_F_DEPTH;
-        return true;
-    }
-    return false;
-}
-
 template <int NP>
 int reach_device(dsm_ctx *c, const uint16_t *d_trace, const uint32_t *d_counts, const dsm_reach_opts *o, uint32_t L,
                  dsm_reach_info *info, uint32_t *d_parents, uint8_t *d_masks, u64 *d_fps, uint64_t *level_off,
                  u64 *d_terminals, u64 term_cap, hipStream_t st) {
     const u64 cap = o->max_states;
     const u64 chunk = o->chunk ? o->chunk : DEFAULT_CHUNK;
-    u64 slots = 64;
-    while (slots < 2 * (cap + chunk)) slots <<= 1;
+    const u64 slots = visit_slots(cap + chunk);
     const uint32_t stride = c->cfg.max_instr;
     const StepArgs step = {d_trace, d_counts, reinterpret_cast<const uint32_t *>(c->d_table), stride, L};
 
@@ -398,7 +341,7 @@ int reach_device(dsm_ctx *c, const uint16_t *d_trace, const uint32_t *d_counts, 
             hipLaunchKernelGGL(reach_term_kernel<NP>, dim3(grid_of(nf)), dim3(RT), 0, st, b_store.as<uint32_t>(), cap, lo,
                                nf, b_term.as<uint32_t>(), b_toff.as<u64>(), (u64)r.terminals, d_terminals, term_cap, ctr);
         r.terminals += nterm;
-        if (stop_before_expand(o, depth, total, &r.flags)) break;
+        if (rs_stop_before_expand(o->max_depth, depth, total, &r.flags)) break;
         r.transitions += total;
         u64 fresh = states;
         for (u64 c0 = 0; c0 < total && fresh <= cap; c0 += chunk) {
@@ -444,15 +387,9 @@ int reach_device(dsm_ctx *c, const uint16_t *d_trace, const uint32_t *d_counts, 
     HIPCK(hipStreamSynchronize(st));
     HIPCK(hipGetLastError());
     if (h.table_full) return DSM_E_STATE;     /* cannot happen: slots >= 2 * (max_states + chunk) */
-    r.states = states;
-    r.levels = loff.size();
-    loff.push_back(states);
     r.max_fill = h.max_fill;
     for (int k = 0; k < 5; ++k) r.by_status[k] = h.by_status[k];
-    r.fp_collisions = h.coll;
-    if (h.coll) r.flags |= DSM_REACH_F_COLLISION;
-    if (info) *info = r;
-    if (level_off) memcpy(level_off, loff.data(), loff.size() * sizeof(uint64_t));
+    rs_close(&r, loff.data(), loff.size(), states, h.coll, info, level_off);
     return DSM_OK;
 }
 
@@ -480,7 +417,7 @@ int reach_host(const uint16_t *trace, const uint32_t *counts, uint32_t stride, c
         if (masks) masks[0] = 0;
         if (fps) fps[0] = fp;
     }
-    u64 states = 1, lo = 0, hi = 1;
+    u64 states = 1, lo = 0, hi = 1, collisions = 0;
     for (;;) {
         const u64 nf = hi - lo, depth = loff.size();
         loff.push_back(lo);
@@ -489,11 +426,11 @@ int reach_host(const uint16_t *trace, const uint32_t *counts, uint32_t stride, c
         u64 total = 0;
         for (u64 i = 0; i < nf; ++i) {
             const StMem m = {&S[(lo + i) * W], 1};
-            const uint32_t a = rs_enabled<NP>(m, counts, stride);
-            const uint64_t f = rs_max_fill<NP>(m);
-            if (f > r.max_fill) r.max_fill = f;
-            dsm_sys_result res;
-            if (rs_terminal<NP>(m, a, &res)) {
+            const RsItem it = rs_level_item<NP>(m, counts, stride);
+            if (it.fill > r.max_fill) r.max_fill = it.fill;
+            if (it.terminal) {
+                dsm_sys_result res;
+                (void)rs_terminal<NP>(m, it.A, &res);
                 r.by_status[res.status & 7u]++;
                 if (terminals && r.terminals < term_cap) {
                     terminals[r.terminals].state = lo + i;
@@ -501,15 +438,15 @@ int reach_host(const uint16_t *trace, const uint32_t *counts, uint32_t stride, c
                 }
                 r.terminals++;
             } else {
-                A[i] = a;
-                total += (1u << __builtin_popcount(a)) - 1u;
+                A[i] = it.A;
+                total += it.cnt;
             }
         }
-        if (stop_before_expand(o, depth, total, &r.flags)) break;
+        if (rs_stop_before_expand(o->max_depth, depth, total, &r.flags)) break;
         r.transitions += total;
         u64 fresh = states;
         for (u64 i = 0; i < nf && fresh <= cap; ++i) {
-            const uint32_t cnt = A[i] ? (1u << __builtin_popcount(A[i])) - 1u : 0u;
+            const uint32_t cnt = rs_succ_count(A[i]);     /* 0 for a terminal state: its A stayed 0 */
             for (uint32_t j = 1; j <= cnt && fresh <= cap; ++j) {
                 const uint32_t mask = rs_deposit(j, A[i]);
                 memcpy(tmp, &S[(lo + i) * W], W * 4);
@@ -518,7 +455,7 @@ int reach_host(const uint16_t *trace, const uint32_t *counts, uint32_t stride, c
                 const uint64_t fp = rs_fingerprint<NP>(m);
                 const auto it = seen.find(fp);
                 if (it != seen.end()) {
-                    if (it->second < cap && memcmp(tmp, &S[it->second * W], W * 4)) r.fp_collisions++;
+                    if (it->second < cap && !visit_same(tmp, &S[it->second * W], 1, W)) collisions++;
                     continue;
                 }
                 seen.emplace(fp, fresh);
@@ -535,12 +472,7 @@ int reach_host(const uint16_t *trace, const uint32_t *counts, uint32_t stride, c
         if (fresh == states) break;
         lo = states; hi = fresh; states = fresh;
     }
-    r.states = states;
-    r.levels = loff.size();
-    loff.push_back(states);
-    if (r.fp_collisions) r.flags |= DSM_REACH_F_COLLISION;
-    if (info) *info = r;
-    if (level_off) memcpy(level_off, loff.data(), loff.size() * sizeof(uint64_t));
+    rs_close(&r, loff.data(), loff.size(), states, collisions, info, level_off);
     return DSM_OK;
 }
 
@@ -599,6 +531,12 @@ extern "C" int dsm_debug_exscan_device(dsm_ctx *c, const uint32_t *d_in, uint64_
     return DSM_OK;
 }
 
+/* test only (dsm_internal.h): the resolve rule of both searches, on the host */
+extern "C" int dsm_debug_visit_resolve(uint64_t meta, uint64_t j, const uint32_t *cand, uint64_t cs, uint32_t words) {
+    if (!cand || j >= cs || (!(meta & SETTLED) && owner_of(meta) >= cs)) return DSM_E_INVAL;
+    return visit_resolve(meta, j, cand, (size_t)cs, words);
+}
+
 extern "C" int dsm_debug_reach_times(double *ms, uint64_t *chunks) {
     if (!ms || !chunks) return DSM_E_INVAL;
     for (int k = 0; k < T_CLASSES; ++k) ms[k] = g_reach_ms[k];
@@ -613,15 +551,10 @@ extern "C" int dsm_reach_device(dsm_ctx *c, const uint16_t *d_trace, const uint3
     if (!c || !d_trace || !d_counts || !opts_ok(opts, &L)) return DSM_E_INVAL;
     if (((uintptr_t)d_fps & 7u) || ((uintptr_t)d_terminals & 7u) || ((uintptr_t)d_parents & 3u)) return DSM_E_INVAL;
     HIPCK(hipSetDevice(c->device));
-    try {
-        if (c->cfg.np == 4)
-            return reach_device<4>(c, d_trace, d_counts, opts, L, info, d_parents, d_masks, (u64 *)d_fps, level_off,
-                                   (u64 *)d_terminals, term_cap, (hipStream_t)stream);
-        return reach_device<8>(c, d_trace, d_counts, opts, L, info, d_parents, d_masks, (u64 *)d_fps, level_off,
-                               (u64 *)d_terminals, term_cap, (hipStream_t)stream);
-    } catch (const std::bad_alloc &) {
-        return DSM_E_NOMEM;
-    }
+    return by_np(c->cfg.np, [&](auto n) {
+        return reach_device<decltype(n)::value>(c, d_trace, d_counts, opts, L, info, d_parents, d_masks, (u64 *)d_fps, level_off,
+                                                (u64 *)d_terminals, term_cap, (hipStream_t)stream);
+    });
 }
 
 extern "C" int dsm_reach(int np, const uint16_t *trace, const uint32_t *counts, uint32_t stride,
@@ -630,12 +563,10 @@ extern "C" int dsm_reach(int np, const uint16_t *trace, const uint32_t *counts, 
     uint32_t L;
     if ((np != 4 && np != 8) || !trace || !counts || stride == 0 || stride > DSM_MAX_INSTR || !opts_ok(opts, &L))
         return DSM_E_INVAL;
-    try {
-        if (np == 4) return reach_host<4>(trace, counts, stride, opts, L, info, parents, masks, fps, level_off, terminals, term_cap);
-        return reach_host<8>(trace, counts, stride, opts, L, info, parents, masks, fps, level_off, terminals, term_cap);
-    } catch (const std::bad_alloc &) {
-        return DSM_E_NOMEM;
-    }
+    return by_np(np, [&](auto n) {
+        return reach_host<decltype(n)::value>(trace, counts, stride, opts, L, info, parents, masks, fps, level_off, terminals,
+                                              term_cap);
+    });
 }
 
 extern "C" int dsm_reach_path(const uint32_t *parents, const uint8_t *masks, uint64_t id, uint8_t *out_masks,
@@ -658,6 +589,7 @@ extern "C" int dsm_reach_replay(int np, const uint16_t *trace, const uint32_t *c
         (n && !masks))
         return DSM_E_INVAL;
     const uint32_t L = inbox_limit ? inbox_limit : RS_RING;
-    if (np == 4) return replay_host<4>(trace, counts, stride, L, masks, n, dump, final_state, res);
-    return replay_host<8>(trace, counts, stride, L, masks, n, dump, final_state, res);
+    return by_np(np, [&](auto k) {
+        return replay_host<decltype(k)::value>(trace, counts, stride, L, masks, n, dump, final_state, res);
+    });
 }

@@ -13,19 +13,18 @@
  *                             to its end, writes info[s] and the system's rows of the outputs, and
  *                             claims again until the ids run out.  No workgroup waits for another.
  *
- * Per level, in the workgroup (the algorithm and the numbering are dsm_reach.hip's):
- *   count       a lane per state of the level, a tile of RT at a time: enabled set, successor
- *               count, terminal flag, deepest inbox; one workgroup scan of the tile carries both
- *               the successor offsets (low word) and the terminal ranks (high word), so the
- *               terminals are written in id order in the same pass
+ * Per level, in the workgroup -- the search is dsm_reach.hip's: a level's rules are the same
+ * functions of dsm_reach.h, the visited table's protocol the same of dsm_reach_dev.h ("the visited
+ * table", with the argument for it), so the numbering is the same:
+ *   count       a lane per state of the level, a tile of RT at a time (rs_level_item); one workgroup
+ *               scan of the tile carries both the successor offsets (low word) and the terminal
+ *               ranks (high word), so the terminals are written in id order in the same pass
  *   per chunk of the level's candidates, in order:
  *   expand      a lane per candidate: dsm_reach_dev.h's successor (rs_round in place in the chunk
- *               buffer, the micro-op table in LDS), the fingerprint, and the insert into the
- *               visited table (compare-and-swap on the key, max on meta with ~candidate)
- *   resolve     a candidate is new exactly when it owns its slot; a non-owner whose owner is in
- *               the same chunk compares the two full states (the collision count)
+ *               buffer, the micro-op table in LDS), the fingerprint, visit_insert
+ *   resolve     visit_resolve; a lane counts its collisions
  *   settle      a tile of RT candidates at a time: a workgroup scan of the new-flags gives the
- *               ids; owners write meta = settled | id and move to the store with parent and mask
+ *               ids; visit_settle, with parent and mask
  * Everything between two barriers touches the slab of this workgroup alone, so the table's atomics
  * are workgroup scope and __syncthreads orders the phases.
  *
@@ -46,12 +45,10 @@
 
 namespace {
 
-constexpr u64 SETTLED = 1ull << 63;
 constexpr uint32_t BATCH_DEFAULT_CHUNK = 1024;   /* measured: DESIGN.md, "Reach batch" */
-constexpr uint32_t NO_SLOT = 0xFFFFFFFFu;
+constexpr uint32_t NO_SLOT32 = (uint32_t)NO_SLOT;   /* a slab's table has fewer than 2^32 slots: cslot keeps 32 bits */
 constexpr int WAVE = 64;
-
-DSM_HD u64 pending_of(u64 j) { return ~j & ~SETTLED; }
+constexpr int WG = __HIP_MEMORY_SCOPE_WORKGROUP;    /* the table's atomics: a slab is one workgroup's */
 
 /* one system's slab: byte offsets of its arrays (each a multiple of 16) */
 struct Slab {
@@ -77,8 +74,7 @@ int batch_opts_ok(int np, const dsm_reach_opts *o, uint32_t *L) {
 Slab slab_of(int np, const dsm_reach_opts *o) {
     const u64 cap = o->max_states, chunk = o->chunk ? o->chunk : BATCH_DEFAULT_CHUNK;
     Slab s;
-    s.slots = 64;
-    while (s.slots < 2 * (cap + chunk)) s.slots <<= 1;
+    s.slots = visit_slots(cap + chunk);
     u64 at = 0;
     s.o_table = at; at = up16(at + s.slots * 16);
     s.o_offs = at;  at = up16(at + (cap + 1) * 8);
@@ -109,7 +105,6 @@ struct BatchArgs {
 
 constexpr int INFO_WORDS = 14;
 static_assert(sizeof(dsm_reach_info) == INFO_WORDS * 8, "the kernel writes dsm_reach_info as words");
-static_assert(sizeof(dsm_reach_terminal) == 40, "the kernel writes dsm_reach_terminal as five words");
 
 /* exclusive scan of one value per lane over the workgroup; *total = the sum.  Every lane calls it. */
 __device__ __forceinline__ u64 wg_exscan(u64 v, u64 *s_w, u64 *total) {
@@ -132,16 +127,6 @@ __device__ __forceinline__ u64 wg_exscan(u64 v, u64 *s_w, u64 *total) {
     }
     *total = tot;
     return before + x - v;
-}
-
-/* dsm_reach.hip's stop_before_expand */
-__device__ __forceinline__ bool stop_level(uint32_t max_depth, u64 depth, u64 total, u64 *flags) {
-    if (total == 0) return true;
-    if ((max_depth && depth >= max_depth) || depth + 1 >= DSM_REACH_MAX_LEVELS) {
-        *flags |= DSM_REACH_F_DEPTH;
-        return true;
-    }
-    return false;
 }
 
 template <int NP>
@@ -179,7 +164,7 @@ __global__ void __launch_bounds__(RT) reach_batch_kernel(const BatchArgs a) {
         StepArgs step = a.step;
         step.trace += (size_t)sys * NP * step.stride;
         step.counts += (size_t)sys * NP;
-        u64 *terminals = a.terminals ? a.terminals + (size_t)sys * a.term_cap * 5 : nullptr;
+        u64 *terminals = a.terminals ? rs_terminal_at(a.terminals, sys * a.term_cap) : nullptr;
         uint32_t *parents = a.parents ? a.parents + (size_t)sys * cap : nullptr;
         uint8_t *masks = a.masks ? a.masks + (size_t)sys * cap : nullptr;
 
@@ -200,7 +185,8 @@ __global__ void __launch_bounds__(RT) reach_batch_kernel(const BatchArgs a) {
         }
         __syncthreads();
 
-        u64 states = 1, lo = 0, hi = 1, depth = 0, transitions = 0, nterm = 0, max_frontier = 0, flags = 0;
+        u64 states = 1, lo = 0, hi = 1, depth = 0, transitions = 0, nterm = 0, max_frontier = 0;
+        uint64_t flags = 0;
         uint32_t fillmax = 0, coll = 0;
         for (;;) {
             const u64 nf = hi - lo;
@@ -214,12 +200,11 @@ __global__ void __launch_bounds__(RT) reach_batch_kernel(const BatchArgs a) {
                 uint32_t cnt = 0;
                 bool term = false;
                 if (valid) {
-                    const uint32_t en = rs_enabled<NP>(m, step.counts, step.stride);
-                    term = rs_terminal<NP>(m, en, nullptr);
-                    A[i] = (uint8_t)en;
-                    cnt = term ? 0u : (1u << __builtin_popcount(en)) - 1u;
-                    const uint32_t f = rs_max_fill<NP>(m);
-                    fillmax = f > fillmax ? f : fillmax;
+                    const RsItem it = rs_level_item<NP>(m, step.counts, step.stride);
+                    term = it.terminal;
+                    A[i] = (uint8_t)it.A;
+                    cnt = it.cnt;
+                    fillmax = it.fill > fillmax ? it.fill : fillmax;
                 }
                 u64 tile;
                 const u64 ex = wg_exscan((u64)cnt | ((u64)(term ? 1u : 0u) << 32), s_w, &tile);
@@ -229,21 +214,14 @@ __global__ void __launch_bounds__(RT) reach_batch_kernel(const BatchArgs a) {
                     (void)rs_terminal<NP>(m, 0u, &res);
                     atomicAdd(&s_by[res.status & 7u], 1u);
                     const u64 k = nterm + (ex >> 32);
-                    if (terminals && k < a.term_cap) {
-                        u64 *o = terminals + 5 * k;
-                        o[0] = lo + i;
-                        o[1] = (u64)res.status;          /* rounds 0 */
-                        o[2] = 0;                        /* msgs, instrs 0 */
-                        o[3] = res.dump_hash;
-                        o[4] = res.final_hash;
-                    }
+                    if (terminals && k < a.term_cap) rs_put_terminal(rs_terminal_at(terminals, k), lo + i, res);
                 }
                 total += tile & 0xFFFFFFFFull;
                 nterm += tile >> 32;
             }
             if (t == 0) offs[nf] = total;
             __syncthreads();
-            if (stop_level(a.max_depth, depth, total, &flags)) break;
+            if (rs_stop_before_expand(a.max_depth, depth, total, &flags)) break;
             transitions += total;
 
             u64 fresh = states;
@@ -258,42 +236,17 @@ __global__ void __launch_bounds__(RT) reach_batch_kernel(const BatchArgs a) {
                     const u64 fp = rs_fingerprint<NP>(m);
                     cpar[j] = (uint32_t)(lo + p);
                     cmask[j] = (uint8_t)mask;
-                    u64 s = fp & (slots - 1);
-                    uint32_t found = NO_SLOT;
-                    for (u64 q = 0; q < slots; ++q, s = (s + 1) & (slots - 1)) {
-                        u64 k = __hip_atomic_load(&table[2 * s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        if (k == 0) {
-                            if (__hip_atomic_compare_exchange_strong(&table[2 * s], &k, fp, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                                     __HIP_MEMORY_SCOPE_WORKGROUP))
-                                k = fp;
-                        }
-                        if (k == fp) {
-                            __hip_atomic_fetch_max(&table[2 * s + 1], pending_of(j), __ATOMIC_RELAXED,
-                                                   __HIP_MEMORY_SCOPE_WORKGROUP);
-                            found = (uint32_t)s;
-                            break;
-                        }
-                    }
-                    cslot[j] = found;         /* NO_SLOT cannot happen: slots >= 2 (max_states + chunk) */
+                    cslot[j] = (uint32_t)visit_insert<WG>(table, slots, fp, j);   /* NO_SLOT cannot happen: slots >= 2 (max_states + chunk) */
                 }
                 __syncthreads();
                 /* resolve */
                 for (u64 j = t; j < n; j += RT) {
                     const uint32_t s = cslot[j];
-                    uint8_t isnew = 0;
-                    if (s != NO_SLOT) {
-                        const u64 meta = __hip_atomic_load(&table[2 * (u64)s + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        if (meta == pending_of(j)) {
-                            isnew = 1;
-                        } else if (!(meta & SETTLED)) {   /* the owner is candidate o of this chunk, o < j */
-                            const u64 o = ~meta & ~SETTLED;
-                            bool same = true;
-                            for (uint32_t i = 0; i < RS_WORDS(NP); ++i)
-                                same = same && cand[(size_t)i * chunk + j] == cand[(size_t)i * chunk + o];
-                            if (!same) ++coll;
-                        }
-                    }
-                    newflag[j] = isnew;
+                    const int v = s == NO_SLOT32 ? VISIT_SEEN
+                                                 : visit_resolve(__hip_atomic_load(&table[2 * (u64)s + 1], __ATOMIC_RELAXED, WG), j, cand,
+                                                                 (size_t)chunk, RS_WORDS(NP));
+                    if (v == VISIT_COLLISION) ++coll;
+                    newflag[j] = v == VISIT_NEW ? 1 : 0;
                 }
                 __syncthreads();
                 /* settle, in id order */
@@ -302,13 +255,9 @@ __global__ void __launch_bounds__(RT) reach_batch_kernel(const BatchArgs a) {
                     const uint32_t f = j < n ? newflag[j] : 0u;
                     u64 tile;
                     const u64 id = fresh + wg_exscan(f, s_w, &tile);
-                    if (f && id < cap) {      /* past max_states the level is dropped whole */
-                        __hip_atomic_store(&table[2 * (u64)cslot[j] + 1], SETTLED | id, __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_WORKGROUP);
-                        for (uint32_t i = 0; i < RS_WORDS(NP); ++i) store[(size_t)i * cap + id] = cand[(size_t)i * chunk + j];
-                        if (parents) parents[id] = cpar[j];
-                        if (masks) masks[id] = cmask[j];
-                    }
+                    if (f && id < cap)        /* past max_states the level is dropped whole */
+                        visit_settle(table, cslot[j], id, store, (size_t)cap, cand, (size_t)chunk, j, RS_WORDS(NP), parents, cpar,
+                                     masks, cmask, (u64 *)nullptr, (const u64 *)nullptr);
                     fresh += tile;
                 }
                 __syncthreads();

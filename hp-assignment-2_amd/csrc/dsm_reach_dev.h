@@ -1,11 +1,15 @@
 /*
- * dsm_reach_dev.h -- the device plumbing the exhaustive exploration (dsm_reach.hip) and the outcome
- * distribution (dsm_dist.hip) share: workgroup size and chunk limits, a device buffer, the check
- * of dsm_reach_opts, and "successor g of a level" over dsm_reach.h's rs_round.  Internal to those
- * two units.
+ * dsm_reach_dev.h -- the device plumbing of the reach family: workgroup size and chunk limits, a
+ * device buffer, the check of dsm_reach_opts, "successor g of a level" over dsm_reach.h's rs_round,
+ * the visited table's protocol (its one definition and the argument for it), and the np dispatch
+ * of the entry points.  Internal to the five units of the family: dsm_reach.hip, dsm_reach_batch.hip,
+ * dsm_dist.hip, dsm_fate.hip and dsm_raudit.hip (the last three through dsm_dist_dev.h).
  */
 #ifndef DSM_REACH_DEV_H
 #define DSM_REACH_DEV_H
+
+#include <new>
+#include <type_traits>
 
 #include "dsm_internal.h"
 #include "dsm_reach.h"
@@ -89,6 +93,103 @@ __device__ __forceinline__ StMem successor(const uint32_t *store, size_t ss, u64
     *parent = lo;
     *mask = rs_deposit((uint32_t)(g - offs[lo]) + 1u, A[lo]);
     return step_from<NP>(store + lo, ss, dst, ds, *mask, s_tab, a);
+}
+
+/* ---- the visited table ------------------------------------------------------------------------
+ * Open addressing over `slots` (a power of two) pairs {key, meta} of 64-bit words, zeroed before
+ * the search.  A key is a fingerprint (never 0: an empty slot).  A meta is SETTLED | id -- the key
+ * is numbered state id's -- or pending_of(j) -- candidate j of the chunk in hand claims it: ~j
+ * with the top bit clear.  A chunk's candidates pass three phases, each finished (a kernel boundary
+ * in dsm_reach.hip, a barrier in dsm_reach_batch.hip) before the next begins:
+ *   insert    visit_insert: probe from fp & (slots - 1); compare-and-swap the key into the first
+ *             empty slot (a loser that meets its own fingerprint there joins the winner); then an
+ *             UNCONDITIONAL max on the slot's meta with pending_of(j)
+ *   resolve   visit_resolve: reads the metas, writes nothing
+ *   settle    visit_settle: the new candidates overwrite their slot's meta with SETTLED | id
+ * Why a slot's owner is "the lowest candidate of the chunk, or an earlier state": a settled meta
+ * has the top bit and a pending one has not, so a settled meta compares above every pending value
+ * and no max moves it; pending_of falls as j rises, so of the candidates that share a fingerprint
+ * the max keeps the lowest; a fresh slot's 0 is below them all; and the order in which the atomics
+ * land does not show.  So candidate j is new exactly when it reads pending_of(j) back.  The new
+ * candidates settle before the next chunk inserts, so no pending value outlives its chunk -- but
+ * where an id passes max_states: that level is dropped whole and the table is not read again.  It
+ * holds max_states settled keys and a chunk of pending ones at most, half of
+ * visit_slots(max_states + chunk), so a probe always ends.  A candidate whose owner is a candidate
+ * of the same chunk has the owner's rows beside its own: the two states are compared in full, and
+ * a difference is a fingerprint collision (counted, the candidate dropped as seen, the result
+ * flagged inexact).  Against an earlier state nothing is compared. */
+constexpr u64 SETTLED = 1ull << 63;
+constexpr u64 NO_SLOT = ~0ull;               /* visit_insert found no slot; a caller may keep its low 32 bits */
+DSM_HD u64 pending_of(u64 j) { return ~j & ~SETTLED; }
+DSM_HD u64 owner_of(u64 meta) { return ~meta & ~SETTLED; }   /* of a pending meta: the candidate */
+
+/* the slots of a table for `need` keys: 64, doubled until >= 2 * need */
+static inline u64 visit_slots(u64 need) {
+    u64 slots = 64;
+    while (slots < 2 * need) slots <<= 1;
+    return slots;
+}
+
+/* candidate j's fingerprint into the table -> its slot, or NO_SLOT where the table is full.
+ * SCOPE: __HIP_MEMORY_SCOPE_AGENT, or _WORKGROUP where one workgroup alone uses the table. */
+template <int SCOPE>
+__device__ __forceinline__ u64 visit_insert(u64 *table, u64 slots, u64 fp, u64 j) {
+    u64 s = fp & (slots - 1);
+    u64 found = NO_SLOT;
+    for (u64 p = 0; p < slots; ++p, s = (s + 1) & (slots - 1)) {
+        u64 k = __hip_atomic_load(&table[2 * s], __ATOMIC_RELAXED, SCOPE);
+        if (k == 0) {
+            if (__hip_atomic_compare_exchange_strong(&table[2 * s], &k, fp, __ATOMIC_RELAXED, __ATOMIC_RELAXED, SCOPE)) k = fp;
+        }
+        if (k == fp) {
+            __hip_atomic_fetch_max(&table[2 * s + 1], pending_of(j), __ATOMIC_RELAXED, SCOPE);
+            found = s;
+            break;
+        }
+    }
+    return found;
+}
+
+/* are the `words`-word states at a and b, rows `stride` words apart, the same? */
+DSM_HD bool visit_same(const uint32_t *a, const uint32_t *b, size_t stride, uint32_t words) {
+    bool same = true;
+    for (uint32_t i = 0; i < words; ++i) same = same && a[(size_t)i * stride] == b[(size_t)i * stride];
+    return same;
+}
+
+/* What is candidate j, whose slot holds meta after the insert phase?  cand: the chunk's candidates,
+ * word i of candidate j at cand[i * cs + j]; a pending meta that is not j's names a lower candidate. */
+enum { VISIT_NEW = 0, VISIT_SEEN, VISIT_COLLISION };
+DSM_HD int visit_resolve(u64 meta, u64 j, const uint32_t *cand, size_t cs, uint32_t words) {
+    if (meta == pending_of(j)) return VISIT_NEW;
+    if (meta & SETTLED) return VISIT_SEEN;
+    return visit_same(cand + j, cand + owner_of(meta), cs, words) ? VISIT_SEEN : VISIT_COLLISION;
+}
+
+/* New candidate j becomes state id: its slot's meta (a plain store: the phase boundary orders it
+ * before the next probe), its rows into the store (word i of state id at store[i * cap + id]), and
+ * its parent, mask and fingerprint where the caller has an array for them (each may be null). */
+template <typename TM>
+__device__ __forceinline__ void visit_settle(u64 *table, u64 slot, u64 id, uint32_t *store, size_t cap, const uint32_t *cand,
+                                             size_t cs, u64 j, uint32_t words, uint32_t *parents, const uint32_t *cpar,
+                                             uint8_t *masks, const TM *cmask, u64 *fps, const u64 *cfp) {
+    table[2 * slot + 1] = SETTLED | id;
+    for (uint32_t i = 0; i < words; ++i) store[(size_t)i * cap + id] = cand[(size_t)i * cs + j];
+    if (parents) parents[id] = cpar[j];
+    if (masks) masks[id] = (uint8_t)cmask[j];
+    if (fps) fps[id] = cfp[j];
+}
+
+/* ---- entry points -------------------------------------------------------------------------------
+ * f(std::integral_constant<int, NP>) -> int for np (4 or 8: the entry has checked it), a failed
+ * allocation of the host's as DSM_E_NOMEM */
+template <typename F>
+static inline int by_np(int np, F &&f) {
+    try {
+        return np == 4 ? f(std::integral_constant<int, 4>{}) : f(std::integral_constant<int, 8>{});
+    } catch (const std::bad_alloc &) {
+        return DSM_E_NOMEM;
+    }
 }
 
 #endif

@@ -211,6 +211,7 @@ def lib():
             # test-only (csrc/dsm_internal.h, not in include/dsm.h)
             "dsm_debug_raudit_times": (i32, [vp, ctypes.POINTER(u64)]),
             "dsm_debug_raudit_lane": (i32, [i32, vp, u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]),
+            "dsm_debug_visit_resolve": (i32, [u64, u64, vp, u64, u32]),
             "dsm_debug_fate_times": (i32, [vp, vp]),
             "dsm_debug_dist_edges": (i32, [i32, vp, vp, u32, ctypes.POINTER(ReachOpts), vp, vp, vp, u64,
                                            ctypes.POINTER(u64)]),

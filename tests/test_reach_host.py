@@ -9,7 +9,10 @@ References, none of them the code under test:
   - the oracle under 256 seeded schedules at three thresholds: every run is a path of the graph, so
     every key it produces is in the search's census (closure);
   - tests/golden/explore/sample.npy: the 8 keys of the stored exploration are exactly the search's;
-  - orc_run_packed: the path that always takes every enabled node is the lock-step run."""
+  - orc_run_packed: the path that always takes every enabled node is the lock-step run.
+Section 8 holds the visited table's resolve rule (dsm_reach_dev.h visit_resolve, which both device
+searches call) to its definition on crafted chunks: no search we have makes two fingerprints collide,
+so nothing else runs its colliding branch."""
 import os
 import subprocess
 
@@ -253,6 +256,71 @@ def test_invariants(name):
     lv = r["level_off"].astype(np.int64)
     assert lv[0] == 0 and lv[1] == 1 and lv[-1] == i["states"] and (np.diff(lv) > 0).all()
     assert i["max_frontier"] == np.diff(lv).max()
+
+
+# -- 8. the resolve rule of the visited table -------------------------------------------------------
+SETTLED = 1 << 63
+WORDS4 = 33 * 4 + 4                              # RS_WORDS(4)
+NEW, SEEN, COLLISION = 0, 1, 2
+
+
+def pending_of(j):
+    return ~j & (SETTLED - 1)
+
+
+def chunk_of(differ_at=None):
+    """Three candidates in a chunk buffer of stride 5, word i of candidate j at [i, j]: candidates 0
+    and 1 are one state, candidate 2 the same state or, with differ_at, one that differs in that
+    word alone.  The two columns behind the candidates, and every row, hold other values, so a
+    row / column mix-up compares different words."""
+    cand = np.random.default_rng(5).integers(0, 1 << 32, (WORDS4, 5), dtype=np.uint64).astype(np.uint32)
+    cand[:, 1] = cand[:, 0]
+    cand[:, 2] = cand[:, 0]
+    if differ_at is not None:
+        cand[differ_at, 2] ^= 1
+    assert len(np.unique(cand[:, 0])) > WORDS4 // 2 and not np.array_equal(cand[:, 3], cand[:, 0])
+    return np.ascontiguousarray(cand)
+
+
+def resolve(meta, j, cand):
+    return pydsm.lib().dsm_debug_visit_resolve(meta, j, pydsm._ptr(cand), cand.shape[1], cand.shape[0])
+
+
+def test_visit_resolve_new_is_the_own_pending_value():
+    cand = chunk_of(differ_at=0)
+    for j in range(3):
+        assert resolve(pending_of(j), j, cand) == NEW
+
+
+def test_visit_resolve_settled_is_seen_whatever_the_rows():
+    cand = chunk_of(differ_at=0)
+    for j in range(3):
+        for state in (0, 2, 12345, SETTLED - 1):
+            assert resolve(SETTLED | state, j, cand) == SEEN
+
+
+def test_visit_resolve_equal_lower_candidate_is_seen():
+    cand = chunk_of()
+    assert resolve(pending_of(0), 1, cand) == SEEN
+    assert resolve(pending_of(0), 2, cand) == SEEN
+    assert resolve(pending_of(1), 2, cand) == SEEN
+
+
+@pytest.mark.parametrize("word", (WORDS4 - 1, 0))
+def test_visit_resolve_one_differing_word_is_a_collision(word):
+    cand = chunk_of(differ_at=word)
+    assert resolve(pending_of(0), 2, cand) == COLLISION
+    assert resolve(pending_of(1), 2, cand) == COLLISION
+    assert resolve(pending_of(0), 1, cand) == SEEN                         # candidates 0 and 1 still agree
+    # over the words before the differing one the states agree: the compare stops at `words`
+    assert pydsm.lib().dsm_debug_visit_resolve(pending_of(0), 2, pydsm._ptr(cand), 5, word) == SEEN
+
+
+def test_visit_resolve_refuses_candidates_outside_the_chunk():
+    cand = chunk_of()
+    assert resolve(pending_of(0), 5, cand) == pydsm.E_INVAL
+    assert resolve(pending_of(5), 1, cand) == pydsm.E_INVAL
+    assert pydsm.lib().dsm_debug_visit_resolve(pending_of(0), 1, None, 5, WORDS4) == pydsm.E_INVAL
 
 
 def test_census_insert_is_the_update_of_census_results():
