@@ -145,6 +145,18 @@
  *                    terminal states), then
  *                        screened N tests: D can deadlock, X exhaustive
  *                    Exits 2 when D > 0, else 3 when any search was truncated, else 0.
+ *   --reach-batch-audit
+ *                    --reach-batch with the coherence audit of every reachable state of every test
+ *                    (one dsm_reach_batch_audit_device call in place of the plain one); the same
+ *                    options, and the same usage errors: --audit beside either flag stays one, as
+ *                    it was beside --reach-batch.  After each directory's line:
+ *                        <dir>: audit all V/N quiescent V/N terminal V/N completed V/N
+ *                    (V violating of N states per set) and, when the completed set violates,
+ *                        <dir>: can end incoherent: C of K completed states, first F depth D
+ *                    The summary becomes
+ *                        screened N tests: D can deadlock, I can end incoherent, X exhaustive
+ *                    and the exit code 2 when D > 0 or I > 0, else 3 when any search was truncated,
+ *                    else 0.
  */
 #include <errno.h>
 #include <stdio.h>
@@ -165,7 +177,7 @@ static void usage(const char *argv0) {
                     "          [--fate completed|deadlocked|ring_overflow|assert_failed|round_limit|0xKEY]\n"
                     "          [--explore-dir DIR]\n"
                     "          [--explore-kind dumps|final] [--check DIR]] <test_directory>\n"
-                    "       %s [--np 4|8] [--max-instr N] [--device D] [--quiet] --reach-batch [--reach-states N]\n"
+                    "       %s [--np 4|8] [--max-instr N] [--device D] [--quiet] --reach-batch | --reach-batch-audit [--reach-states N]\n"
                     "          [--reach-depth D] [--reach-inbox L] [--explore-kind dumps|final] <test_directory>...\n",
             argv0, argv0);
 }
@@ -816,10 +828,10 @@ static int append_core_file(const char *dir, int n, char **text, uint64_t *len) 
 }
 
 /* --reach-batch: the tests of dirs read with one dsm_parse_traces call and searched with one
- * dsm_reach_batch_device call; a line per test and the screen's summary.  Returns the process
- * exit code. */
+ * dsm_reach_batch_device call (with audit: one dsm_reach_batch_audit_device call); a line per test
+ * (with audit: its audit lines) and the screen's summary.  Returns the process exit code. */
 static int reach_batch(int np, uint32_t max_instr, int device, char **dirs, int n_dirs,
-                       unsigned long long max_states, uint32_t max_depth, uint32_t inbox, int kind) {
+                       unsigned long long max_states, uint32_t max_depth, uint32_t inbox, int kind, int audit) {
     const uint32_t stride = (max_instr + 7u) & ~7u;
     const uint64_t n_files = (uint64_t)n_dirs * (uint64_t)np;
     const uint64_t term_cap = max_states < (DSM_CENSUS_MAX_CAP / 2) ? max_states : (DSM_CENSUS_MAX_CAP / 2);
@@ -831,13 +843,14 @@ static int reach_batch(int np, uint32_t max_instr, int device, char **dirs, int 
     int32_t *pst = (int32_t *)calloc((size_t)n_files, sizeof(int32_t));
     dsm_reach_info *info = (dsm_reach_info *)calloc((size_t)n_dirs, sizeof *info), *d_info = NULL;
     dsm_reach_terminal *term = (dsm_reach_terminal *)malloc((size_t)term_cap * sizeof *term), *d_term = NULL;
+    dsm_reach_audit_info *ainfo = audit ? (dsm_reach_audit_info *)calloc((size_t)n_dirs, sizeof *ainfo) : NULL, *d_ainfo = NULL;
     uint64_t *cen = NULL;
     dsm_ctx *ctx = NULL;
     dsm_reach_opts opts;
     dsm_config cfg;
     int rc = DSM_OK, code = EXIT_FAILURE;
     const char *what = "out of memory";
-    if (!off || !traces || !counts || !pst || !info || !term) goto fail;
+    if (!off || !traces || !counts || !pst || !info || !term || (audit && !ainfo)) goto fail;
     for (uint64_t f = 0; f < n_files; ++f) {
         uint64_t len = off[f];
         if (append_core_file(dirs[f / (uint64_t)np], (int)(f % (uint64_t)np), &text, &len)) goto fail;
@@ -866,17 +879,25 @@ static int reach_batch(int np, uint32_t max_instr, int device, char **dirs, int 
     if (hipMalloc((void **)&d_tr, tr_bytes) != hipSuccess || hipMalloc((void **)&d_cn, cn_bytes) != hipSuccess ||
         hipMalloc((void **)&d_info, (size_t)n_dirs * sizeof *info) != hipSuccess ||
         hipMalloc((void **)&d_term, (size_t)n_dirs * (size_t)term_cap * sizeof *term) != hipSuccess ||
+        (audit && hipMalloc((void **)&d_ainfo, (size_t)n_dirs * sizeof *ainfo) != hipSuccess) ||
         hipMemcpy(d_tr, traces, tr_bytes, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(d_cn, counts, cn_bytes, hipMemcpyHostToDevice) != hipSuccess)
         goto fail;
-    what = "dsm_reach_batch_device";
-    if ((rc = dsm_reach_batch_device(ctx, d_tr, d_cn, (uint64_t)n_dirs, &opts, 0, d_info, d_term, term_cap, NULL, NULL, NULL)))
-        goto fail;
+    if (audit) {
+        what = "dsm_reach_batch_audit_device";
+        rc = dsm_reach_batch_audit_device(ctx, d_tr, d_cn, (uint64_t)n_dirs, &opts, 0, d_info, d_ainfo, d_term, term_cap, NULL,
+                                          NULL, NULL, NULL, NULL, NULL);
+    } else {
+        what = "dsm_reach_batch_device";
+        rc = dsm_reach_batch_device(ctx, d_tr, d_cn, (uint64_t)n_dirs, &opts, 0, d_info, d_term, term_cap, NULL, NULL, NULL);
+    }
+    if (rc) goto fail;
     what = "read-back";
     if (hipDeviceSynchronize() != hipSuccess ||
-        hipMemcpy(info, d_info, (size_t)n_dirs * sizeof *info, hipMemcpyDeviceToHost) != hipSuccess)
+        hipMemcpy(info, d_info, (size_t)n_dirs * sizeof *info, hipMemcpyDeviceToHost) != hipSuccess ||
+        (audit && hipMemcpy(ainfo, d_ainfo, (size_t)n_dirs * sizeof *ainfo, hipMemcpyDeviceToHost) != hipSuccess))
         goto fail;
-    uint64_t n_dead = 0, n_exh = 0;
+    uint64_t n_dead = 0, n_exh = 0, n_inc = 0;
     for (int s = 0; s < n_dirs; ++s) {
         const dsm_reach_info *r = &info[s];
         uint32_t cap = DSM_CENSUS_MIN_CAP;
@@ -906,10 +927,26 @@ static int reach_batch(int np, uint32_t max_instr, int device, char **dirs, int 
             printf("warning: %llu fingerprint collisions: the result is not exact\n", (unsigned long long)r->fp_collisions);
         n_dead += r->by_status[DSM_DEADLOCKED] != 0;
         n_exh += !truncated;
+        if (audit) {
+            const dsm_audit *set = ainfo[s].set, *c = &set[DSM_RAUDIT_COMPLETED];
+            printf("%s: audit", dirs[s]);
+            for (int q = 0; q < DSM_RAUDIT_NSETS; ++q)
+                printf(" %s %llu/%llu", raudit_sets[q], (unsigned long long)set[q].violating, (unsigned long long)set[q].systems);
+            printf("\n");
+            if (c->violating)
+                printf("%s: can end incoherent: %llu of %llu completed states, first %llu depth %llu\n", dirs[s],
+                       (unsigned long long)c->violating, (unsigned long long)c->systems, (unsigned long long)~c->inv_first[7],
+                       (unsigned long long)ainfo[s].first_depth[DSM_RAUDIT_COMPLETED][7]);
+            n_inc += c->violating != 0;
+        }
     }
-    printf("screened %d tests: %llu can deadlock, %llu exhaustive\n", n_dirs, (unsigned long long)n_dead,
-           (unsigned long long)n_exh);
-    code = n_dead ? 2 : n_exh != (uint64_t)n_dirs ? 3 : 0;
+    if (audit)
+        printf("screened %d tests: %llu can deadlock, %llu can end incoherent, %llu exhaustive\n", n_dirs,
+               (unsigned long long)n_dead, (unsigned long long)n_inc, (unsigned long long)n_exh);
+    else
+        printf("screened %d tests: %llu can deadlock, %llu exhaustive\n", n_dirs, (unsigned long long)n_dead,
+               (unsigned long long)n_exh);
+    code = n_dead || n_inc ? 2 : n_exh != (uint64_t)n_dirs ? 3 : 0;
     what = NULL;
     rc = DSM_OK;
 fail:
@@ -918,13 +955,14 @@ fail:
     if (d_cn) (void)hipFree(d_cn);
     if (d_info) (void)hipFree(d_info);
     if (d_term) (void)hipFree(d_term);
+    if (d_ainfo) (void)hipFree(d_ainfo);
     if (ctx) dsm_close(ctx);
-    free(text); free(off); free(traces); free(counts); free(pst); free(info); free(term); free(cen);
+    free(text); free(off); free(traces); free(counts); free(pst); free(info); free(term); free(ainfo); free(cen);
     return code;
 }
 
 int main(int argc, char **argv) {
-    int np = 4, device = 0, quiet = 0, audit = 0, do_reach = 0, do_batch = 0, n_dirs = 0, states_set = 0;
+    int np = 4, device = 0, quiet = 0, audit = 0, do_reach = 0, do_batch = 0, batch_audit = 0, n_dirs = 0, states_set = 0;
     long long reach_states = 1ll << 22, reach_depth = 0, reach_inbox = 16;
     int reach_opts = 0;
     uint32_t prob_t[DSM_DIST_MAX_THRESH], n_prob = 0;
@@ -955,6 +993,7 @@ int main(int argc, char **argv) {
         }
         else if (!strcmp(argv[i], "--reach")) do_reach = 1;
         else if (!strcmp(argv[i], "--reach-batch")) do_batch = 1;
+        else if (!strcmp(argv[i], "--reach-batch-audit")) do_batch = batch_audit = 1;
         else if (!strcmp(argv[i], "--reach-states") && i + 1 < argc) { reach_states = atoll(argv[++i]); reach_opts = states_set = 1; }
         else if (!strcmp(argv[i], "--reach-depth") && i + 1 < argc) { reach_depth = atoll(argv[++i]); reach_opts = 1; }
         else if (!strcmp(argv[i], "--reach-inbox") && i + 1 < argc) { reach_inbox = atoll(argv[++i]); reach_opts = 1; }
@@ -1022,7 +1061,7 @@ int main(int argc, char **argv) {
             return EXIT_FAILURE;
         }
         return reach_batch(np, max_instr, device, argv + 1, n_dirs, (unsigned long long)reach_states,
-                           (uint32_t)reach_depth, (uint32_t)reach_inbox, explore_kind);
+                           (uint32_t)reach_depth, (uint32_t)reach_inbox, explore_kind, batch_audit);
     }
     if ((explore_n && issue_file) || (!explore_n && !do_reach && explore_opts)) { usage(argv[0]); return EXIT_FAILURE; }
     if ((reach_opts && !do_reach) ||

@@ -35,13 +35,20 @@
  * Every loop is bounded: levels by DSM_REACH_MAX_LEVELS, probes by the slot count, chunks by the
  * level's total, claims by n_sys (a workgroup stops at its first id >= n_sys).
  *
- * Host side of the same unit: dsm_reach_batch (a plain loop of dsm_reach), the slab's layout, and
- * the ctx-owned scratch.
+ * The reach batch audit (include/dsm.h, dsm_reach_batch_audit*) is the same kernel text with the
+ * AUDIT blocks compiled in, reach_batch_kernel<NP, AuditOut>: in the count pass the lane that holds
+ * state lo + i audits it from the slab's own word-major store (dsm_raudit_fn.h's raudit_state, the
+ * reach audit's lane body), writes its word and set byte, and the tile's words go into the
+ * system's four summaries and first depths in LDS (audit_accumulate), which the workgroup zeroes
+ * again with every claim and writes to ainfo[s] beside info[s].  Nothing is added to the slab.
+ *
+ * Host side of the same unit: dsm_reach_batch (a plain loop of dsm_reach), dsm_reach_batch_audit (a
+ * plain loop of dsm_reach_audit), the slab's layout, and the ctx-owned scratch.
  */
 #include <stdint.h>
 #include <string.h>
 
-#include "dsm_reach_dev.h"
+#include "dsm_raudit_fn.h"
 
 namespace {
 
@@ -106,6 +113,20 @@ struct BatchArgs {
 constexpr int INFO_WORDS = 14;
 static_assert(sizeof(dsm_reach_info) == INFO_WORDS * 8, "the kernel writes dsm_reach_info as words");
 
+/* what the audit form writes beside the search's outputs; each may be null */
+struct AuditOut {
+    u64 *ainfo;                   /* dsm_reach_audit_info: AINFO_WORDS words a system */
+    uint32_t *words;
+    uint8_t *sets;
+    uint32_t *term_words;
+};
+
+constexpr int SUM_WORDS = DSM_RAUDIT_NSETS * DSM_NAUDIT, FD_WORDS = DSM_RAUDIT_NSETS * 8;
+constexpr int AINFO_WORDS = SUM_WORDS + FD_WORDS + 4;         /* the summaries, first_depth, flags, 3 reserved */
+static_assert(sizeof(dsm_reach_audit_info) == AINFO_WORDS * 8, "the kernel writes dsm_reach_audit_info as words");
+static_assert(sizeof(dsm_audit) == DSM_NAUDIT * 8 && A_INV + 8 <= DSM_NAUDIT, "the summaries are DSM_NAUDIT slots each");
+static_assert(AINFO_WORDS <= RT, "one thread per word of dsm_reach_audit_info");
+
 /* exclusive scan of one value per lane over the workgroup; *total = the sum.  Every lane calls it. */
 __device__ __forceinline__ u64 wg_exscan(u64 v, u64 *s_w, u64 *total) {
     const uint32_t lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
@@ -129,12 +150,55 @@ __device__ __forceinline__ u64 wg_exscan(u64 v, u64 *s_w, u64 *total) {
     return before + x - v;
 }
 
-template <int NP>
-__global__ void __launch_bounds__(RT) reach_batch_kernel(const BatchArgs a) {
+/* The audit of one tile of the count pass into the system's summaries: aw the lane's audit word,
+ * setb its set byte (0 on a lane without a state), id0 the state of the wave's lane 0.  Every lane
+ * calls it.  One-bit counters are ballots, lines and bad items one packed wave sum per set; the
+ * wave's lane 0 adds them to LDS.  A class's first id is the ballot's lowest lane (ids ascend with
+ * the lane), its first depth the lowest level that saw it (levels ascend). */
+__device__ __forceinline__ void audit_accumulate(uint32_t aw, uint32_t setb, u64 id0, u64 depth, u64 *s_sum, u64 *s_fd) {
+    const bool first = (threadIdx.x & (WAVE - 1)) == 0;
+    const uint32_t c7 = aw & 0x7Fu, mark = c7 | (c7 ? 0x80u : 0u);   /* bit 7: any class */
+#pragma unroll
+    for (int k = 0; k < DSM_RAUDIT_NSETS; ++k) {
+        const bool in = (setb >> k) & 1u;
+        const u64 members = __ballot(in);
+        if (members == 0) continue;                                  /* uniform over the wave */
+        uint32_t pk = in ? ((aw >> 8) & 0xFFu) | ((aw >> 24) << 16) : 0u;   /* 64 x 255 fits 16 bits */
+#pragma unroll
+        for (int off = WAVE / 2; off > 0; off >>= 1) pk += __shfl_xor(pk, off, WAVE);
+        u64 *sum = s_sum + k * DSM_NAUDIT;
+        if (first) {
+            __hip_atomic_fetch_add(&sum[A_SYSTEMS], (u64)__builtin_popcountll(members), __ATOMIC_RELAXED, WG);
+            if (pk & 0xFFFFu) __hip_atomic_fetch_add(&sum[A_LINES], (u64)(pk & 0xFFFFu), __ATOMIC_RELAXED, WG);
+            if (pk >> 16) __hip_atomic_fetch_add(&sum[A_BAD], (u64)(pk >> 16), __ATOMIC_RELAXED, WG);
+        }
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const u64 hit = __ballot(in && ((mark >> b) & 1u));     /* every lane takes every ballot */
+            if (hit != 0 && first) {
+                __hip_atomic_fetch_add(&sum[b == 7 ? A_VIOLATING : A_CLASS + b], (u64)__builtin_popcountll(hit), __ATOMIC_RELAXED,
+                                       WG);
+                __hip_atomic_fetch_max(&sum[A_INV + b], ~(id0 + (u64)__builtin_ctzll(hit)), __ATOMIC_RELAXED, WG);
+                __hip_atomic_fetch_min(&s_fd[k * 8 + b], depth, __ATOMIC_RELAXED, WG);
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ const AuditOut &audit_out(const AuditOut &au) { return au; }
+
+/* reach_batch_kernel<NP>(BatchArgs) is the plain search; reach_batch_kernel<NP, AuditOut>(BatchArgs,
+ * AuditOut) the same text with the AUDIT blocks compiled in.  The audit's argument is a pack so that
+ * the plain kernel keeps its name, its arguments and, the AUDIT blocks being discarded, its code. */
+template <int NP, typename... AU>
+__global__ void __launch_bounds__(RT) reach_batch_kernel(const BatchArgs a, const AU... aus) {
+    constexpr bool AUDIT = sizeof...(AU) != 0;
+    static_assert(sizeof...(AU) <= 1, "at most the audit's outputs");
     __shared__ uint32_t s_tab[DT_TABLE_WORDS];
     __shared__ u64 s_w[RT / WAVE];
     __shared__ u64 s_sys;
     __shared__ uint32_t s_by[8], s_fill, s_coll;
+    __shared__ u64 s_sum[SUM_WORDS], s_fd[FD_WORDS];   /* AUDIT only: the four summaries, the first depths */
     const uint32_t t = threadIdx.x;
     table_to_lds(s_tab, a.step.table);
 
@@ -158,6 +222,10 @@ __global__ void __launch_bounds__(RT) reach_batch_kernel(const BatchArgs a) {
             s_fill = 0;
             s_coll = 0;
         }
+        if constexpr (AUDIT) {                /* a workgroup's summaries are one system's */
+            if (t < (uint32_t)SUM_WORDS) s_sum[t] = 0;
+            if (t < (uint32_t)FD_WORDS) s_fd[t] = ~0ull;
+        }
         __syncthreads();
         const u64 sys = s_sys;
         if (sys >= a.n_sys) break;
@@ -167,6 +235,14 @@ __global__ void __launch_bounds__(RT) reach_batch_kernel(const BatchArgs a) {
         u64 *terminals = a.terminals ? rs_terminal_at(a.terminals, sys * a.term_cap) : nullptr;
         uint32_t *parents = a.parents ? a.parents + (size_t)sys * cap : nullptr;
         uint8_t *masks = a.masks ? a.masks + (size_t)sys * cap : nullptr;
+        uint32_t *words = nullptr, *term_words = nullptr;
+        uint8_t *sets = nullptr;
+        if constexpr (AUDIT) {
+            const AuditOut &au = audit_out(aus...);
+            words = au.words ? au.words + (size_t)sys * cap : nullptr;
+            sets = au.sets ? au.sets + (size_t)sys * cap : nullptr;
+            term_words = au.term_words ? au.term_words + (size_t)sys * a.term_cap : nullptr;
+        }
 
         /* the slab's table, emptied; then the root */
         {
@@ -209,12 +285,27 @@ __global__ void __launch_bounds__(RT) reach_batch_kernel(const BatchArgs a) {
                 u64 tile;
                 const u64 ex = wg_exscan((u64)cnt | ((u64)(term ? 1u : 0u) << 32), s_w, &tile);
                 if (valid) offs[i] = total + (ex & 0xFFFFFFFFull);
+                uint32_t cls = DIST_RUNNING;  /* AUDIT: all the set byte needs of the class */
                 if (term) {
                     dsm_sys_result res;
                     (void)rs_terminal<NP>(m, 0u, &res);
                     atomicAdd(&s_by[res.status & 7u], 1u);
                     const u64 k = nterm + (ex >> 32);
                     if (terminals && k < a.term_cap) rs_put_terminal(rs_terminal_at(terminals, k), lo + i, res);
+                    if constexpr (AUDIT) cls = DIST_TERMINAL + (res.status & 7u);
+                }
+                if constexpr (AUDIT) {
+                    /* the audit of state lo + i on the lane that holds it: word w at (store + lo + base)[w * cap + t] */
+                    uint32_t aw = 0, setb = 0;
+                    if (valid) {
+                        const RaLoad ld = {store + lo + base, cap, t};
+                        aw = raudit_state<NP>(ld, cls, &setb);
+                        if (words) (words + lo + base)[t] = aw;
+                        if (sets) (sets + lo + base)[t] = (uint8_t)setb;
+                        const u64 k = nterm + (ex >> 32);
+                        if (term && term_words && k < a.term_cap) term_words[k] = aw;
+                    }
+                    audit_accumulate(aw, setb, lo + base + (t & ~(uint32_t)(WAVE - 1)), depth, s_sum, s_fd);
                 }
                 total += tile & 0xFFFFFFFFull;
                 nterm += tile >> 32;
@@ -284,13 +375,28 @@ __global__ void __launch_bounds__(RT) reach_batch_kernel(const BatchArgs a) {
             o[12] = flags | (s_coll ? DSM_REACH_F_COLLISION : 0u);
             o[13] = 0;
         }
+        if constexpr (AUDIT) {
+            const AuditOut &au = audit_out(aus...);
+            if (au.ainfo && t < (uint32_t)AINFO_WORDS) {
+                const uint64_t f = ((flags & (DSM_REACH_F_STATES | DSM_REACH_F_DEPTH)) ? DSM_RAUDIT_F_TRUNCATED : 0u) |
+                                   (s_coll ? DSM_RAUDIT_F_INEXACT : 0u);
+                au.ainfo[(size_t)sys * AINFO_WORDS + t] = t < (uint32_t)SUM_WORDS              ? s_sum[t]
+                                                          : t < (uint32_t)(SUM_WORDS + FD_WORDS) ? s_fd[t - SUM_WORDS]
+                                                          : t == (uint32_t)(SUM_WORDS + FD_WORDS) ? f
+                                                                                                  : 0;
+            }
+        }
     }
 }
 
+
+/* au: the audit form's outputs (reach_batch_kernel<NP, AuditOut>), or null (reach_batch_kernel<NP>) */
 template <int NP>
-int batch_launch(dsm_ctx *c, const BatchArgs &a, u64 budget, bool shrink, hipStream_t st) {
+int batch_launch(dsm_ctx *c, const BatchArgs &a, const AuditOut *au, u64 budget, bool shrink, hipStream_t st) {
     int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reach_batch_kernel<NP>, RT, 0) != hipSuccess || per_cu < 1)
+    if ((!au ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reach_batch_kernel<NP>, RT, 0)
+             : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reach_batch_kernel<NP, AuditOut>, RT, 0)) != hipSuccess ||
+        per_cu < 1)
         return DSM_E_DEVICE;
     u64 w = (u64)per_cu * (u64)(c->cus > 0 ? c->cus : 1);
     if (w > a.n_sys) w = a.n_sys;
@@ -325,7 +431,10 @@ int batch_launch(dsm_ctx *c, const BatchArgs &a, u64 budget, bool shrink, hipStr
     b.slabs = c->d_rb_scratch;
     b.claim = reinterpret_cast<u64 *>(c->d_rb_claim);
     HIPCK(hipMemsetAsync(c->d_rb_claim, 0, 8, st));
-    hipLaunchKernelGGL(reach_batch_kernel<NP>, dim3((unsigned)w), dim3(RT), 0, st, b);
+    if (au)
+        hipLaunchKernelGGL((reach_batch_kernel<NP, AuditOut>), dim3((unsigned)w), dim3(RT), 0, st, b, *au);
+    else
+        hipLaunchKernelGGL(reach_batch_kernel<NP>, dim3((unsigned)w), dim3(RT), 0, st, b);
     HIPCK(hipGetLastError());
     return DSM_OK;
 }
@@ -369,13 +478,14 @@ extern "C" int dsm_reach_batch(int np, const uint16_t *traces, const uint32_t *c
     return DSM_OK;
 }
 
-extern "C" int dsm_reach_batch_device(dsm_ctx *c, const uint16_t *d_traces, const uint32_t *d_counts, uint64_t n_sys,
-                                      const dsm_reach_opts *opts, uint64_t scratch_bytes, dsm_reach_info *d_info,
-                                      dsm_reach_terminal *d_terminals, uint64_t term_cap, uint32_t *d_parents,
-                                      uint8_t *d_masks, void *stream) {
+/* both device calls: au null for the plain one */
+static int batch_device(dsm_ctx *c, const uint16_t *d_traces, const uint32_t *d_counts, uint64_t n_sys, const dsm_reach_opts *opts,
+                        uint64_t scratch_bytes, dsm_reach_info *d_info, dsm_reach_terminal *d_terminals, uint64_t term_cap,
+                        uint32_t *d_parents, uint8_t *d_masks, const AuditOut *au, void *stream) {
     uint32_t L;
     if (!c || !batch_opts_ok(c->cfg.np, opts, &L) || (n_sys && (!d_traces || !d_counts))) return DSM_E_INVAL;
     if (((uintptr_t)d_info & 7u) || ((uintptr_t)d_terminals & 7u) || ((uintptr_t)d_parents & 3u)) return DSM_E_INVAL;
+    if (au && (((uintptr_t)au->ainfo & 7u) || ((uintptr_t)au->words & 3u) || ((uintptr_t)au->term_words & 3u))) return DSM_E_INVAL;
     if (n_sys == 0) return DSM_OK;
     BatchArgs a;
     memset(&a, 0, sizeof a);
@@ -398,6 +508,44 @@ extern "C" int dsm_reach_batch_device(dsm_ctx *c, const uint16_t *d_traces, cons
     a.parents = d_parents;
     a.masks = d_masks;
     const hipStream_t st = (hipStream_t)stream;
-    return c->cfg.np == 4 ? batch_launch<4>(c, a, budget, scratch_bytes == 0, st)
-                          : batch_launch<8>(c, a, budget, scratch_bytes == 0, st);
+    return c->cfg.np == 4 ? batch_launch<4>(c, a, au, budget, scratch_bytes == 0, st)
+                          : batch_launch<8>(c, a, au, budget, scratch_bytes == 0, st);
+}
+
+extern "C" int dsm_reach_batch_device(dsm_ctx *c, const uint16_t *d_traces, const uint32_t *d_counts, uint64_t n_sys,
+                                      const dsm_reach_opts *opts, uint64_t scratch_bytes, dsm_reach_info *d_info,
+                                      dsm_reach_terminal *d_terminals, uint64_t term_cap, uint32_t *d_parents,
+                                      uint8_t *d_masks, void *stream) {
+    return batch_device(c, d_traces, d_counts, n_sys, opts, scratch_bytes, d_info, d_terminals, term_cap, d_parents, d_masks,
+                        nullptr, stream);
+}
+
+/* ---- the reach batch audit ---------------------------------------------------------------------- */
+extern "C" int dsm_reach_batch_audit(int np, const uint16_t *traces, const uint32_t *counts, uint32_t stride, uint64_t n_sys,
+                                     const dsm_reach_opts *opts, dsm_reach_info *info, dsm_reach_audit_info *ainfo,
+                                     dsm_reach_terminal *terminals, uint64_t term_cap, uint32_t *parents, uint8_t *masks,
+                                     uint32_t *words, uint8_t *sets, uint32_t *term_words) {
+    uint32_t L;
+    if (!batch_opts_ok(np, opts, &L) || stride == 0 || stride > DSM_MAX_INSTR || (n_sys && (!traces || !counts)))
+        return DSM_E_INVAL;
+    for (uint64_t s = 0; s < n_sys; ++s) {
+        const size_t row = (size_t)s * opts->max_states, trow = (size_t)s * term_cap;
+        const int rc = dsm_reach_audit(np, traces + (size_t)s * np * stride, counts + (size_t)s * np, stride, opts,
+                                       info ? info + s : nullptr, ainfo ? ainfo + s : nullptr, parents ? parents + row : nullptr,
+                                       masks ? masks + row : nullptr, nullptr, terminals ? terminals + trow : nullptr, term_cap,
+                                       words ? words + row : nullptr, sets ? sets + row : nullptr,
+                                       term_words ? term_words + trow : nullptr);
+        if (rc) return rc;
+    }
+    return DSM_OK;
+}
+
+extern "C" int dsm_reach_batch_audit_device(dsm_ctx *c, const uint16_t *d_traces, const uint32_t *d_counts, uint64_t n_sys,
+                                            const dsm_reach_opts *opts, uint64_t scratch_bytes, dsm_reach_info *d_info,
+                                            dsm_reach_audit_info *d_ainfo, dsm_reach_terminal *d_terminals, uint64_t term_cap,
+                                            uint32_t *d_parents, uint8_t *d_masks, uint32_t *d_words, uint8_t *d_sets,
+                                            uint32_t *d_term_words, void *stream) {
+    const AuditOut au = {reinterpret_cast<u64 *>(d_ainfo), d_words, d_sets, d_term_words};
+    return batch_device(c, d_traces, d_counts, n_sys, opts, scratch_bytes, d_info, d_terminals, term_cap, d_parents, d_masks, &au,
+                        stream);
 }

@@ -189,6 +189,10 @@ def lib():
             "dsm_reach_batch": (i32, [i32, vp, vp, u32, u64, ctypes.POINTER(ReachOpts), vp, vp, u64, vp, vp]),
             "dsm_reach_batch_device": (i32, [vp, vp, vp, u64, ctypes.POINTER(ReachOpts), u64, vp, vp, u64, vp, vp, vp]),
             "dsm_debug_reach_batch_state": (i32, [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+            "dsm_reach_batch_audit": (i32, [i32, vp, vp, u32, u64, ctypes.POINTER(ReachOpts), vp, vp, vp, u64, vp, vp, vp,
+                                            vp, vp]),
+            "dsm_reach_batch_audit_device": (i32, [vp, vp, vp, u64, ctypes.POINTER(ReachOpts), u64, vp, vp, vp, u64, vp,
+                                                   vp, vp, vp, vp, vp]),
             "dsm_reach_path": (i32, [vp, vp, u64, vp, u64, ctypes.POINTER(u64)]),
             "dsm_reach_replay": (i32, [i32, vp, vp, u32, u32, vp, u64, vp, vp, vp]),
             "dsm_census_insert": (i32, [vp, u32, u64, u64]),
@@ -861,6 +865,53 @@ def reach_audit(np_, traces, counts, inbox_limit=16, kind=CENSUS_DUMPS, max_stat
     return _raudit_result(info, ainfo, parents, masks, level_off, terms, words, sets, term_words, term_cap)
 
 
+# -- reach batch audit (ABI 5 +reach batch audit) ---------------------------------------------
+def _reach_audit_many_result(info, ainfo, terms, term_cap, parents, masks, words, sets, term_words, max_states):
+    """The dict of reach_audit_many from the batch audit's flat arrays."""
+    n = len(info)
+    out = _reach_many_result(info, terms, term_cap, parents, masks, max_states)
+    tw = term_words[:n * term_cap].reshape(n, term_cap)
+    out.update({"audit": ainfo["set"].copy().reshape(n, RAUDIT_NSETS), "first_depth": ainfo["first_depth"].copy(),
+                "flags": ainfo["flags"].copy(), "reserved": ainfo["reserved"].copy(),
+                "term_words": [tw[s, :min(term_cap, int(info["terminals"][s]))] for s in range(n)],
+                "can_end_incoherent": ainfo["set"]["violating"][:, RAUDIT_COMPLETED] > 0 if n else np.zeros(0, bool),
+                "incoherent_quiescent": ainfo["set"]["violating"][:, RAUDIT_QUIESCENT] > 0 if n else np.zeros(0, bool)})
+    if words is not None:
+        out["words"] = [words[s * max_states: s * max_states + int(info["states"][s])] for s in range(n)]
+        out["sets"] = [sets[s * max_states: s * max_states + int(info["states"][s])] for s in range(n)]
+    return out
+
+
+def reach_audit_many(np_, traces, counts, inbox_limit=16, kind=CENSUS_DUMPS, max_states=1 << 16, max_depth=0, term_cap=None,
+                     witnesses=False, per_state=False):
+    """dsm_reach_batch_audit (the host reference; no GPU): pydsm.reach_audit over every system of
+    traces [n, np, stride] u16, counts [n, np] -> the dict of reach_many plus audit (AUDIT_DTYPE
+    [n, 4]: the summaries of the sets all, quiescent, terminal, completed), first_depth (uint64
+    [n, 4, 8]), flags (RAUDIT_F_*), term_words (a list per system: the audit words of its terminals),
+    can_end_incoherent (the completed set has a violating state) and incoherent_quiescent (the
+    quiescent set has one), bool arrays; with per_state the lists words and sets."""
+    traces = np.ascontiguousarray(traces, dtype=np.uint16)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    assert traces.ndim == 3 and traces.shape[1] == np_ and counts.shape == traces.shape[:2]
+    n = traces.shape[0]
+    opts = ReachOpts(inbox_limit, CENSUS_KINDS.get(kind, kind), max_states, max_depth, 0)
+    ok = 0 < max_states <= REACH_BATCH_MAX_STATES
+    cap = max_states if ok else 1
+    term_cap = min(cap, 4096) if term_cap is None else term_cap
+    info = np.zeros(n, dtype=REACH_INFO_DTYPE)
+    ainfo = np.zeros(n, dtype=RAUDIT_INFO_DTYPE)
+    terms = np.zeros(max(n * term_cap, 1), dtype=REACH_TERMINAL_DTYPE)
+    term_words = np.zeros(max(n * term_cap, 1), np.uint32)
+    parents = np.zeros(max(n * cap, 1), np.uint32) if witnesses else None
+    masks = np.zeros(max(n * cap, 1), np.uint8) if witnesses else None
+    words = np.zeros(max(n * cap, 1), np.uint32) if per_state else None
+    sets = np.zeros(max(n * cap, 1), np.uint8) if per_state else None
+    _check(lib().dsm_reach_batch_audit(np_, _ptr(traces), _ptr(counts), traces.shape[2], n, ctypes.byref(opts), _ptr(info),
+                                       _ptr(ainfo), _ptr(terms), term_cap, _ptr(parents), _ptr(masks), _ptr(words),
+                                       _ptr(sets), _ptr(term_words)), "dsm_reach_batch_audit")
+    return _reach_audit_many_result(info, ainfo, terms[:n * term_cap], term_cap, parents, masks, words, sets, term_words, cap)
+
+
 def _reach_terminals_result(info, terms, kind):
     d = reach_info_to_dict(info)
     nt = min(d["terminals"], len(terms))
@@ -1171,6 +1222,53 @@ class Engine:
         return _reach_many_result(info, terms, term_cap,
                                   d_par.cpu().numpy().view(np.uint32) if witnesses else None,
                                   d_msk.cpu().numpy() if witnesses else None, cap)
+
+    def reach_batch_audit_device(self, d_traces, d_counts, n_sys, opts, d_info, d_ainfo, d_terminals, term_cap, d_parents,
+                                 d_masks, d_words, d_sets, d_term_words, scratch_bytes=0, stream=0):
+        """dsm_reach_batch_audit_device: device pointers or tensors, each output may be None.
+        ASYNCHRONOUS on `stream`; returns the error code."""
+        return lib().dsm_reach_batch_audit_device(self.ctx, _dptr(d_traces), _dptr(d_counts), n_sys, ctypes.byref(opts),
+                                                  scratch_bytes, _dptr(d_info), _dptr(d_ainfo), _dptr(d_terminals),
+                                                  term_cap, _dptr(d_parents), _dptr(d_masks), _dptr(d_words),
+                                                  _dptr(d_sets), _dptr(d_term_words), ctypes.c_void_p(stream))
+
+    def reach_audit_many(self, traces, counts, inbox_limit=16, kind=CENSUS_DUMPS, max_states=1 << 16, max_depth=0, chunk=0,
+                         term_cap=None, witnesses=False, per_state=False, scratch_bytes=0):
+        """The coherence audit of every state each of n systems (traces [n, np, max_instr] u16, counts
+        [n, np]) can reach, searched and audited by one asynchronous launch on the GPU -> the dict of
+        pydsm.reach_audit_many."""
+        import torch
+        tr, cn = np.ascontiguousarray(traces, dtype=np.uint16), np.ascontiguousarray(counts, dtype=np.uint32)
+        if tr.ndim != 3 or tr.shape[1:] != (self.np, self.max_instr) or cn.shape != tr.shape[:2]:
+            raise DsmError(E_INVAL, "reach_audit_many: systems of the engine's np and max_instr")
+        n = tr.shape[0]
+        dev = torch.device("cuda", self.device)
+        d_tr = torch.from_numpy(tr.view(np.int16).reshape(-1)).to(dev)
+        d_cn = torch.from_numpy(cn.view(np.int32).reshape(-1)).to(dev)
+        ok = 0 < max_states <= REACH_BATCH_MAX_STATES
+        cap = max_states if ok else 1
+        term_cap = min(cap, 4096) if term_cap is None else term_cap
+        d_info = torch.zeros(max(n, 1) * len(REACH_INFO_FIELDS), dtype=torch.int64, device=dev)
+        d_ainfo = torch.zeros(max(n, 1) * (RAUDIT_INFO_DTYPE.itemsize // 8), dtype=torch.int64, device=dev)
+        d_term = torch.zeros(5 * max(n * term_cap, 1), dtype=torch.int64, device=dev)
+        d_tw = torch.zeros(max(n * term_cap, 1), dtype=torch.int32, device=dev)
+        d_par = torch.zeros(max(n * cap, 1), dtype=torch.int32, device=dev) if witnesses else None
+        d_msk = torch.zeros(max(n * cap, 1), dtype=torch.uint8, device=dev) if witnesses else None
+        d_words = torch.zeros(max(n * cap, 1), dtype=torch.int32, device=dev) if per_state else None
+        d_sets = torch.zeros(max(n * cap, 1), dtype=torch.uint8, device=dev) if per_state else None
+        opts = ReachOpts(inbox_limit, CENSUS_KINDS.get(kind, kind), max_states, max_depth, chunk)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _check(self.reach_batch_audit_device(d_tr, d_cn, n, opts, d_info, d_ainfo, d_term, term_cap, d_par, d_msk, d_words,
+                                             d_sets, d_tw, scratch_bytes, st), "dsm_reach_batch_audit_device")
+        info = d_info.cpu().numpy().view(REACH_INFO_DTYPE)[:n]          # .cpu() waits for the stream
+        ainfo = d_ainfo.cpu().numpy().view(RAUDIT_INFO_DTYPE)[:n]
+        terms = d_term.cpu().numpy().view(REACH_TERMINAL_DTYPE)[:n * term_cap]
+        return _reach_audit_many_result(info, ainfo, terms, term_cap,
+                                        d_par.cpu().numpy().view(np.uint32) if witnesses else None,
+                                        d_msk.cpu().numpy() if witnesses else None,
+                                        d_words.cpu().numpy().view(np.uint32) if per_state else None,
+                                        d_sets.cpu().numpy() if per_state else None,
+                                        d_tw.cpu().numpy().view(np.uint32), cap)
 
     def reach_dist_device(self, d_trace, d_counts, opts, thresh, max_rounds, rinfo, dinfo, d_terminals, d_term_mass,
                           term_cap, round_mass, stream=0):

@@ -62,7 +62,9 @@ extern "C" {
                              5 (+reach batch): additive -- the search of a whole ensemble in one
                                 asynchronous launch (dsm_reach_batch*) likewise;
                              5 (+reach audit): additive -- the coherence of every reachable state
-                                (dsm_reach_audit*) likewise */
+                                (dsm_reach_audit*) likewise;
+                             5 (+reach batch audit): additive -- that audit for a whole ensemble
+                                in one asynchronous launch (dsm_reach_batch_audit*) likewise */
 
 #define DSM_MAX_NP 8             /* bitVector is one byte (README.md:51)                  */
 #define DSM_CACHE_SIZE 4         /* CACHE_SIZE      assignment.c:10                        */
@@ -1027,6 +1029,44 @@ int dsm_reach_audit_device(dsm_ctx *ctx, const uint16_t *d_trace, const uint32_t
                            dsm_reach_audit_info *ainfo, uint32_t *d_parents, uint8_t *d_masks,
                            uint64_t *level_off, dsm_reach_terminal *d_terminals, uint64_t term_cap,
                            uint32_t *d_words, uint8_t *d_sets, uint32_t *d_term_words, void *stream);
+
+/* ---- reach batch audit: the coherence of every reachable state, per ensemble ---------------- *
+ * The reach batch and the reach audit in one call: which systems of an ensemble can END
+ * incoherent (the DSM_RAUDIT_COMPLETED set has a violating state), or pass through an incoherent
+ * quiescent state, under any interleaving.  Inputs, options, limits and the rows of info,
+ * terminals, parents and masks are dsm_reach_batch's; the audit adds, each may be NULL:
+ *   ainfo[s];
+ *   term_words[s * term_cap + i] for i < min(term_cap, info[s].terminals): the audit word of
+ *     terminal i (it does not need `terminals` itself);
+ *   words[s * max_states + id] and sets[s * max_states + id] for id < info[s].states.
+ * Entries of a system's own row at and after those bounds are unspecified (the host call leaves
+ * them alone); nothing outside the rows is written.  For every s, every written value equals what
+ * dsm_reach_audit gives for that system alone under the same opts -- the summaries, inv_first,
+ * first_depth, the flags, the zeroed reserved words, and under truncation the audit of the last
+ * kept level and of nothing after it -- but fp_collisions, which keeps the device's meaning as in
+ * dsm_reach_batch_device; DSM_RAUDIT_F_INEXACT follows the device's DSM_REACH_F_COLLISION.
+ * Results never depend on chunk, on scratch_bytes or on how many systems are in flight. */
+/* the host reference (no GPU): dsm_reach_audit over systems 0 .. n_sys-1, a plain loop */
+int dsm_reach_batch_audit(int np, const uint16_t *traces, const uint32_t *counts, uint32_t stride,
+                          uint64_t n_sys, const dsm_reach_opts *opts, dsm_reach_info *info,
+                          dsm_reach_audit_info *ainfo, dsm_reach_terminal *terminals,
+                          uint64_t term_cap, uint32_t *parents, uint8_t *masks, uint32_t *words,
+                          uint8_t *sets, uint32_t *term_words);
+/* The same on the GPU, ASYNCHRONOUS on `stream` like dsm_reach_batch_device: one memset and one
+ * launch, no host wait.  A state is audited by the lane that holds it when its level is counted,
+ * from the slab's own state store, so the slab is dsm_reach_batch_device's
+ * (dsm_reach_batch_slab_bytes applies unchanged) and so are the ctx's scratch, the claim counter,
+ * scratch_bytes and the "one run at a time, one stream" convention: plain and audit calls may
+ * follow each other on one ctx.  All pointers are device memory (d_info, d_ainfo and d_terminals
+ * 8-byte aligned, d_parents, d_words and d_term_words 4-byte; a misaligned output is
+ * DSM_E_INVAL).  DSM_E_NOMEM, with nothing enqueued, when not one slab fits; n_sys == 0 is a
+ * no-op; every other error as in dsm_reach_batch_device. */
+int dsm_reach_batch_audit_device(dsm_ctx *ctx, const uint16_t *d_traces, const uint32_t *d_counts,
+                                 uint64_t n_sys, const dsm_reach_opts *opts, uint64_t scratch_bytes,
+                                 dsm_reach_info *d_info, dsm_reach_audit_info *d_ainfo,
+                                 dsm_reach_terminal *d_terminals, uint64_t term_cap,
+                                 uint32_t *d_parents, uint8_t *d_masks, uint32_t *d_words,
+                                 uint8_t *d_sets, uint32_t *d_term_words, void *stream);
 
 /* ---- multi-GPU group: RCCL over xGMI --------------------------------------- *
  * Systems are independent, so an ensemble shards over GPUs with no data-path exchange; the
