@@ -63,6 +63,24 @@
  *                    the device traces of the exploration.  Exit codes and the other output do not
  *                    change.
  *   --events-kind instr|msg|all   which build's lines (default all: both, interleaved)
+ *   --profile        the access profile of the run (dsm_profile_runs_device: a replay of the system
+ *                    on the GPU with a counting log): after the run's other output, one line per
+ *                    node with the 16 fields of its dsm_node_profile, then their totals,
+ *                        profile node n: rd_hit H rd_miss_cold C ... open_since R recv M
+ *                        profile total: rd_hit H ... max_wait W open_since O recv M
+ *                    (in the totals max_wait is the maximum and open_since the number of nodes
+ *                    whose transaction is still open).  With --explore N it profiles the N variants
+ *                    on the device traces of the exploration and prints, after the explore output,
+ *                        profile: systems N accesses A hits H misses cold C conflict F coherence K
+ *                        profile total: ...
+ *                        profile latency: txns T mean M max W open O
+ *                        profile latency histogram: L:count ...
+ *                        profile top misses: 0xAA:count ...
+ *                        profile top coherence misses: 0xAA:count ...
+ *                    (the non-empty buckets, bucket 63 as 63+; the eight commonest addresses, ties
+ *                    by address; `none` where there is nothing to list).  It composes with
+ *                    --schedule, --quiet does not suppress it, and exit codes, the output files
+ *                    and the other output do not change.  Not valid with --reach or --reach-batch.
  *   --check DIR      only with --explore: can the system produce the output files in DIR, and
  *                    how often?  DIR/core_<n>_output.txt is read back into a record
  *                    (dsm_read_dump; a core without a file is one that wrote none) and looked up
@@ -172,7 +190,7 @@ static void usage(const char *argv0) {
     fprintf(stderr, "Usage: %s [--np 4|8] [--max-instr N] [--device D] [--quiet] [--issue-order FILE]\n"
                     "          [--schedule SEED:THRESH] [--explore N [--explore-dir DIR]\n"
                     "          [--explore-kind dumps|final|full] [--check DIR]] [--audit]\n"
-                    "          [--events FILE [--events-kind instr|msg|all]]\n"
+                    "          [--events FILE [--events-kind instr|msg|all]] [--profile]\n"
                     "          [--reach [--audit] [--reach-states N] [--reach-depth D] [--reach-inbox L] [--reach-prob T[,T...]]\n"
                     "          [--fate completed|deadlocked|ring_overflow|assert_failed|round_limit|0xKEY]\n"
                     "          [--explore-dir DIR]\n"
@@ -252,11 +270,85 @@ done:
     return rc;
 }
 
+/* --profile: the 16 fields by name on one line */
+static void print_profile_fields(const char *prefix, const uint64_t *v) {
+    printf("%s:", prefix);
+    for (int f = 0; f < 16; ++f) printf(" %s %llu", dsm_profile_field_name(f), (unsigned long long)v[f]);
+    printf("\n");
+}
+
+/* the `top` commonest addresses of a 128-bin histogram, ties by address */
+static void print_profile_top(const char *prefix, const uint64_t *h, int top) {
+    int done[128] = {0}, k = 0;
+    printf("%s:", prefix);
+    for (; k < top; ++k) {
+        int best = -1;
+        for (int a = 0; a < 128; ++a)
+            if (!done[a] && h[a] && (best < 0 || h[a] > h[best])) best = a;
+        if (best < 0) break;
+        done[best] = 1;
+        printf(" 0x%02X:%llu", best, (unsigned long long)h[best]);
+    }
+    printf(k ? "\n" : " none\n");
+}
+
+/* --profile: systems 0 .. n-1 of the device ensemble profiled under the ctx's schedule.  A plain
+ * run (n 1, nodes set): a line per node, then the totals; --explore: the ensemble summary.
+ * Returns DSM_OK or an error code (*what names the step). */
+static int print_profile(dsm_ctx *ctx, int np, const uint16_t *d_tr, const uint32_t *d_cn, uint64_t n, int nodes,
+                         const char **what) {
+    dsm_node_profile *d_np = NULL, rec[DSM_MAX_NP];
+    dsm_profile *d_pf = NULL, pf;
+    int rc = DSM_E_NOMEM;
+    *what = "profile: memory";
+    if (hipMalloc((void **)&d_pf, sizeof pf) != hipSuccess || hipMemset(d_pf, 0, sizeof pf) != hipSuccess ||
+        (nodes && hipMalloc((void **)&d_np, sizeof rec) != hipSuccess))
+        goto done;
+    *what = "dsm_profile_runs_device";
+    if ((rc = dsm_profile_runs_device(ctx, d_tr, d_cn, n, NULL, n, d_np, d_pf, NULL, NULL))) goto done;
+    rc = DSM_E_DEVICE;
+    if (hipMemcpy(&pf, d_pf, sizeof pf, hipMemcpyDeviceToHost) != hipSuccess ||
+        (d_np && hipMemcpy(rec, d_np, (size_t)np * sizeof rec[0], hipMemcpyDeviceToHost) != hipSuccess))
+        goto done;
+    rc = DSM_OK;
+    if (nodes) {
+        for (int c = 0; c < np; ++c) {
+            const uint32_t *w = (const uint32_t *)&rec[c];
+            uint64_t v[16];
+            char prefix[32];
+            for (int f = 0; f < 16; ++f) v[f] = w[f];
+            snprintf(prefix, sizeof prefix, "profile node %d", c);
+            print_profile_fields(prefix, v);
+        }
+        print_profile_fields("profile total", pf.total);
+    } else {
+        const uint64_t *t = pf.total;
+        const uint64_t hits = t[0] + t[4] + t[5], cold = t[1] + t[6], conf = t[2] + t[7], coh = t[3] + t[8];
+        int k = 0;
+        printf("profile: systems %llu accesses %llu hits %llu misses cold %llu conflict %llu coherence %llu\n",
+               (unsigned long long)pf.systems, (unsigned long long)(hits + cold + conf + coh), (unsigned long long)hits,
+               (unsigned long long)cold, (unsigned long long)conf, (unsigned long long)coh);
+        print_profile_fields("profile total", t);
+        printf("profile latency: txns %llu mean %.3f max %llu open %llu\n", (unsigned long long)t[11],
+               t[11] ? (double)t[12] / (double)t[11] : 0.0, (unsigned long long)t[13], (unsigned long long)t[14]);
+        printf("profile latency histogram:");
+        for (int b = 0; b < 64; ++b)
+            if (pf.latency[b]) printf(" %d%s:%llu", b, b == 63 ? "+" : "", (unsigned long long)pf.latency[b]), ++k;
+        printf(k ? "\n" : " none\n");
+        print_profile_top("profile top misses", pf.miss_addr, 8);
+        print_profile_top("profile top coherence misses", pf.coh_addr, 8);
+    }
+done:
+    if (d_np) (void)hipFree(d_np);
+    if (d_pf) (void)hipFree(d_pf);
+    return rc;
+}
+
 /* --explore: n copies of the parsed system under schedule (seed, thresh), one run with
  * snapshots, both censuses on the device.  Returns the process exit code. */
 static int explore(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces, const uint32_t *counts,
                    uint32_t n, unsigned long long seed, unsigned thresh, int kind, const char *out_dir, int audit,
-                   const char *check_dir, const char *events_file, int events_kind) {
+                   const char *check_dir, const char *events_file, int events_kind, int profile) {
     uint32_t cap = DSM_CENSUS_MIN_CAP;
     while (cap < n) cap <<= 1;
     const size_t words = DSM_CENSUS_WORDS(cap), slot = (size_t)np * stride;
@@ -443,6 +535,7 @@ static int explore(dsm_ctx *ctx, int np, uint32_t stride, const uint16_t *traces
         }
         code = cnt[np] ? 0 : dropped ? 3 : 4;
     }
+    if (profile && (rc = print_profile(ctx, np, d_tr, d_cn, n, 0, &what))) { code = EXIT_FAILURE; goto fail; }
     what = NULL;
 fail:
     if (what) fprintf(stderr, "Error: explore: %s%s%s\n", what, rc ? ": " : "", rc ? dsm_strerror(rc) : "");
@@ -975,13 +1068,14 @@ int main(int argc, char **argv) {
     int have_sched = 0, explore_kind = DSM_CENSUS_DUMPS, explore_opts = 0;
     long long explore_n = 0;
     const char *explore_dir = NULL, *check_dir = NULL, *events_file = NULL;
-    int events_kind = DSM_EV_FMT_INSTR | DSM_EV_FMT_MSG, events_opts = 0;
+    int events_kind = DSM_EV_FMT_INSTR | DSM_EV_FMT_MSG, events_opts = 0, profile = 0;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--np") && i + 1 < argc) np = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--max-instr") && i + 1 < argc) max_instr = (uint32_t)atoi(argv[++i]);
         else if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--quiet")) quiet = 1;
         else if (!strcmp(argv[i], "--audit")) audit = 1;
+        else if (!strcmp(argv[i], "--profile")) profile = 1;
         else if (!strcmp(argv[i], "--issue-order") && i + 1 < argc) issue_file = argv[++i];
         else if (!strcmp(argv[i], "--schedule") && i + 1 < argc) {
             if (sscanf(argv[++i], "%llu:%u", &sched_seed, &sched_thresh) != 2) { usage(argv[0]); return EXIT_FAILURE; }
@@ -1053,7 +1147,7 @@ int main(int argc, char **argv) {
     }
     if (do_batch) {
         if (!states_set) reach_states = 1ll << 16;
-        if (do_reach || explore_n || have_sched || events_file || events_opts || issue_file || audit || explore_dir ||
+        if (do_reach || explore_n || have_sched || events_file || events_opts || issue_file || audit || profile || explore_dir ||
             check_dir || n_prob || fate_name || explore_kind == DSM_CENSUS_FULL || reach_states < 1 ||
             reach_states > (long long)DSM_REACH_BATCH_MAX_STATES || reach_depth < 0 ||
             reach_depth >= (long long)DSM_REACH_MAX_LEVELS || reach_inbox < 1 || reach_inbox > 16) {
@@ -1065,7 +1159,7 @@ int main(int argc, char **argv) {
     }
     if ((explore_n && issue_file) || (!explore_n && !do_reach && explore_opts)) { usage(argv[0]); return EXIT_FAILURE; }
     if ((reach_opts && !do_reach) ||
-        (do_reach && (explore_n || have_sched || events_file || issue_file || explore_kind == DSM_CENSUS_FULL ||
+        (do_reach && (explore_n || have_sched || events_file || issue_file || profile || explore_kind == DSM_CENSUS_FULL ||
                       (check_dir && explore_kind != DSM_CENSUS_DUMPS) || reach_states < 1 ||
                       reach_states > (long long)DSM_REACH_MAX_STATES || reach_depth < 0 ||
                       reach_depth >= (long long)DSM_REACH_MAX_LEVELS || reach_inbox < 1 || reach_inbox > 16))) {
@@ -1127,7 +1221,7 @@ int main(int argc, char **argv) {
     }
     if (explore_n) {
         const int code = explore(ctx, np, stride, traces, counts, (uint32_t)explore_n, sched_seed, sched_thresh,
-                                 explore_kind, explore_dir, audit, check_dir, events_file, events_kind);
+                                 explore_kind, explore_dir, audit, check_dir, events_file, events_kind, profile);
         dsm_close(ctx);
         free(traces);
         return code;
@@ -1199,6 +1293,26 @@ int main(int argc, char **argv) {
             return EXIT_FAILURE;
         }
         print_audit_word("audit", w);
+    }
+    if (profile) {                                      /* hits, misses by cause, miss latency: a replay */
+        uint16_t *d_tr = NULL;
+        uint32_t *d_cn = NULL;
+        const char *what = "profile: memory";
+        const size_t tr_bytes = (size_t)np * stride * sizeof(uint16_t);
+        rc = DSM_E_NOMEM;
+        if (hipMalloc((void **)&d_tr, tr_bytes) == hipSuccess && hipMalloc((void **)&d_cn, sizeof counts) == hipSuccess) {
+            rc = DSM_E_DEVICE;
+            if (hipMemcpy(d_tr, traces, tr_bytes, hipMemcpyHostToDevice) == hipSuccess &&
+                hipMemcpy(d_cn, counts, (size_t)np * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess)
+                rc = print_profile(ctx, np, d_tr, d_cn, 1, 1, &what);
+        }
+        if (d_tr) (void)hipFree(d_tr);
+        if (d_cn) (void)hipFree(d_cn);
+        if (rc) {
+            fprintf(stderr, "Error: %s: %s\n", what, dsm_strerror(rc));
+            dsm_close(ctx);
+            return EXIT_FAILURE;
+        }
     }
     dsm_close(ctx);
     free(traces);

@@ -115,6 +115,9 @@ struct dsm_ctx {
     size_t rb_scratch_cap;
     unsigned long long *d_rb_claim;  /*   and the claim counter, zeroed on the stream per call */
     uint64_t rb_in_flight;           /* workgroups of the last call                           */
+    /* dsm_profile.hip */
+    uint32_t *d_pf_scratch;          /* profile_kernel: per-lane system state (dsm_profile.h) */
+    size_t pf_scratch_cap;
 };
 
 #define HIPCK(x) do { if ((x) != hipSuccess) return DSM_E_DEVICE; } while (0)
@@ -200,6 +203,8 @@ void dsm_text_release(dsm_ctx *c);
 void dsm_events_release(dsm_ctx *c);
 /* dsm_reach_batch.hip: called by dsm_close */
 void dsm_reach_batch_release(dsm_ctx *c);
+/* dsm_profile.hip: called by dsm_close */
+void dsm_profile_release(dsm_ctx *c);
 
 /* dsm_sim.hip: the transition kernel of a launch -- the fast kernel of (ring, mode), nullptr
  * where the dispatch has none, and the 256-deep re-run kernel; its resident workgroups per CU

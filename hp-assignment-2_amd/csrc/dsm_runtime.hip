@@ -135,6 +135,7 @@ extern "C" void dsm_close(dsm_ctx *c) {
     dsm_text_release(c);
     dsm_events_release(c);
     dsm_reach_batch_release(c);
+    dsm_profile_release(c);
     for (int i = 0; i < DSM_TIMING_RING; ++i) {
         if (c->tev0[i]) (void)hipEventDestroy(c->tev0[i]);
         if (c->tev1[i]) (void)hipEventDestroy(c->tev1[i]);

@@ -181,6 +181,11 @@ def lib():
                                        vp, vp, vp]),
             "dsm_event_trace_hash": (u64, [vp, u64]),
             "dsm_format_event_trace": (i32, [vp, u64, i32, ctypes.c_char_p, ctypes.c_size_t]),
+            # ABI 5 (+profile): the access profile
+            "dsm_profile_runs_device": (i32, [vp, vp, vp, u64, vp, u64, vp, vp, vp, vp]),
+            "dsm_profile_runs": (i32, [i32, vp, vp, u32, u64, vp, u64, ctypes.POINTER(EventOpts), vp, vp, vp]),
+            "dsm_profile_merge": (i32, [vp, vp]),
+            "dsm_profile_field_name": (ctypes.c_char_p, [i32]),
             # ABI 5 (+reach): the exhaustive exploration
             "dsm_reach": (i32, [i32, vp, vp, u32, ctypes.POINTER(ReachOpts), vp, vp, vp, vp, vp, vp, u64]),
             "dsm_reach_device": (i32, [vp, vp, vp, ctypes.POINTER(ReachOpts), vp, vp, vp, vp, vp, vp, u64, vp]),
@@ -495,6 +500,73 @@ def format_event_trace(events, what=EV_FMT_ALL):
     if n < 0:
         raise DsmError(n, "dsm_format_event_trace")
     return text
+
+
+# -- access profile (ABI 5 +profile) --------------------------------------------------------------
+PROFILE_FIELDS = ("rd_hit", "rd_miss_cold", "rd_miss_conflict", "rd_miss_coherence", "wr_hit", "wr_upgrade",
+                  "wr_miss_cold", "wr_miss_conflict", "wr_miss_coherence", "repl_clean", "repl_dirty", "txns",
+                  "wait_rounds", "max_wait", "open_since", "recv")
+NODE_PROFILE_DTYPE = np.dtype([(f, "<u4") for f in PROFILE_FIELDS])
+NPROFILE = 352                               # DSM_NPROFILE
+PROFILE_DTYPE = np.dtype([("total", "<u8", (16,)), ("systems", "<u8"), ("reserved", "<u8", (15,)),
+                          ("latency", "<u8", (64,)), ("miss_addr", "<u8", (128,)), ("coh_addr", "<u8", (128,))])
+assert NODE_PROFILE_DTYPE.itemsize == 64 and PROFILE_DTYPE.itemsize == 8 * NPROFILE
+
+
+def profile_field_name(i):
+    """dsm_profile_field_name: the name of field i of a node profile, or None."""
+    s = lib().dsm_profile_field_name(i)
+    return s.decode() if s is not None else None
+
+
+def profile_runs(np_, traces, counts, ids=None, sched=(0, SCHED_LOCKSTEP), round_limit_log2=0, inbox_limit=0,
+                 profile=None):
+    """dsm_profile_runs (the host profile; no GPU): traces [n_sys, np, max_instr] u16, counts
+    [n_sys, np]; ids None: every system -> (node profiles NODE_PROFILE_DTYPE [n_ids, np], summary
+    PROFILE_DTYPE [1], results RESULT_DTYPE [n_ids]).  A summary passed in is accumulated into."""
+    traces = np.ascontiguousarray(traces, dtype=np.uint16)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    n_sys, _, stride = traces.shape
+    assert traces.shape[1] == np_ and counts.shape == (n_sys, np_)
+    if ids is not None:
+        ids = np.ascontiguousarray(ids, dtype=np.uint64)
+    n = n_sys if ids is None else len(ids)
+    recs = np.zeros((n, np_), dtype=NODE_PROFILE_DTYPE)
+    if profile is None:
+        profile = np.zeros(1, dtype=PROFILE_DTYPE)
+    assert profile.dtype == PROFILE_DTYPE and profile.size == 1 and profile.flags.c_contiguous
+    res = np.zeros(n, dtype=RESULT_DTYPE)
+    opts = EventOpts(sched[0], sched[1], round_limit_log2, inbox_limit)
+    _check(lib().dsm_profile_runs(np_, _ptr(traces), _ptr(counts), stride, n_sys, _ptr(ids), n, ctypes.byref(opts),
+                                  _ptr(recs), _ptr(profile), _ptr(res)), "dsm_profile_runs")
+    return recs, profile, res
+
+
+def profile_merge(dst, src):
+    """dsm_profile_merge: dst += src (PROFILE_DTYPE arrays of one element); returns dst."""
+    assert dst.dtype == PROFILE_DTYPE and dst.size == 1 and dst.flags.c_contiguous
+    src = np.ascontiguousarray(src, dtype=PROFILE_DTYPE).reshape(1)
+    _check(lib().dsm_profile_merge(_ptr(dst), _ptr(src)), "dsm_profile_merge")
+    return dst
+
+
+def profile_to_dict(p, top=8):
+    """A dsm_profile (PROFILE_DTYPE record or NPROFILE uint64) as a dict: the 16 totals by name,
+    accesses, hits and the hit ratio, misses by cause, mean and maximum latency of the completed
+    transactions, the latency histogram, and the `top` addresses by misses and by coherence misses
+    as (address, count), commonest first, ties by address."""
+    v = [int(x) for x in np.ascontiguousarray(p).view(np.uint64).reshape(-1)]
+    assert len(v) == NPROFILE
+    t = dict(zip(PROFILE_FIELDS, v[:16]))
+    hits = t["rd_hit"] + t["wr_hit"] + t["wr_upgrade"]
+    cause = {c: t["rd_miss_" + c] + t["wr_miss_" + c] for c in ("cold", "conflict", "coherence")}
+    accesses = hits + sum(cause.values())
+    ranked = lambda h: [(a, h[a]) for a in sorted(range(128), key=lambda a: (-h[a], a)) if h[a]][:top]
+    return {"systems": v[16], "totals": t, "accesses": accesses, "hits": hits,
+            "hit_ratio": hits / accesses if accesses else 0.0, "misses": cause,
+            "replacements": t["repl_clean"] + t["repl_dirty"], "txns": t["txns"], "open": t["open_since"],
+            "mean_latency": t["wait_rounds"] / t["txns"] if t["txns"] else 0.0, "max_latency": t["max_wait"],
+            "latency": v[32:96], "top_miss": ranked(v[96:224]), "top_coherence": ranked(v[224:352])}
 
 
 # -- exhaustive exploration (ABI 5 +reach) ----------------------------------------------------
@@ -1139,6 +1211,47 @@ class Engine:
         torch.cuda.synchronize(dev)
         ev = d_ev.cpu().numpy().view(np.uint64)[:n * cap].reshape(n, cap) if cap else None
         return (ev, d_n.cpu().numpy().view(np.uint32)[:n], d_h.cpu().numpy().view(np.uint64)[:n],
+                d_res.cpu().numpy().view(RESULT_DTYPE)[:n])
+
+    def profile_device(self, d_traces, d_counts, n_sys, d_ids, n_ids, d_node_profiles, d_profile, d_results,
+                       stream=0):
+        """dsm_profile_runs_device: pointers or tensors; each output may be None; d_profile
+        (NPROFILE uint64) is accumulated into."""
+        _check(lib().dsm_profile_runs_device(self.ctx, _dptr(d_traces), _dptr(d_counts), n_sys,
+                                             _dptr(d_ids, 8 * n_ids), n_ids,
+                                             _dptr(d_node_profiles, 64 * self.np * n_ids),
+                                             _dptr(d_profile, 8 * NPROFILE), _dptr(d_results, 32 * n_ids),
+                                             ctypes.c_void_p(stream)), "dsm_profile_runs_device")
+
+    def profile(self, traces, counts, ids=None):
+        """Profile systems `ids` (None: all) of a packed ensemble on the GPU under the engine's
+        schedule, round limit and inbox limit -> (node profiles NODE_PROFILE_DTYPE [n_ids, np], the
+        summary as profile_to_dict gives it, with the raw PROFILE_DTYPE record under "raw", results
+        RESULT_DTYPE [n_ids])."""
+        import torch
+        traces = np.ascontiguousarray(traces, dtype=np.uint16)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        n_sys = counts.shape[0]
+        assert traces.shape == (n_sys, self.np, self.max_instr), traces.shape
+        assert counts.shape == (n_sys, self.np)
+        dev = torch.device("cuda", self.device)
+        d_tr = torch.from_numpy(traces.view(np.int16).reshape(-1)).to(dev)
+        d_cn = torch.from_numpy(counts.view(np.int32).reshape(-1)).to(dev)
+        d_ids = None
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, dtype=np.uint64)
+            d_ids = torch.from_numpy(ids.view(np.int64)).to(dev)
+        n = n_sys if ids is None else len(ids)
+        d_np = torch.zeros(8 * self.np * max(n, 1), dtype=torch.int64, device=dev)
+        d_pf = torch.zeros(NPROFILE, dtype=torch.int64, device=dev)
+        d_res = torch.zeros(4 * max(n, 1), dtype=torch.int64, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        self.profile_device(d_tr, d_cn, n_sys, d_ids, n, d_np, d_pf, d_res, st)
+        torch.cuda.synchronize(dev)
+        raw = d_pf.cpu().numpy().view(PROFILE_DTYPE)
+        summary = profile_to_dict(raw)
+        summary["raw"] = raw
+        return (d_np.cpu().numpy().view(NODE_PROFILE_DTYPE)[:n * self.np].reshape(n, self.np), summary,
                 d_res.cpu().numpy().view(RESULT_DTYPE)[:n])
 
     def reach_device(self, d_trace, d_counts, opts, info, d_parents, d_masks, d_fps, level_off, d_terminals,

@@ -64,7 +64,8 @@ extern "C" {
                              5 (+reach audit): additive -- the coherence of every reachable state
                                 (dsm_reach_audit*) likewise;
                              5 (+reach batch audit): additive -- that audit for a whole ensemble
-                                in one asynchronous launch (dsm_reach_batch_audit*) likewise */
+                                in one asynchronous launch (dsm_reach_batch_audit*) likewise;
+                             5 (+profile): additive -- the access profile (dsm_profile_*) likewise */
 
 #define DSM_MAX_NP 8             /* bitVector is one byte (README.md:51)                  */
 #define DSM_CACHE_SIZE 4         /* CACHE_SIZE      assignment.c:10                        */
@@ -623,6 +624,97 @@ uint64_t dsm_event_trace_hash(const uint64_t *events, uint64_t n);
  * or both, interleaved in event order); an ACCESS write hit on SHARED prints :637 and then :648.
  * Returns the length, or DSM_E_INVAL if cap is too small (host only). */
 int dsm_format_event_trace(const uint64_t *events, uint64_t n, int what, char *buf, size_t cap);
+
+/* ---- access profile: hits, misses by cause and miss latency ------------------------------- *
+ * The event trace says what one system did, line by line; the access profile counts it, for a
+ * whole ensemble, on the device: how often a node hit, why it missed, how long a miss kept it
+ * waiting, and which addresses are the hot ones.  A kernel of its own (one system per lane, the
+ * replay's round loop with a counting log) re-runs chosen systems of a packed ensemble under the
+ * ctx's schedule, round limit and inbox limit; the engine kernels are untouched and the profile's
+ * results are the engine's.
+ *
+ * All definitions refer to a node's record (dsm_node_state) before and after an action.
+ *
+ *   access       an issued instruction (op, a) of node n whose action does not assert, classified
+ *                by the line L = cache[a & 3] of n's record BEFORE the action:
+ *                  hit             L.address == a && L.state != INVALID (assignment.c:608, :635):
+ *                                  a read hit; a write hit on MODIFIED or EXCLUSIVE; a write hit on
+ *                                  SHARED, which is an upgrade (:646)
+ *                  coherence miss  L.address == a && L.state == INVALID: the tag is still there
+ *                                  and somebody else took the line
+ *                  cold miss       not a coherence miss, and n has had no counted access to a
+ *                                  before in this run
+ *                  conflict miss   any other miss
+ *                An issue whose action asserts (an instruction whose home is >= np among them) is
+ *                counted nowhere and does not mark a as seen: the event trace's rule.
+ *   replacement  the access called handleCacheReplacement on a valid line (:616, :670; the
+ *                REPLACE event of an issuing action): clean when the line was SHARED or EXCLUSIVE
+ *                (EVICT_SHARED), dirty when it was MODIFIED (EVICT_MODIFIED)
+ *   transaction  a node's transaction opens in the round r0 in which an action takes its record's
+ *                waiting flag from 0 to 1 and completes in the round r1 in which an action takes
+ *                it from 1 to 0; its latency is r1 - r0 rounds.  Rounds are counted as the
+ *                result's `rounds` counts them, from 1, under whatever schedule is set.  A
+ *                transaction still open when the run ends never completes.  (No action that
+ *                asserts changes the flag.)
+ *
+ * Per node, dsm_node_profile: 16 x uint32.  Per ensemble, dsm_profile: DSM_NPROFILE x uint64, all
+ * sums but one maximum, so the summaries of shards and batches merge (dsm_profile_merge) and every
+ * device update is a commutative atomic.
+ *
+ * For a system that did not assert: fields 0..8 summed over its nodes equal result.instrs; field
+ * 15 summed equals result.msgs; the latency histogram sums to field 11. */
+typedef struct dsm_node_profile {
+    uint32_t rd_hit;              /*  0                                                          */
+    uint32_t rd_miss_cold;        /*  1                                                          */
+    uint32_t rd_miss_conflict;    /*  2                                                          */
+    uint32_t rd_miss_coherence;   /*  3                                                          */
+    uint32_t wr_hit;              /*  4  on MODIFIED or EXCLUSIVE                                */
+    uint32_t wr_upgrade;          /*  5  on SHARED                                               */
+    uint32_t wr_miss_cold;        /*  6                                                          */
+    uint32_t wr_miss_conflict;    /*  7                                                          */
+    uint32_t wr_miss_coherence;   /*  8                                                          */
+    uint32_t repl_clean;          /*  9                                                          */
+    uint32_t repl_dirty;          /* 10                                                          */
+    uint32_t txns;                /* 11  completed transactions                                  */
+    uint32_t wait_rounds;         /* 12  the sum of their latencies                              */
+    uint32_t max_wait;            /* 13  the longest of them                                     */
+    uint32_t open_since;          /* 14  r0 of the transaction still open at the end, 0: none    */
+    uint32_t recv;                /* 15  messages the node handled                               */
+} dsm_node_profile;
+#define DSM_NPROFILE 352
+typedef struct dsm_profile {
+    uint64_t total[16];           /* per field, the sum over all nodes of all profiled systems;
+                                   * but [13] is the maximum, and [14] the number of nodes whose
+                                   * transaction is still open                                   */
+    uint64_t systems;             /* systems profiled                                            */
+    uint64_t reserved[15];        /* zero                                                        */
+    uint64_t latency[64];         /* completed transactions by latency, bucket min(latency, 63)  */
+    uint64_t miss_addr[128];      /* misses of any cause, read and write, upgrades excluded, by
+                                   * address                                                     */
+    uint64_t coh_addr[128];       /* coherence misses by address                                 */
+} dsm_profile;
+/* Profile systems d_ids[0 .. n_ids) (NULL: 0 .. n_ids-1) of a packed ensemble of n_sys systems
+ * (layout, ids and settings as dsm_trace_events_device).  d_node_profiles is [n_ids][np] records
+ * (16-byte aligned); d_profile is ACCUMULATED into (zero it first for one run); d_results is the
+ * engine's result of every system under the same settings, bit for bit.  Each output may be NULL.
+ * An id >= n_sys is not run and nothing is read for it: records zero, result all ones, not counted
+ * in the summary.  The lanes' state lives in a ctx-owned scratch sized by the lanes in flight (at
+ * most DSM_EVENTS_MAX_LANES), allocated at the first call and freed by dsm_close.  Asynchronous on
+ * `stream`; n_ids == 0 is a no-op. */
+int dsm_profile_runs_device(dsm_ctx *ctx, const uint16_t *d_traces, const uint32_t *d_counts,
+                            uint64_t n_sys, const uint64_t *d_ids, uint64_t n_ids,
+                            dsm_node_profile *d_node_profiles, dsm_profile *d_profile,
+                            dsm_sys_result *d_results, void *stream);
+/* the same on the host (no GPU needed): the plain reference.  traces [n_sys][np][max_instr];
+ * opts NULL: lock-step, no limits; profile is accumulated into as well.  An id >= n_sys is
+ * DSM_E_INVAL. */
+int dsm_profile_runs(int np, const uint16_t *traces, const uint32_t *counts, uint32_t max_instr,
+                     uint64_t n_sys, const uint64_t *ids, uint64_t n_ids, const dsm_event_opts *opts,
+                     dsm_node_profile *node_profiles, dsm_profile *profile, dsm_sys_result *results);
+/* dst += src: sums, and the maximum for total[13] (host only) */
+int dsm_profile_merge(dsm_profile *dst, const dsm_profile *src);
+/* "rd_hit" .. "recv" for fields 0..15, NULL for any other index (host only) */
+const char *dsm_profile_field_name(int i);
 
 /* ---- exhaustive exploration: every outcome the schedule model can reach ------------------- *
  * dsm_set_schedule samples interleavings; this is their closure: the graph of every state ONE
