@@ -175,6 +175,23 @@
  *                        screened N tests: D can deadlock, I can end incoherent, X exhaustive
  *                    and the exit code 2 when D > 0 or I > 0, else 3 when any search was truncated,
  *                    else 0.
+ *   --shrink deadlock|overflow|assert|end-incoherent|quiescent-incoherent
+ *                    the smallest test that keeps a reachable defect: every positional argument is
+ *                    a test directory, all read with one dsm_parse_traces call and all shrunk with
+ *                    one dsm_shrink_many_device call (instructions are deleted while the property
+ *                    stays reachable; include/dsm.h, "shrink").  Takes --shrink-classes NAME,...
+ *                    (the audit classes the two incoherent properties look for; default all),
+ *                    --reach-states (default 65536), --reach-depth, --reach-inbox and --shrink-out;
+ *                    any other mode flag is a usage error.  Per directory, in argument order:
+ *                        <dir>: shrink <property>: A -> B instructions, R rounds, C candidates, S states, <STATUS>
+ *                    With --shrink-out D every directory also gets D/<basename>/: core_<n>.txt,
+ *                    the shrunk test in the input files' own form; shrink.txt, the trail (a line
+ *                    per round) and per core the original line numbers of the surviving
+ *                    instructions; and, when the test has the property, schedule.txt, its shortest
+ *                    witness in the shrunk test (from dsm_reach_audit and dsm_reach_path on the
+ *                    host), one act mask per round as --reach writes it.  Exits 0 when every
+ *                    directory ended MINIMAL, else 3 when one ended MINIMAL_WITHIN_CAP or
+ *                    ROOT_UNKNOWN, else 1 (NOT_FOUND, TOO_LONG).
  */
 #include <errno.h>
 #include <stdio.h>
@@ -196,8 +213,11 @@ static void usage(const char *argv0) {
                     "          [--explore-dir DIR]\n"
                     "          [--explore-kind dumps|final] [--check DIR]] <test_directory>\n"
                     "       %s [--np 4|8] [--max-instr N] [--device D] [--quiet] --reach-batch | --reach-batch-audit [--reach-states N]\n"
-                    "          [--reach-depth D] [--reach-inbox L] [--explore-kind dumps|final] <test_directory>...\n",
-            argv0, argv0);
+                    "          [--reach-depth D] [--reach-inbox L] [--explore-kind dumps|final] <test_directory>...\n"
+                    "       %s [--np 4|8] [--max-instr N] [--device D] [--quiet]\n"
+                    "          --shrink deadlock|overflow|assert|end-incoherent|quiescent-incoherent [--shrink-classes NAME,...]\n"
+                    "          [--reach-states N] [--reach-depth D] [--reach-inbox L] [--shrink-out DIR] <test_directory>...\n",
+            argv0, argv0, argv0);
 }
 
 static const char *const status_names[5] = {"COMPLETED", "DEADLOCKED", "RING_OVERFLOW", "ASSERT_FAILED",
@@ -1054,8 +1074,187 @@ fail:
     return code;
 }
 
+/* --shrink-out: the shortest witness of `property` in one shrunk system (host search) to
+ * dir/schedule.txt, one act mask per round.  Returns DSM_OK or an error code. */
+static int write_shrink_witness(const char *dir, int np, const uint16_t *trace, const uint32_t *counts, uint32_t stride,
+                                const dsm_reach_opts *opts, const dsm_shrink_opts *so) {
+    const uint64_t cap = opts->max_states;
+    dsm_reach_info ri;
+    dsm_reach_audit_info ai;
+    uint32_t *par = (uint32_t *)malloc((size_t)cap * sizeof *par);
+    uint8_t *msk = (uint8_t *)malloc((size_t)cap), *path = (uint8_t *)malloc(DSM_REACH_MAX_LEVELS);
+    dsm_reach_terminal *term = (dsm_reach_terminal *)malloc((size_t)cap * sizeof *term);
+    uint64_t id = ~0ull, n = 0;
+    char file[600];
+    FILE *f = NULL;
+    int rc = DSM_E_NOMEM;
+    if (!par || !msk || !path || !term) goto done;
+    if ((rc = dsm_reach_audit(np, trace, counts, stride, opts, &ri, &ai, par, msk, NULL, term, cap, NULL, NULL, NULL))) goto done;
+    if (so->property <= DSM_SHRINK_ASSERT) {
+        const uint32_t want = so->property == DSM_SHRINK_DEADLOCK ? DSM_DEADLOCKED
+                            : so->property == DSM_SHRINK_OVERFLOW ? DSM_RING_OVERFLOW : DSM_ASSERT_FAILED;
+        for (uint64_t t = 0; t < ri.terminals && t < cap && id == ~0ull; ++t)       /* ascending ids: the shallowest first */
+            if ((term[t].res.status & 0xFFu) == want) id = term[t].state;
+    } else {
+        const dsm_audit *a = &ai.set[so->property == DSM_SHRINK_END_INCOHERENT ? DSM_RAUDIT_COMPLETED : DSM_RAUDIT_QUIESCENT];
+        const uint32_t m = so->class_mask ? so->class_mask : (1u << DSM_AUDIT_NCLASS) - 1u;
+        for (int b = 0; b < DSM_AUDIT_NCLASS; ++b)
+            if (((m >> b) & 1u) && a->by_class[b] && ~a->inv_first[b] < id) id = ~a->inv_first[b];
+    }
+    rc = DSM_E_STATE;
+    if (id == ~0ull) goto done;
+    if ((rc = dsm_reach_path(par, msk, id, path, DSM_REACH_MAX_LEVELS, &n))) goto done;
+    rc = DSM_E_IO;
+    snprintf(file, sizeof file, "%s/schedule.txt", dir);
+    if (!(f = fopen(file, "w"))) goto done;
+    for (uint64_t r = 0; r < n; ++r) fprintf(f, "%02x\n", path[r]);
+    if (fclose(f) == 0) rc = DSM_OK;
+done:
+    free(par); free(msk); free(path); free(term);
+    return rc;
+}
+
+/* --shrink: the tests of dirs read with one dsm_parse_traces call and shrunk with one
+ * dsm_shrink_many_device call; a line per test and, with out_dir, the shrunk tests.  Returns the
+ * process exit code. */
+static int shrink_dirs(int np, uint32_t max_instr, int device, char **dirs, int n_dirs, unsigned long long max_states,
+                       uint32_t max_depth, uint32_t inbox, const dsm_shrink_opts *so, const char *out_dir) {
+    const uint32_t stride = (max_instr + 7u) & ~7u;
+    const uint64_t n_files = (uint64_t)n_dirs * (uint64_t)np;
+    const size_t sys_cells = (size_t)np * stride;
+    const size_t tr_bytes = (size_t)n_files * stride * sizeof(uint16_t), cn_bytes = (size_t)n_files * sizeof(uint32_t);
+    const uint32_t trail_cap = DSM_SHRINK_MAX_ROUNDS;
+    char *text = NULL;
+    uint64_t *off = (uint64_t *)calloc((size_t)n_files + 1, sizeof(uint64_t));
+    uint16_t *traces = (uint16_t *)calloc((size_t)n_files * stride, sizeof(uint16_t)), *d_tr = NULL, *d_out = NULL, *d_orig = NULL;
+    uint16_t *out = (uint16_t *)calloc((size_t)n_files * stride, sizeof(uint16_t));
+    uint16_t *orig = (uint16_t *)calloc((size_t)n_files * stride, sizeof(uint16_t));
+    uint32_t *counts = (uint32_t *)calloc((size_t)n_files, sizeof(uint32_t)), *d_cn = NULL, *d_ocn = NULL;
+    uint32_t *ocn = (uint32_t *)calloc((size_t)n_files, sizeof(uint32_t));
+    int32_t *pst = (int32_t *)calloc((size_t)n_files, sizeof(int32_t));
+    dsm_shrink_info *info = (dsm_shrink_info *)calloc((size_t)n_dirs, sizeof *info);
+    dsm_shrink_step *trail = (dsm_shrink_step *)calloc((size_t)n_dirs * trail_cap, sizeof *trail);
+    dsm_ctx *ctx = NULL;
+    dsm_reach_opts opts;
+    dsm_config cfg;
+    int rc = DSM_OK, code = EXIT_FAILURE;
+    const char *what = "out of memory";
+    if (!off || !traces || !out || !orig || !counts || !ocn || !pst || !info || !trail) goto fail;
+    for (uint64_t f = 0; f < n_files; ++f) {
+        uint64_t len = off[f];
+        if (append_core_file(dirs[f / (uint64_t)np], (int)(f % (uint64_t)np), &text, &len)) goto fail;
+        off[f + 1] = len;
+    }
+    memset(&cfg, 0, sizeof cfg);
+    cfg.np = np;
+    cfg.max_instr = stride;
+    what = "dsm_open";
+    if ((rc = dsm_open(device, &cfg, &ctx))) goto fail;
+    what = "dsm_parse_traces";
+    if ((rc = dsm_parse_traces(ctx, text ? text : "", off, n_files, max_instr, traces, counts, pst))) goto fail;
+    for (uint64_t f = 0; f < n_files; ++f) {
+        if (pst[f]) {
+            fprintf(stderr, "Error: tests/%s/core_%d.txt: %s (instruction %u)\n", dirs[f / (uint64_t)np], (int)(f % (uint64_t)np),
+                    dsm_strerror(pst[f]), counts[f]);
+            what = NULL;
+            rc = DSM_OK;
+            goto fail;
+        }
+    }
+    memset(&opts, 0, sizeof opts);
+    opts.inbox_limit = inbox; opts.kind = DSM_CENSUS_DUMPS; opts.max_states = max_states; opts.max_depth = max_depth;
+    what = "device memory";
+    rc = DSM_OK;
+    if (hipMalloc((void **)&d_tr, tr_bytes) != hipSuccess || hipMalloc((void **)&d_cn, cn_bytes) != hipSuccess ||
+        hipMalloc((void **)&d_out, tr_bytes) != hipSuccess || hipMalloc((void **)&d_orig, tr_bytes) != hipSuccess ||
+        hipMalloc((void **)&d_ocn, cn_bytes) != hipSuccess ||
+        hipMemcpy(d_tr, traces, tr_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_cn, counts, cn_bytes, hipMemcpyHostToDevice) != hipSuccess)
+        goto fail;
+    what = "dsm_shrink_many_device";
+    if ((rc = dsm_shrink_many_device(ctx, d_tr, d_cn, (uint64_t)n_dirs, &opts, so, 0, d_out, d_ocn, d_orig, info, trail, trail_cap,
+                                     NULL)))
+        goto fail;
+    what = "read-back";
+    if (hipMemcpy(out, d_out, tr_bytes, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(orig, d_orig, tr_bytes, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(ocn, d_ocn, cn_bytes, hipMemcpyDeviceToHost) != hipSuccess)
+        goto fail;
+    int n_cap = 0, n_miss = 0;
+    for (int s = 0; s < n_dirs; ++s) {
+        const dsm_shrink_info *si = &info[s];
+        printf("%s: shrink %s: %u -> %u instructions, %u rounds, %llu candidates, %llu states, %s\n", dirs[s],
+               dsm_shrink_property_name((int)so->property), si->instrs_in, si->instrs_out, si->rounds,
+               (unsigned long long)si->candidates, (unsigned long long)si->states, dsm_shrink_status_name((int)si->status));
+        n_cap += si->status == DSM_SHRINK_MINIMAL_WITHIN_CAP || si->status == DSM_SHRINK_ROOT_UNKNOWN;
+        n_miss += si->status == DSM_SHRINK_NOT_FOUND || si->status == DSM_SHRINK_TOO_LONG;
+        if (!out_dir) continue;
+        char dir[512], file[600];
+        const char *base = strrchr(dirs[s], '/');
+        base = base ? base + 1 : dirs[s];
+        what = "--shrink-out";
+        rc = DSM_E_IO;
+        if ((mkdir(out_dir, 0777) != 0 && errno != EEXIST) ||
+            snprintf(dir, sizeof dir, "%s/%s", out_dir, base) >= (int)sizeof dir || (mkdir(dir, 0777) != 0 && errno != EEXIST))
+            goto fail;
+        const uint16_t *tr = out + (size_t)s * sys_cells, *og = orig + (size_t)s * sys_cells;
+        const uint32_t *cn = ocn + (size_t)s * (size_t)np;
+        for (int c = 0; c < np; ++c) {
+            snprintf(file, sizeof file, "%s/core_%d.txt", dir, c);
+            FILE *f = fopen(file, "w");
+            if (!f) goto fail;
+            for (uint32_t i = 0; i < cn[c]; ++i) {       /* the packed word: bit 15 WR, bits 8-14 the address, bits 0-7 the value */
+                const uint32_t w = tr[(size_t)c * stride + i];
+                if (w >> 15) fprintf(f, "WR 0x%02X %u\n", (w >> 8) & 0x7Fu, w & 0xFFu);
+                else fprintf(f, "RD 0x%02X\n", (w >> 8) & 0x7Fu);
+            }
+            if (fclose(f) != 0) goto fail;
+        }
+        snprintf(file, sizeof file, "%s/shrink.txt", dir);
+        FILE *f = fopen(file, "w");
+        if (!f) goto fail;
+        fprintf(f, "shrink %s: %u -> %u instructions, %u rounds, %llu candidates, %llu states, %s\n",
+                dsm_shrink_property_name((int)so->property), si->instrs_in, si->instrs_out, si->rounds,
+                (unsigned long long)si->candidates, (unsigned long long)si->states, dsm_shrink_status_name((int)si->status));
+        for (uint32_t r = 0; r < si->rounds && r < trail_cap; ++r) {
+            const dsm_shrink_step *t = &trail[(size_t)s * trail_cap + r];
+            fprintf(f, "round %u: g %u candidates %u found %u unknown %u states %llu", r + 1, t->g, t->n_cand, t->n_found,
+                    t->n_unknown, (unsigned long long)t->states);
+            if (t->core != ~0u) fprintf(f, " deleted core %u [%u, %u)\n", t->core, t->start, t->start + t->len);
+            else fprintf(f, " deleted nothing\n");
+        }
+        for (int c = 0; c < np; ++c) {
+            fprintf(f, "core %d lines:", c);
+            for (uint32_t i = 0; i < cn[c]; ++i) fprintf(f, " %u", (unsigned)og[(size_t)c * stride + i] + 1u);
+            fprintf(f, "\n");
+        }
+        if (fclose(f) != 0) goto fail;
+        if (si->status == DSM_SHRINK_MINIMAL || si->status == DSM_SHRINK_MINIMAL_WITHIN_CAP) {
+            what = "witness";
+            if ((rc = write_shrink_witness(dir, np, tr, cn, stride, &opts, so))) goto fail;
+        }
+        rc = DSM_OK;
+    }
+    code = n_cap ? 3 : n_miss ? EXIT_FAILURE : 0;
+    what = NULL;
+    rc = DSM_OK;
+fail:
+    if (what) fprintf(stderr, "Error: shrink: %s%s%s\n", what, rc ? ": " : "", rc ? dsm_strerror(rc) : "");
+    if (d_tr) (void)hipFree(d_tr);
+    if (d_cn) (void)hipFree(d_cn);
+    if (d_out) (void)hipFree(d_out);
+    if (d_orig) (void)hipFree(d_orig);
+    if (d_ocn) (void)hipFree(d_ocn);
+    if (ctx) dsm_close(ctx);
+    free(text); free(off); free(traces); free(out); free(orig); free(counts); free(ocn); free(pst); free(info); free(trail);
+    return code;
+}
+
 int main(int argc, char **argv) {
     int np = 4, device = 0, quiet = 0, audit = 0, do_reach = 0, do_batch = 0, batch_audit = 0, n_dirs = 0, states_set = 0;
+    int shrink_prop = -1, shrink_classes = 0;
+    const char *shrink_out = NULL;
+    dsm_shrink_opts shrink_opts;
     long long reach_states = 1ll << 22, reach_depth = 0, reach_inbox = 16;
     int reach_opts = 0;
     uint32_t prob_t[DSM_DIST_MAX_THRESH], n_prob = 0;
@@ -1088,6 +1287,27 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--reach")) do_reach = 1;
         else if (!strcmp(argv[i], "--reach-batch")) do_batch = 1;
         else if (!strcmp(argv[i], "--reach-batch-audit")) do_batch = batch_audit = 1;
+        else if (!strcmp(argv[i], "--shrink") && i + 1 < argc) {
+            const char *v = argv[++i];
+            shrink_prop = -1;
+            for (int k = 0; k < DSM_SHRINK_NPROPERTY; ++k)
+                if (!strcmp(v, dsm_shrink_property_name(k))) shrink_prop = k;
+            if (shrink_prop < 0) { usage(argv[0]); return EXIT_FAILURE; }
+        }
+        else if (!strcmp(argv[i], "--shrink-classes") && i + 1 < argc) {
+            const char *v = argv[++i];
+            for (shrink_classes = 0;;) {
+                const size_t len = strcspn(v, ",");
+                int bit = -1;
+                for (int b = 0; b < DSM_AUDIT_NCLASS; ++b)
+                    if (strlen(dsm_audit_class_name(b)) == len && !strncmp(v, dsm_audit_class_name(b), len)) bit = b;
+                if (bit < 0) { usage(argv[0]); return EXIT_FAILURE; }
+                shrink_classes |= 1 << bit;
+                if (v[len] == '\0') break;
+                v += len + 1;
+            }
+        }
+        else if (!strcmp(argv[i], "--shrink-out") && i + 1 < argc) shrink_out = argv[++i];
         else if (!strcmp(argv[i], "--reach-states") && i + 1 < argc) { reach_states = atoll(argv[++i]); reach_opts = states_set = 1; }
         else if (!strcmp(argv[i], "--reach-depth") && i + 1 < argc) { reach_depth = atoll(argv[++i]); reach_opts = 1; }
         else if (!strcmp(argv[i], "--reach-inbox") && i + 1 < argc) { reach_inbox = atoll(argv[++i]); reach_opts = 1; }
@@ -1144,6 +1364,22 @@ int main(int argc, char **argv) {
     if ((np != 4 && np != 8) || max_instr == 0 || max_instr > DSM_MAX_INSTR) {
         usage(argv[0]);
         return EXIT_FAILURE;
+    }
+    if (shrink_prop < 0 && (shrink_classes || shrink_out)) { usage(argv[0]); return EXIT_FAILURE; }
+    if (shrink_prop >= 0) {
+        if (!states_set) reach_states = 1ll << 16;
+        if (do_batch || do_reach || explore_n || have_sched || events_file || events_opts || issue_file || audit || profile ||
+            explore_opts || n_prob || fate_name || reach_states < 1 || reach_states > (long long)DSM_REACH_BATCH_MAX_STATES ||
+            reach_depth < 0 || reach_depth >= (long long)DSM_REACH_MAX_LEVELS || reach_inbox < 1 || reach_inbox > 16 ||
+            (shrink_classes && shrink_prop < DSM_SHRINK_END_INCOHERENT) || (shrink_out && !*shrink_out)) {
+            usage(argv[0]);
+            return EXIT_FAILURE;
+        }
+        memset(&shrink_opts, 0, sizeof shrink_opts);
+        shrink_opts.property = (uint32_t)shrink_prop;
+        shrink_opts.class_mask = (uint32_t)shrink_classes;
+        return shrink_dirs(np, max_instr, device, argv + 1, n_dirs, (unsigned long long)reach_states, (uint32_t)reach_depth,
+                           (uint32_t)reach_inbox, &shrink_opts, shrink_out);
     }
     if (do_batch) {
         if (!states_set) reach_states = 1ll << 16;

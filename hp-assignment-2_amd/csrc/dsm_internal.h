@@ -17,9 +17,11 @@
  *                    one asynchronous launch; its host loop
  *   dsm_raudit.hip   reach audit: the coherence audit word of every state of the reach graph, one
  *                    lane per state over the rebuilt store; its host reference
- * The last six replay ONE system a round at a time: the round is dsm_step.h's st_round, once,
+ *   dsm_shrink.hip   test shrinker: the rounds of candidates over the reach batch audit (plan, build
+ *                    and pick kernels; the rule is dsm_shrink.h's), its host loop
+ * The six before it replay ONE system a round at a time: the round is dsm_step.h's st_round, once,
  * under dsm_events.h's and dsm_reach.h's inbox and log policies, and the hashes are dsm_hash.h's.
- * The last five are the reach family.  dsm_reach.h holds the search's state and the rules of a
+ * The last five of those are the reach family.  dsm_reach.h holds the search's state and the rules of a
  * level (host and device), dsm_reach_dev.h the device plumbing all five share: the successor of a
  * level, the visited table's protocol of the two searches, the np dispatch of the entry points.
  * dsm_dist_dev.h is the edge list (its kernels and its host twin) of dsm_dist.hip and dsm_fate.hip;
@@ -188,6 +190,16 @@ extern "C" int dsm_debug_raudit_lane(int np, const uint32_t *state, uint32_t cls
  * cand[i * cs + j], words words each.  DSM_E_INVAL where j, or the candidate a pending meta names,
  * is not below cs. */
 extern "C" int dsm_debug_visit_resolve(uint64_t meta, uint64_t j, const uint32_t *cand, uint64_t cs, uint32_t words);
+
+/* Test-only (not part of the ABI): dsm_shrink.h's shrink_verdict on the host -- the verdict
+ * (DSM_SHRINK_ABSENT, _FOUND, _UNKNOWN) of one searched system from its two rows, the function the
+ * host loop and shrink_pick_kernel both compile.  DSM_E_INVAL (negative) for a NULL row or bad sopts. */
+extern "C" int dsm_debug_shrink_verdict(const dsm_reach_info *info, const dsm_reach_audit_info *ainfo,
+                                        const dsm_shrink_opts *sopts);
+/* Measurement-only view of the last dsm_shrink_many_device call that ran with DSM_SHRINK_TIMING=1 in
+ * the environment (tools/shrink_time.py): milliseconds on the stream per phase -- plan (with its
+ * scan and the read-back), build, search, pick -- and the rounds of the last call, timed or not. */
+extern "C" int dsm_debug_shrink_times(double *ms, uint64_t *rounds);
 
 /* Measurement-only view of the last dsm_reach_batch_device call (not part of the ABI;
  * tools/reach_batch_time.py): the systems it kept in flight and the bytes of the ctx's scratch. */

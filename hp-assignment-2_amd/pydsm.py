@@ -88,6 +88,10 @@ class FateOpts(ctypes.Structure):
     _fields_ = [("status_mask", ctypes.c_uint32), ("max_sweeps", ctypes.c_uint32), ("key", ctypes.c_uint64)]
 
 
+class ShrinkOpts(ctypes.Structure):
+    _fields_ = [("property", ctypes.c_uint32), ("class_mask", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 2)]
+
+
 RESUME_FORMS = {0: "none", 1: "lock-step", 2: "serial", 3: "fast-forward lock-step"}
 
 
@@ -217,7 +221,20 @@ def lib():
                                       vp]),
             "dsm_reach_audit_device": (i32, [vp, vp, vp, ctypes.POINTER(ReachOpts), vp, vp, vp, vp, vp, vp, u64, vp, vp,
                                              vp, vp]),
+            # ABI 5 (+shrink): the test shrinker
+            "dsm_shrink_many": (i32, [i32, vp, vp, u32, u64, ctypes.POINTER(ReachOpts), ctypes.POINTER(ShrinkOpts), vp, vp, vp,
+                                      vp, vp, u32]),
+            "dsm_shrink_many_device": (i32, [vp, vp, vp, u64, ctypes.POINTER(ReachOpts), ctypes.POINTER(ShrinkOpts), u64, vp,
+                                             vp, vp, vp, vp, u32, vp]),
+            "dsm_shrink": (i32, [i32, vp, vp, u32, ctypes.POINTER(ReachOpts), ctypes.POINTER(ShrinkOpts), vp, vp, vp, vp, vp,
+                                 u32]),
+            "dsm_shrink_device": (i32, [vp, vp, vp, ctypes.POINTER(ReachOpts), ctypes.POINTER(ShrinkOpts), u64, vp, vp, vp, vp,
+                                        vp, u32, vp]),
+            "dsm_shrink_status_name": (ctypes.c_char_p, [i32]),
+            "dsm_shrink_property_name": (ctypes.c_char_p, [i32]),
             # test-only (csrc/dsm_internal.h, not in include/dsm.h)
+            "dsm_debug_shrink_verdict": (i32, [vp, vp, ctypes.POINTER(ShrinkOpts)]),
+            "dsm_debug_shrink_times": (i32, [vp, ctypes.POINTER(u64)]),
             "dsm_debug_raudit_times": (i32, [vp, ctypes.POINTER(u64)]),
             "dsm_debug_raudit_lane": (i32, [i32, vp, u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]),
             "dsm_debug_visit_resolve": (i32, [u64, u64, vp, u64, u32]),
@@ -984,6 +1001,102 @@ def reach_audit_many(np_, traces, counts, inbox_limit=16, kind=CENSUS_DUMPS, max
     return _reach_audit_many_result(info, ainfo, terms[:n * term_cap], term_cap, parents, masks, words, sets, term_words, cap)
 
 
+# -- shrink (ABI 5 +shrink) --------------------------------------------------------------------
+SHRINK_DEADLOCK, SHRINK_OVERFLOW, SHRINK_ASSERT, SHRINK_END_INCOHERENT, SHRINK_QUIESCENT_INCOHERENT = range(5)
+SHRINK_PROPERTIES = {"deadlock": 0, "overflow": 1, "assert": 2, "end-incoherent": 3, "quiescent-incoherent": 4}
+SHRINK_ABSENT, SHRINK_FOUND, SHRINK_UNKNOWN = 0, 1, 2
+SHRINK_MINIMAL, SHRINK_MINIMAL_WITHIN_CAP, SHRINK_NOT_FOUND, SHRINK_ROOT_UNKNOWN, SHRINK_TOO_LONG = range(5)
+SHRINK_STATUS_NAMES = ["MINIMAL", "MINIMAL_WITHIN_CAP", "NOT_FOUND", "ROOT_UNKNOWN", "TOO_LONG"]
+SHRINK_MAX_INSTRS = 64                       # DSM_SHRINK_MAX_INSTRS
+SHRINK_MAX_ROUNDS = 80                       # DSM_SHRINK_MAX_ROUNDS
+SHRINK_NO_CORE = 0xFFFFFFFF                  # dsm_shrink_step.core of a round that accepted nothing
+SHRINK_STEP_DTYPE = np.dtype([("g", "<u4"), ("n_cand", "<u4"), ("n_found", "<u4"), ("n_unknown", "<u4"), ("core", "<u4"),
+                              ("start", "<u4"), ("len", "<u4"), ("reserved", "<u4"), ("states", "<u8")])
+SHRINK_INFO_DTYPE = np.dtype([("status", "<u4"), ("rounds", "<u4"), ("instrs_in", "<u4"), ("instrs_out", "<u4"),
+                              ("accepted", "<u4"), ("reserved0", "<u4"), ("candidates", "<u8"), ("unknown", "<u8"),
+                              ("states", "<u8"), ("root_states", "<u8"), ("root_flags", "<u8"), ("reserved", "<u8", (2,))])
+assert SHRINK_STEP_DTYPE.itemsize == 40 and SHRINK_INFO_DTYPE.itemsize == 80
+
+
+def shrink_opts(property, classes=None):
+    """A ShrinkOpts from a property (a SHRINK_* value or its name) and classes (None: all; a mask,
+    or an iterable of audit class names or bits)."""
+    prop = SHRINK_PROPERTIES.get(property, property)
+    if classes is None:
+        mask = 0
+    elif isinstance(classes, int):
+        mask = classes
+    else:
+        mask = 0
+        for c in classes:
+            mask |= 1 << (AUDIT_CLASS_NAMES.index(c) if isinstance(c, str) else c)
+    return ShrinkOpts(prop, mask)
+
+
+def shrink_verdict(info, ainfo, property, classes=None):
+    """dsm_debug_shrink_verdict: the verdict (SHRINK_ABSENT, _FOUND, _UNKNOWN) of one searched
+    system from its REACH_INFO_DTYPE and RAUDIT_INFO_DTYPE rows."""
+    info = np.ascontiguousarray(info).reshape(-1).view(np.uint8)
+    ainfo = np.ascontiguousarray(ainfo).reshape(-1).view(np.uint8)
+    assert info.nbytes == REACH_INFO_DTYPE.itemsize and ainfo.nbytes == RAUDIT_INFO_DTYPE.itemsize
+    so = shrink_opts(property, classes)
+    rc = lib().dsm_debug_shrink_verdict(_ptr(info), _ptr(ainfo), ctypes.byref(so))
+    _check(min(rc, 0), "dsm_debug_shrink_verdict")
+    return rc
+
+
+def _shrink_result(traces, counts, orig, info, trail, trail_cap):
+    n = len(info)
+    tr = trail.reshape(n, trail_cap) if trail_cap else trail.reshape(n, 0)
+    return {"traces": traces, "counts": counts, "orig": orig, "info": info,
+            "trail": [tr[s, :min(trail_cap, int(info["rounds"][s]))] for s in range(n)],
+            "status": [SHRINK_STATUS_NAMES[int(x)] if int(x) < len(SHRINK_STATUS_NAMES) else None for x in info["status"]]}
+
+
+def shrink_many(np_, traces, counts, property, classes=None, inbox_limit=16, kind=CENSUS_DUMPS, max_states=1 << 16,
+                max_depth=0, trail_cap=SHRINK_MAX_ROUNDS):
+    """dsm_shrink_many (the host reference; no GPU): every system of traces [n, np, stride] u16,
+    counts [n, np] shrunk to a test of which no single instruction can be deleted without losing
+    `property` -> a dict: traces, counts, orig (uint16 [n, np, stride]: where each surviving
+    instruction was in the input; 0xFFFF after the count), info (SHRINK_INFO_DTYPE [n]), trail (a
+    list per system: SHRINK_STEP_DTYPE, one per round) and status (the names)."""
+    traces = np.ascontiguousarray(traces, dtype=np.uint16)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    assert traces.ndim == 3 and traces.shape[1] == np_ and counts.shape == traces.shape[:2]
+    n = traces.shape[0]
+    opts = ReachOpts(inbox_limit, CENSUS_KINDS.get(kind, kind), max_states, max_depth, 0)
+    so = shrink_opts(property, classes)
+    out_t, out_c = np.zeros_like(traces), np.zeros_like(counts)
+    orig = np.zeros_like(traces)
+    info = np.zeros(n, dtype=SHRINK_INFO_DTYPE)
+    trail = np.zeros(max(n * trail_cap, 1), dtype=SHRINK_STEP_DTYPE)
+    _check(lib().dsm_shrink_many(np_, _ptr(traces), _ptr(counts), traces.shape[2], n, ctypes.byref(opts), ctypes.byref(so),
+                                 _ptr(out_t), _ptr(out_c), _ptr(orig), _ptr(info), _ptr(trail), trail_cap), "dsm_shrink_many")
+    return _shrink_result(out_t, out_c, orig, info, trail[:n * trail_cap], trail_cap)
+
+
+def _shrink_first(r):
+    return {k: v[0] for k, v in r.items()}
+
+
+def shrink(np_, traces, counts, property, classes=None, **kw):
+    """shrink_many of ONE system (traces [np, stride], counts [np]) -> the same dict, unstacked."""
+    traces = np.ascontiguousarray(traces, dtype=np.uint16)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+    assert traces.ndim == 2
+    return _shrink_first(shrink_many(np_, traces[None], counts[None], property, classes, **kw))
+
+
+def shrink_status_name(status):
+    s = lib().dsm_shrink_status_name(status)
+    return s.decode() if s else None
+
+
+def shrink_property_name(prop):
+    s = lib().dsm_shrink_property_name(prop)
+    return s.decode() if s else None
+
+
 def _reach_terminals_result(info, terms, kind):
     d = reach_info_to_dict(info)
     nt = min(d["terminals"], len(terms))
@@ -1382,6 +1495,48 @@ class Engine:
                                         d_words.cpu().numpy().view(np.uint32) if per_state else None,
                                         d_sets.cpu().numpy() if per_state else None,
                                         d_tw.cpu().numpy().view(np.uint32), cap)
+
+    def shrink_many_device(self, d_traces, d_counts, n_sys, opts, sopts, d_out_traces, d_out_counts, d_orig, info, trail,
+                           trail_cap, scratch_bytes=0, stream=0):
+        """dsm_shrink_many_device: device pointers or tensors for the traces, counts and the three
+        array outputs, numpy arrays (or None) for info and trail.  SYNCHRONOUS; returns the error
+        code."""
+        return lib().dsm_shrink_many_device(self.ctx, _dptr(d_traces), _dptr(d_counts), n_sys, ctypes.byref(opts),
+                                            ctypes.byref(sopts), scratch_bytes, _dptr(d_out_traces), _dptr(d_out_counts),
+                                            _dptr(d_orig), _ptr(info), _ptr(trail), trail_cap, ctypes.c_void_p(stream))
+
+    def shrink_many(self, traces, counts, property, classes=None, inbox_limit=16, kind=CENSUS_DUMPS, max_states=1 << 16,
+                    max_depth=0, chunk=0, trail_cap=SHRINK_MAX_ROUNDS, scratch_bytes=0):
+        """Every system of traces [n, np, max_instr] u16, counts [n, np] shrunk on the GPU, the
+        candidates of all systems of a round searched by one launch -> the dict of
+        pydsm.shrink_many."""
+        import torch
+        tr, cn = np.ascontiguousarray(traces, dtype=np.uint16), np.ascontiguousarray(counts, dtype=np.uint32)
+        if tr.ndim != 3 or tr.shape[1:] != (self.np, self.max_instr) or cn.shape != tr.shape[:2]:
+            raise DsmError(E_INVAL, "shrink_many: systems of the engine's np and max_instr")
+        n = tr.shape[0]
+        dev = torch.device("cuda", self.device)
+        d_tr = torch.from_numpy(tr.view(np.int16).reshape(-1)).to(dev)
+        d_cn = torch.from_numpy(cn.view(np.int32).reshape(-1)).to(dev)
+        d_out = torch.zeros(max(tr.size, 1), dtype=torch.int16, device=dev)
+        d_orig = torch.zeros(max(tr.size, 1), dtype=torch.int16, device=dev)
+        d_ocn = torch.zeros(max(cn.size, 1), dtype=torch.int32, device=dev)
+        info = np.zeros(n, dtype=SHRINK_INFO_DTYPE)
+        trail = np.zeros(max(n * trail_cap, 1), dtype=SHRINK_STEP_DTYPE)
+        opts = ReachOpts(inbox_limit, CENSUS_KINDS.get(kind, kind), max_states, max_depth, chunk)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _check(self.shrink_many_device(d_tr, d_cn, n, opts, shrink_opts(property, classes), d_out, d_ocn, d_orig, info, trail,
+                                       trail_cap, scratch_bytes, st), "dsm_shrink_many_device")
+        return _shrink_result(d_out.cpu().numpy().view(np.uint16)[:tr.size].reshape(tr.shape),
+                              d_ocn.cpu().numpy().view(np.uint32)[:cn.size].reshape(cn.shape),
+                              d_orig.cpu().numpy().view(np.uint16)[:tr.size].reshape(tr.shape), info, trail[:n * trail_cap],
+                              trail_cap)
+
+    def shrink(self, traces, counts, property, classes=None, **kw):
+        """shrink_many of ONE system (traces [np, max_instr], counts [np]) -> the same dict, unstacked."""
+        traces = np.ascontiguousarray(traces, dtype=np.uint16)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+        return _shrink_first(self.shrink_many(traces[None], counts[None], property, classes, **kw))
 
     def reach_dist_device(self, d_trace, d_counts, opts, thresh, max_rounds, rinfo, dinfo, d_terminals, d_term_mass,
                           term_cap, round_mass, stream=0):

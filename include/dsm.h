@@ -65,7 +65,8 @@ extern "C" {
                                 (dsm_reach_audit*) likewise;
                              5 (+reach batch audit): additive -- that audit for a whole ensemble
                                 in one asynchronous launch (dsm_reach_batch_audit*) likewise;
-                             5 (+profile): additive -- the access profile (dsm_profile_*) likewise */
+                             5 (+profile): additive -- the access profile (dsm_profile_*) likewise;
+                             5 (+shrink): additive -- the test shrinker (dsm_shrink*) likewise */
 
 #define DSM_MAX_NP 8             /* bitVector is one byte (README.md:51)                  */
 #define DSM_CACHE_SIZE 4         /* CACHE_SIZE      assignment.c:10                        */
@@ -1159,6 +1160,110 @@ int dsm_reach_batch_audit_device(dsm_ctx *ctx, const uint16_t *d_traces, const u
                                  dsm_reach_terminal *d_terminals, uint64_t term_cap,
                                  uint32_t *d_parents, uint8_t *d_masks, uint32_t *d_words,
                                  uint8_t *d_sets, uint32_t *d_term_words, void *stream);
+
+/* ---- shrink: the minimal test that keeps a reachable defect ---------------------------------- *
+ * The screens say THAT a test has a reachable defect; the shrinker says which of its instructions
+ * cause it: it deletes instructions while the defect stays reachable, and ends with a test of which
+ * no single instruction can be deleted.  One system is trace [np][stride] and counts [np] (clamped
+ * to the stride); it is shrunk under a dsm_reach_opts, a property and a class mask.
+ *
+ * Verdict of a searched system, from its dsm_reach_info and dsm_reach_audit_info:
+ * DSM_SHRINK_FOUND when the property holds; else DSM_SHRINK_UNKNOWN when info.flags has
+ * DSM_REACH_F_STATES or DSM_REACH_F_DEPTH; else DSM_SHRINK_ABSENT.  Every property is existential
+ * over numbered states, so a FOUND from a truncated search is genuine.  Properties:
+ *   DSM_SHRINK_DEADLOCK              by_status[DSM_DEADLOCKED] > 0
+ *   DSM_SHRINK_OVERFLOW              by_status[DSM_RING_OVERFLOW] > 0
+ *   DSM_SHRINK_ASSERT                by_status[DSM_ASSERT_FAILED] > 0
+ *   DSM_SHRINK_END_INCOHERENT        set[DSM_RAUDIT_COMPLETED].by_class[c] > 0 for a class c of
+ *                                    class_mask (bit c; 0 = all DSM_AUDIT_NCLASS classes)
+ *   DSM_SHRINK_QUIESCENT_INCOHERENT  the same on set[DSM_RAUDIT_QUIESCENT]
+ *
+ * Candidates of the current system at granularity g, in index order: for each core c ascending and
+ * each k in [0, ceil(count_c / g)) ascending, the system with instructions [k g, min((k + 1) g,
+ * count_c)) of core c deleted: the core's tail moves down, the freed cells are zero, the count is
+ * reduced.  A core of count 0 has none.
+ *
+ * Round 0 is the verdict of the system itself: ABSENT ends with DSM_SHRINK_NOT_FOUND, UNKNOWN with
+ * DSM_SHRINK_ROOT_UNKNOWN; a system of more than DSM_SHRINK_MAX_INSTRS instructions ends with
+ * DSM_SHRINK_TOO_LONG and is not searched.  In these three cases the output is the input and orig
+ * the identity.  Then g = the largest power of two <= max_c count_c (no instruction at all:
+ * DSM_SHRINK_MINIMAL with 0 rounds), and per round all candidates at g are searched under the
+ * caller's opts.  With a FOUND candidate the LOWEST-INDEXED one becomes the current system, and g
+ * is halved while g > 1 && g > max_c count_c; with none g is halved, and the loop ends when g was
+ * 1.  It also ends when no instruction is left.  The result is DSM_SHRINK_MINIMAL when the last
+ * g == 1 round had no UNKNOWN candidate (or there was none), else DSM_SHRINK_MINIMAL_WITHIN_CAP:
+ * either way every single-instruction deletion of the result was searched and lacks the property,
+ * or was unknown.  A system of n instructions takes at most n + log2(n) + 1 rounds.
+ *
+ * Outputs, each may be NULL:
+ *   out_traces [n_sys][np][stride], out_counts [n_sys][np]: the shrunk systems; cells at and after
+ *     a core's count are zero, counts are clamped to the stride;
+ *   orig [n_sys][np][stride]: orig[s][c][i] is the index in the input of the instruction now at i,
+ *     strictly ascending below the count, 0xFFFF at and after it;
+ *     out_traces[s][c][i] == traces[s][c][orig[s][c][i]] below the count;
+ *   info [n_sys];
+ *   trail [n_sys][trail_cap]: the step of round r >= 1 at trail[s][r - 1] for r <= min(rounds,
+ *     trail_cap); entries after those are not written.
+ * Results per system never depend on which other systems share the call, on chunk or on
+ * scratch_bytes. */
+enum { DSM_SHRINK_DEADLOCK = 0, DSM_SHRINK_OVERFLOW = 1, DSM_SHRINK_ASSERT = 2, DSM_SHRINK_END_INCOHERENT = 3,
+       DSM_SHRINK_QUIESCENT_INCOHERENT = 4 };
+#define DSM_SHRINK_NPROPERTY 5
+enum { DSM_SHRINK_ABSENT = 0, DSM_SHRINK_FOUND = 1, DSM_SHRINK_UNKNOWN = 2 };        /* verdicts */
+enum { DSM_SHRINK_MINIMAL = 0, DSM_SHRINK_MINIMAL_WITHIN_CAP = 1, DSM_SHRINK_NOT_FOUND = 2,
+       DSM_SHRINK_ROOT_UNKNOWN = 3, DSM_SHRINK_TOO_LONG = 4 };                       /* statuses */
+#define DSM_SHRINK_NSTATUS 5
+#define DSM_SHRINK_MAX_INSTRS 64u      /* of one system, all cores together */
+#define DSM_SHRINK_MAX_ROUNDS 80u
+typedef struct dsm_shrink_opts { uint32_t property; uint32_t class_mask; uint32_t reserved[2]; } dsm_shrink_opts;
+typedef struct dsm_shrink_step {      /* one per round >= 1 */
+    uint32_t g, n_cand, n_found, n_unknown;
+    uint32_t core, start, len;        /* the accepted deletion in the CURRENT system's indices; core ~0: none */
+    uint32_t reserved;
+    uint64_t states;                  /* sum of info.states over the round's candidates */
+} dsm_shrink_step;
+typedef struct dsm_shrink_info {
+    uint32_t status, rounds;          /* DSM_SHRINK_MINIMAL.. ; rounds >= 1 only */
+    uint32_t instrs_in, instrs_out, accepted, reserved0;
+    uint64_t candidates, unknown, states;     /* sums over rounds >= 1 */
+    uint64_t root_states, root_flags;         /* round 0's info.states and info.flags */
+    uint64_t reserved[2];
+} dsm_shrink_info;
+/* The host reference (no GPU needed): the loop above over dsm_reach_batch_audit, one system at a
+ * time.  Errors are dsm_reach_batch's, plus DSM_E_INVAL for an unknown property or a class-mask
+ * bit >= DSM_AUDIT_NCLASS; a bad argument writes nothing. */
+int dsm_shrink_many(int np, const uint16_t *traces, const uint32_t *counts, uint32_t stride, uint64_t n_sys,
+                    const dsm_reach_opts *opts, const dsm_shrink_opts *sopts, uint16_t *out_traces,
+                    uint32_t *out_counts, uint16_t *orig, dsm_shrink_info *info, dsm_shrink_step *trail,
+                    uint32_t trail_cap);
+/* The same on the GPU for systems of the ctx's np and max_instr: every round puts the candidates of
+ * ALL systems still active into one dsm_reach_batch_audit_device call (shrink_plan_kernel counts
+ * and places them, shrink_build_kernel writes them, shrink_pick_kernel takes the verdicts and moves
+ * each system on).  d_traces, d_counts, d_out_traces, d_out_counts and d_orig are device memory
+ * (d_out_counts 4-byte aligned, d_out_traces and d_orig 2-byte); info and trail are host memory.
+ * SYNCHRONOUS like dsm_reach_device: per round the host reads back the round's total candidate
+ * count, 8 bytes, and nothing else; traces, candidates and verdicts never leave the device.  Its
+ * own buffers are allocated for the call and freed before it returns (DSM_E_NOMEM with nothing
+ * leaked); the searches use the ctx's slabs as dsm_reach_batch_audit_device does, under the same
+ * "one run at a time, one stream" convention, and scratch_bytes is passed through.  n_sys == 0 is a
+ * no-op; a bad argument is DSM_E_INVAL with nothing written.  Every written value equals
+ * dsm_shrink_many's bit for bit. */
+int dsm_shrink_many_device(dsm_ctx *ctx, const uint16_t *d_traces, const uint32_t *d_counts, uint64_t n_sys,
+                           const dsm_reach_opts *opts, const dsm_shrink_opts *sopts, uint64_t scratch_bytes,
+                           uint16_t *d_out_traces, uint32_t *d_out_counts, uint16_t *d_orig,
+                           dsm_shrink_info *info, dsm_shrink_step *trail, uint32_t trail_cap, void *stream);
+/* the n_sys == 1 conveniences */
+int dsm_shrink(int np, const uint16_t *trace, const uint32_t *counts, uint32_t stride, const dsm_reach_opts *opts,
+               const dsm_shrink_opts *sopts, uint16_t *out_trace, uint32_t *out_counts, uint16_t *orig,
+               dsm_shrink_info *info, dsm_shrink_step *trail, uint32_t trail_cap);
+int dsm_shrink_device(dsm_ctx *ctx, const uint16_t *d_trace, const uint32_t *d_counts, const dsm_reach_opts *opts,
+                      const dsm_shrink_opts *sopts, uint64_t scratch_bytes, uint16_t *d_out_trace,
+                      uint32_t *d_out_counts, uint16_t *d_orig, dsm_shrink_info *info, dsm_shrink_step *trail,
+                      uint32_t trail_cap, void *stream);
+/* "MINIMAL" .. "TOO_LONG"; "deadlock", "overflow", "assert", "end-incoherent", "quiescent-incoherent";
+ * NULL for any other value (host only) */
+const char *dsm_shrink_status_name(int status);
+const char *dsm_shrink_property_name(int property);
 
 /* ---- multi-GPU group: RCCL over xGMI --------------------------------------- *
  * Systems are independent, so an ensemble shards over GPUs with no data-path exchange; the
