@@ -163,6 +163,16 @@
  *                    terminal states), then
  *                        screened N tests: D can deadlock, X exhaustive
  *                    Exits 2 when D > 0, else 3 when any search was truncated, else 0.
+ *   --reach-batch-prob T[,T...]
+ *                    --reach-batch with the outcome probabilities of every test under the seeded
+ *                    schedules' thresholds T (as --reach-prob takes them; one
+ *                    dsm_reach_batch_dist_device call in place of the plain one); the same options
+ *                    and exit codes.  After each directory's line, one line per threshold,
+ *                        <dir>: p[0xT] deadlocked P overflow P assert P completed P lost N escaped N rounds R
+ *                    (P as --reach-prob prints it, N in units of 2^-63), after the summary line
+ *                        rank k: <dir> p[0xT] deadlocked P
+ *                    for every directory by descending deadlock probability under the first
+ *                    threshold.  Not valid with --reach-batch-audit.
  *   --reach-batch-audit
  *                    --reach-batch with the coherence audit of every reachable state of every test
  *                    (one dsm_reach_batch_audit_device call in place of the plain one); the same
@@ -212,7 +222,7 @@ static void usage(const char *argv0) {
                     "          [--fate completed|deadlocked|ring_overflow|assert_failed|round_limit|0xKEY]\n"
                     "          [--explore-dir DIR]\n"
                     "          [--explore-kind dumps|final] [--check DIR]] <test_directory>\n"
-                    "       %s [--np 4|8] [--max-instr N] [--device D] [--quiet] --reach-batch | --reach-batch-audit [--reach-states N]\n"
+                    "       %s [--np 4|8] [--max-instr N] [--device D] [--quiet] --reach-batch | --reach-batch-audit | --reach-batch-prob T[,T...] [--reach-states N]\n"
                     "          [--reach-depth D] [--reach-inbox L] [--explore-kind dumps|final] <test_directory>...\n"
                     "       %s [--np 4|8] [--max-instr N] [--device D] [--quiet]\n"
                     "          --shrink deadlock|overflow|assert|end-incoherent|quiescent-incoherent [--shrink-classes NAME,...]\n"
@@ -574,6 +584,19 @@ fail:
 static void print_mass(uint64_t mass) {
     const unsigned __int128 v = ((unsigned __int128)mass * 1000000000000000000ull) >> 63;
     printf("%llu.%018llu", (unsigned long long)(v / 1000000000000000000ull), (unsigned long long)(v % 1000000000000000000ull));
+}
+
+/* T[,T...] -> t[0 .. *n): 1..65536 each, at most DSM_DIST_MAX_THRESH of them; non-zero when it is not that */
+static int parse_thresholds(const char *v, uint32_t *t, uint32_t *n) {
+    for (*n = 0;;) {
+        char *end;
+        const unsigned long x = strtoul(v, &end, 0);
+        if (end == v || x < 1 || x > 65536 || *n == DSM_DIST_MAX_THRESH) return 1;
+        t[(*n)++] = (uint32_t)x;
+        if (*end == '\0') return 0;
+        if (*end != ',') return 1;
+        v = end + 1;
+    }
 }
 
 /* --reach: every state the system can reach under the schedule model (dsm_reach_device), the
@@ -940,11 +963,25 @@ static int append_core_file(const char *dir, int n, char **text, uint64_t *len) 
     return 0;
 }
 
+/* the order of --reach-batch-prob's ranking: descending deadlock mass under the first threshold,
+ * ties by position on the command line */
+static const dsm_dist_info *rank_dinfo;
+static uint32_t rank_nth;
+static int rank_cmp(const void *a, const void *b) {
+    const int x = *(const int *)a, y = *(const int *)b;
+    const uint64_t mx = rank_dinfo[(size_t)x * rank_nth].by_status[DSM_DEADLOCKED];
+    const uint64_t my = rank_dinfo[(size_t)y * rank_nth].by_status[DSM_DEADLOCKED];
+    return mx != my ? (mx > my ? -1 : 1) : (x > y) - (x < y);
+}
+
 /* --reach-batch: the tests of dirs read with one dsm_parse_traces call and searched with one
- * dsm_reach_batch_device call (with audit: one dsm_reach_batch_audit_device call); a line per test
- * (with audit: its audit lines) and the screen's summary.  Returns the process exit code. */
+ * dsm_reach_batch_device call (with audit: one dsm_reach_batch_audit_device call; with n_prob
+ * thresholds: one dsm_reach_batch_dist_device call); a line per test (with audit: its audit lines;
+ * with thresholds: its probability lines) and the screen's summary (with thresholds: then the
+ * ranking).  Returns the process exit code. */
 static int reach_batch(int np, uint32_t max_instr, int device, char **dirs, int n_dirs,
-                       unsigned long long max_states, uint32_t max_depth, uint32_t inbox, int kind, int audit) {
+                       unsigned long long max_states, uint32_t max_depth, uint32_t inbox, int kind, int audit,
+                       const uint32_t *prob_t, uint32_t n_prob) {
     const uint32_t stride = (max_instr + 7u) & ~7u;
     const uint64_t n_files = (uint64_t)n_dirs * (uint64_t)np;
     const uint64_t term_cap = max_states < (DSM_CENSUS_MAX_CAP / 2) ? max_states : (DSM_CENSUS_MAX_CAP / 2);
@@ -957,13 +994,16 @@ static int reach_batch(int np, uint32_t max_instr, int device, char **dirs, int 
     dsm_reach_info *info = (dsm_reach_info *)calloc((size_t)n_dirs, sizeof *info), *d_info = NULL;
     dsm_reach_terminal *term = (dsm_reach_terminal *)malloc((size_t)term_cap * sizeof *term), *d_term = NULL;
     dsm_reach_audit_info *ainfo = audit ? (dsm_reach_audit_info *)calloc((size_t)n_dirs, sizeof *ainfo) : NULL, *d_ainfo = NULL;
+    dsm_dist_info *dinfo = n_prob ? (dsm_dist_info *)calloc((size_t)n_dirs * n_prob, sizeof *dinfo) : NULL, *d_dinfo = NULL;
+    int *order = n_prob ? (int *)calloc((size_t)n_dirs, sizeof(int)) : NULL;
     uint64_t *cen = NULL;
     dsm_ctx *ctx = NULL;
     dsm_reach_opts opts;
+    dsm_dist_batch_opts dopts;
     dsm_config cfg;
     int rc = DSM_OK, code = EXIT_FAILURE;
     const char *what = "out of memory";
-    if (!off || !traces || !counts || !pst || !info || !term || (audit && !ainfo)) goto fail;
+    if (!off || !traces || !counts || !pst || !info || !term || (audit && !ainfo) || (n_prob && (!dinfo || !order))) goto fail;
     for (uint64_t f = 0; f < n_files; ++f) {
         uint64_t len = off[f];
         if (append_core_file(dirs[f / (uint64_t)np], (int)(f % (uint64_t)np), &text, &len)) goto fail;
@@ -993,10 +1033,18 @@ static int reach_batch(int np, uint32_t max_instr, int device, char **dirs, int 
         hipMalloc((void **)&d_info, (size_t)n_dirs * sizeof *info) != hipSuccess ||
         hipMalloc((void **)&d_term, (size_t)n_dirs * (size_t)term_cap * sizeof *term) != hipSuccess ||
         (audit && hipMalloc((void **)&d_ainfo, (size_t)n_dirs * sizeof *ainfo) != hipSuccess) ||
+        (n_prob && hipMalloc((void **)&d_dinfo, (size_t)n_dirs * n_prob * sizeof *dinfo) != hipSuccess) ||
         hipMemcpy(d_tr, traces, tr_bytes, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(d_cn, counts, cn_bytes, hipMemcpyHostToDevice) != hipSuccess)
         goto fail;
-    if (audit) {
+    if (n_prob) {
+        memset(&dopts, 0, sizeof dopts);
+        dopts.n_thresh = n_prob;
+        for (uint32_t j = 0; j < n_prob; ++j) dopts.thresh[j] = prob_t[j];
+        what = "dsm_reach_batch_dist_device";
+        rc = dsm_reach_batch_dist_device(ctx, d_tr, d_cn, (uint64_t)n_dirs, &opts, &dopts, 0, d_info, d_dinfo, d_term, NULL, term_cap,
+                                         NULL, NULL, NULL);
+    } else if (audit) {
         what = "dsm_reach_batch_audit_device";
         rc = dsm_reach_batch_audit_device(ctx, d_tr, d_cn, (uint64_t)n_dirs, &opts, 0, d_info, d_ainfo, d_term, term_cap, NULL,
                                           NULL, NULL, NULL, NULL, NULL);
@@ -1008,7 +1056,8 @@ static int reach_batch(int np, uint32_t max_instr, int device, char **dirs, int 
     what = "read-back";
     if (hipDeviceSynchronize() != hipSuccess ||
         hipMemcpy(info, d_info, (size_t)n_dirs * sizeof *info, hipMemcpyDeviceToHost) != hipSuccess ||
-        (audit && hipMemcpy(ainfo, d_ainfo, (size_t)n_dirs * sizeof *ainfo, hipMemcpyDeviceToHost) != hipSuccess))
+        (audit && hipMemcpy(ainfo, d_ainfo, (size_t)n_dirs * sizeof *ainfo, hipMemcpyDeviceToHost) != hipSuccess) ||
+        (n_prob && hipMemcpy(dinfo, d_dinfo, (size_t)n_dirs * n_prob * sizeof *dinfo, hipMemcpyDeviceToHost) != hipSuccess))
         goto fail;
     uint64_t n_dead = 0, n_exh = 0, n_inc = 0;
     for (int s = 0; s < n_dirs; ++s) {
@@ -1052,6 +1101,24 @@ static int reach_batch(int np, uint32_t max_instr, int device, char **dirs, int 
                        (unsigned long long)ainfo[s].first_depth[DSM_RAUDIT_COMPLETED][7]);
             n_inc += c->violating != 0;
         }
+        for (uint32_t j = 0; j < n_prob; ++j) {
+            const dsm_dist_info *d = &dinfo[(size_t)s * n_prob + j];
+            printf("%s: p[0x%x] ", dirs[s], prob_t[j]);
+            if (d->flags & DSM_DIST_F_EDGES) {
+                printf("no distribution: %llu edges are more than the batch keeps\n", (unsigned long long)d->edges);
+                continue;
+            }
+            printf("deadlocked ");
+            print_mass(d->by_status[DSM_DEADLOCKED]);
+            printf(" overflow ");
+            print_mass(d->by_status[DSM_RING_OVERFLOW]);
+            printf(" assert ");
+            print_mass(d->by_status[DSM_ASSERT_FAILED]);
+            printf(" completed ");
+            print_mass(d->by_status[DSM_COMPLETED]);
+            printf(" lost %llu escaped %llu rounds %llu\n", (unsigned long long)d->lost, (unsigned long long)d->escaped,
+                   (unsigned long long)d->rounds);
+        }
     }
     if (audit)
         printf("screened %d tests: %llu can deadlock, %llu can end incoherent, %llu exhaustive\n", n_dirs,
@@ -1059,6 +1126,17 @@ static int reach_batch(int np, uint32_t max_instr, int device, char **dirs, int 
     else
         printf("screened %d tests: %llu can deadlock, %llu exhaustive\n", n_dirs, (unsigned long long)n_dead,
                (unsigned long long)n_exh);
+    if (n_prob) {                                       /* the tests by descending deadlock probability */
+        for (int s = 0; s < n_dirs; ++s) order[s] = s;
+        rank_dinfo = dinfo;
+        rank_nth = n_prob;
+        qsort(order, (size_t)n_dirs, sizeof(int), rank_cmp);
+        for (int k = 0; k < n_dirs; ++k) {
+            printf("rank %d: %s p[0x%x] deadlocked ", k + 1, dirs[order[k]], prob_t[0]);
+            print_mass(dinfo[(size_t)order[k] * n_prob].by_status[DSM_DEADLOCKED]);
+            printf("\n");
+        }
+    }
     code = n_dead || n_inc ? 2 : n_exh != (uint64_t)n_dirs ? 3 : 0;
     what = NULL;
     rc = DSM_OK;
@@ -1067,10 +1145,12 @@ fail:
     if (d_tr) (void)hipFree(d_tr);
     if (d_cn) (void)hipFree(d_cn);
     if (d_info) (void)hipFree(d_info);
+    if (d_dinfo) (void)hipFree(d_dinfo);
     if (d_term) (void)hipFree(d_term);
     if (d_ainfo) (void)hipFree(d_ainfo);
     if (ctx) dsm_close(ctx);
     free(text); free(off); free(traces); free(counts); free(pst); free(info); free(term); free(ainfo); free(cen);
+    free(dinfo); free(order);
     return code;
 }
 
@@ -1257,7 +1337,7 @@ int main(int argc, char **argv) {
     dsm_shrink_opts shrink_opts;
     long long reach_states = 1ll << 22, reach_depth = 0, reach_inbox = 16;
     int reach_opts = 0;
-    uint32_t prob_t[DSM_DIST_MAX_THRESH], n_prob = 0;
+    uint32_t prob_t[DSM_DIST_MAX_THRESH], n_prob = 0, bprob_t[DSM_DIST_MAX_THRESH], n_bprob = 0;
     dsm_fate_opts fate_opts;
     const char *fate_name = NULL;
     uint32_t max_instr = DSM_REF_MAX_INSTR;
@@ -1312,17 +1392,12 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--reach-depth") && i + 1 < argc) { reach_depth = atoll(argv[++i]); reach_opts = 1; }
         else if (!strcmp(argv[i], "--reach-inbox") && i + 1 < argc) { reach_inbox = atoll(argv[++i]); reach_opts = 1; }
         else if (!strcmp(argv[i], "--reach-prob") && i + 1 < argc) {
-            const char *v = argv[++i];
             reach_opts = 1;
-            for (n_prob = 0;;) {
-                char *end;
-                const unsigned long t = strtoul(v, &end, 0);
-                if (end == v || t < 1 || t > 65536 || n_prob == DSM_DIST_MAX_THRESH) { usage(argv[0]); return EXIT_FAILURE; }
-                prob_t[n_prob++] = (uint32_t)t;
-                if (*end == '\0') break;
-                if (*end != ',') { usage(argv[0]); return EXIT_FAILURE; }
-                v = end + 1;
-            }
+            if (parse_thresholds(argv[++i], prob_t, &n_prob)) { usage(argv[0]); return EXIT_FAILURE; }
+        }
+        else if (!strcmp(argv[i], "--reach-batch-prob") && i + 1 < argc) {
+            do_batch = 1;
+            if (parse_thresholds(argv[++i], bprob_t, &n_bprob)) { usage(argv[0]); return EXIT_FAILURE; }
         }
         else if (!strcmp(argv[i], "--fate") && i + 1 < argc) {
             const char *v = argv[++i];
@@ -1384,14 +1459,14 @@ int main(int argc, char **argv) {
     if (do_batch) {
         if (!states_set) reach_states = 1ll << 16;
         if (do_reach || explore_n || have_sched || events_file || events_opts || issue_file || audit || profile || explore_dir ||
-            check_dir || n_prob || fate_name || explore_kind == DSM_CENSUS_FULL || reach_states < 1 ||
+            check_dir || n_prob || fate_name || (batch_audit && n_bprob) || explore_kind == DSM_CENSUS_FULL || reach_states < 1 ||
             reach_states > (long long)DSM_REACH_BATCH_MAX_STATES || reach_depth < 0 ||
             reach_depth >= (long long)DSM_REACH_MAX_LEVELS || reach_inbox < 1 || reach_inbox > 16) {
             usage(argv[0]);
             return EXIT_FAILURE;
         }
         return reach_batch(np, max_instr, device, argv + 1, n_dirs, (unsigned long long)reach_states,
-                           (uint32_t)reach_depth, (uint32_t)reach_inbox, explore_kind, batch_audit);
+                           (uint32_t)reach_depth, (uint32_t)reach_inbox, explore_kind, batch_audit, bprob_t, n_bprob);
     }
     if ((explore_n && issue_file) || (!explore_n && !do_reach && explore_opts)) { usage(argv[0]); return EXIT_FAILURE; }
     if ((reach_opts && !do_reach) ||

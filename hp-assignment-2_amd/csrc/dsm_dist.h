@@ -1,7 +1,7 @@
 /*
  * dsm_dist.h -- the outcome distribution's pieces shared by the gfx950 kernels and the host
  * (dsm_dist.hip: dist_*_kernel, dsm_reach_dist, dsm_sched_prob): the class of a state, the index
- * of an edge's probability, and the exact edge probability itself (host only).
+ * of an edge's probability, and the exact edge probability itself.
  *
  * An edge is (src, dst, pk): pk = dist_pidx(k, m) names the entry of the threshold's table
  * P[DIST_P_WORDS], P[pk] = dsm_sched_prob(t, k, m), k = |A(src)|, m = popcount(mask).
@@ -29,13 +29,14 @@ DSM_HD uint32_t dist_class(const StMem &m, uint32_t enabled, bool expanded) {
     return DIST_TERMINAL + (rs_end_status<NP>(m) & 7u);
 }
 
-/* Host only from here on.  256-bit unsigned integers in eight 32-bit limbs, as far as the long
- * division below needs them. */
+/* 256-bit unsigned integers in eight 32-bit limbs, as far as the long division below needs them.
+ * Host and device (the reach batch distribution fills its P tables in the kernel): every limb index
+ * is a constant once the fixed loops are unrolled, so the limbs stay in registers. */
 struct DistBig {
     uint32_t w[8];
 };
 
-static inline void distbig_mul(DistBig *a, uint32_t x) {
+DSM_HD void distbig_mul(DistBig *a, uint32_t x) {
     uint64_t carry = 0;
     for (int i = 0; i < 8; ++i) {
         const uint64_t p = (uint64_t)a->w[i] * x + carry;
@@ -44,13 +45,14 @@ static inline void distbig_mul(DistBig *a, uint32_t x) {
     }
 }
 
-static inline int distbig_cmp(const DistBig *a, const DistBig *b) {
-    for (int i = 7; i >= 0; --i)
-        if (a->w[i] != b->w[i]) return a->w[i] < b->w[i] ? -1 : 1;
-    return 0;
+DSM_HD int distbig_cmp(const DistBig *a, const DistBig *b) {
+    int r = 0;                                                   /* the highest differing limb decides */
+    for (int i = 0; i < 8; ++i)
+        if (a->w[i] != b->w[i]) r = a->w[i] < b->w[i] ? -1 : 1;
+    return r;
 }
 
-static inline void distbig_sub(DistBig *a, const DistBig *b) {
+DSM_HD void distbig_sub(DistBig *a, const DistBig *b) {
     uint64_t borrow = 0;
     for (int i = 0; i < 8; ++i) {
         const uint64_t d = (uint64_t)a->w[i] - b->w[i] - borrow;
@@ -59,9 +61,18 @@ static inline void distbig_sub(DistBig *a, const DistBig *b) {
     }
 }
 
+/* a = 2 a + bit; returns the bit shifted out at the top */
+DSM_HD uint32_t distbig_shl1(DistBig *a, uint32_t bit) {
+    const uint32_t out = a->w[7] >> 31;
+    for (int i = 7; i > 0; --i) a->w[i] = (a->w[i] << 1) | (a->w[i - 1] >> 31);
+    a->w[0] = (a->w[0] << 1) | bit;
+    return out;
+}
+
 /* floor(2^64 t^m q^(k-m) / (65536^k - q^k)), saturated; the numerator is below 2^193 and the
- * divisor at most 2^128, so everything fits 256 bits.  Long division a bit at a time. */
-static inline uint64_t dist_sched_prob(uint32_t t, uint32_t k, uint32_t m) {
+ * divisor at most 2^128, so everything fits 256 bits.  Long division a bit at a time, the
+ * numerator's bits taken from its top as it shifts left. */
+DSM_HD uint64_t dist_sched_prob(uint32_t t, uint32_t k, uint32_t m) {
     if (m < 1u || m > k || k > 8u || t < 1u || t > 65536u) return 0;
     const uint32_t q = 65536u - t;
     DistBig num = {{1u, 0, 0, 0, 0, 0, 0, 0}}, den = {{0, 0, 0, 0, 0, 0, 0, 0}}, qk = {{1u, 0, 0, 0, 0, 0, 0, 0}};
@@ -69,15 +80,15 @@ static inline uint64_t dist_sched_prob(uint32_t t, uint32_t k, uint32_t m) {
     for (uint32_t i = m; i < k; ++i) distbig_mul(&num, q);
     for (int i = 7; i >= 2; --i) num.w[i] = num.w[i - 2];        /* * 2^64 */
     num.w[0] = num.w[1] = 0;
-    den.w[k / 2u] = (k & 1u) ? 0x10000u : 1u;                    /* 65536^k = 2^(16 k) */
+    for (uint32_t i = 0; i < 8u; ++i)                            /* 65536^k = 2^(16 k) */
+        den.w[i] = i == k / 2u ? ((k & 1u) ? 0x10000u : 1u) : 0u;
     for (uint32_t i = 0; i < k; ++i) distbig_mul(&qk, q);
     distbig_sub(&den, &qk);                                      /* > 0: q < 65536 */
     DistBig rem = {{0, 0, 0, 0, 0, 0, 0, 0}};
     uint64_t quo = 0;
     bool high = false;                                           /* a quotient bit at or above 2^64 */
     for (int bit = 255; bit >= 0; --bit) {
-        for (int i = 7; i > 0; --i) rem.w[i] = (rem.w[i] << 1) | (rem.w[i - 1] >> 31);
-        rem.w[0] = (rem.w[0] << 1) | ((num.w[bit >> 5] >> (bit & 31)) & 1u);
+        (void)distbig_shl1(&rem, distbig_shl1(&num, 0u));        /* rem < den <= 2^128: nothing falls out */
         if (distbig_cmp(&rem, &den) >= 0) {
             distbig_sub(&rem, &den);
             if (bit >= 64) high = true; else quo |= 1ull << bit;

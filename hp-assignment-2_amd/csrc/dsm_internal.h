@@ -205,6 +205,12 @@ extern "C" int dsm_debug_shrink_times(double *ms, uint64_t *rounds);
  * tools/reach_batch_time.py): the systems it kept in flight and the bytes of the ctx's scratch. */
 extern "C" int dsm_debug_reach_batch_state(dsm_ctx *c, uint64_t *in_flight, uint64_t *scratch_bytes);
 
+/* Test-only (not part of the ABI): the P tables the reach batch distribution's workgroups compute
+ * for themselves, by the same device code (bdist_fill_P) -- d_P[j * 64 + dist_pidx(k, m)] for
+ * j < n_thresh, 1 <= m <= k <= np, 0 elsewhere; asynchronous on `stream`. */
+extern "C" int dsm_debug_bdist_ptable_device(dsm_ctx *c, const uint32_t *thresh, uint32_t n_thresh, uint64_t *d_P,
+                                             void *stream);
+
 /* Test-only (not part of the ABI): dsm_exscan_launch with tile sums of its own, waited for --
  * d_out[0 .. n] = the exclusive scan of d_in[0 .. n) in 64 bits, d_out[n] the total. */
 extern "C" int dsm_debug_exscan_device(dsm_ctx *c, const uint32_t *d_in, uint64_t n, uint64_t *d_out, void *stream);

@@ -92,6 +92,11 @@ class ShrinkOpts(ctypes.Structure):
     _fields_ = [("property", ctypes.c_uint32), ("class_mask", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 2)]
 
 
+class DistBatchOpts(ctypes.Structure):
+    _fields_ = [("thresh", ctypes.c_uint32 * 16), ("n_thresh", ctypes.c_uint32), ("max_rounds", ctypes.c_uint32),
+                ("max_edges", ctypes.c_uint64), ("reserved", ctypes.c_uint64 * 2)]
+
+
 RESUME_FORMS = {0: "none", 1: "lock-step", 2: "serial", 3: "fast-forward lock-step"}
 
 
@@ -221,6 +226,12 @@ def lib():
                                       vp]),
             "dsm_reach_audit_device": (i32, [vp, vp, vp, ctypes.POINTER(ReachOpts), vp, vp, vp, vp, vp, vp, u64, vp, vp,
                                              vp, vp]),
+            # ABI 5 (+bdist): the reach batch distribution
+            "dsm_reach_batch_dist_slab_bytes": (u64, [i32, ctypes.POINTER(ReachOpts), ctypes.POINTER(DistBatchOpts)]),
+            "dsm_reach_batch_dist": (i32, [i32, vp, vp, u32, u64, ctypes.POINTER(ReachOpts), ctypes.POINTER(DistBatchOpts),
+                                           vp, vp, vp, vp, u64, vp, vp]),
+            "dsm_reach_batch_dist_device": (i32, [vp, vp, vp, u64, ctypes.POINTER(ReachOpts), ctypes.POINTER(DistBatchOpts),
+                                                  u64, vp, vp, vp, vp, u64, vp, vp, vp]),
             # ABI 5 (+shrink): the test shrinker
             "dsm_shrink_many": (i32, [i32, vp, vp, u32, u64, ctypes.POINTER(ReachOpts), ctypes.POINTER(ShrinkOpts), vp, vp, vp,
                                       vp, vp, u32]),
@@ -233,6 +244,7 @@ def lib():
             "dsm_shrink_status_name": (ctypes.c_char_p, [i32]),
             "dsm_shrink_property_name": (ctypes.c_char_p, [i32]),
             # test-only (csrc/dsm_internal.h, not in include/dsm.h)
+            "dsm_debug_bdist_ptable_device": (i32, [vp, vp, u32, vp, vp]),
             "dsm_debug_shrink_verdict": (i32, [vp, vp, ctypes.POINTER(ShrinkOpts)]),
             "dsm_debug_shrink_times": (i32, [vp, ctypes.POINTER(u64)]),
             "dsm_debug_raudit_times": (i32, [vp, ctypes.POINTER(u64)]),
@@ -1001,6 +1013,86 @@ def reach_audit_many(np_, traces, counts, inbox_limit=16, kind=CENSUS_DUMPS, max
     return _reach_audit_many_result(info, ainfo, terms[:n * term_cap], term_cap, parents, masks, words, sets, term_words, cap)
 
 
+# -- reach batch distribution (ABI 5 +bdist) ---------------------------------------------------
+DIST_F_EDGES = 8                             # DSM_DIST_F_EDGES: more edges than max_edges, no distribution
+DIST_INFO_DTYPE = np.dtype([("thresh", "<u8"), ("rounds", "<u8"), ("absorbed", "<u8"), ("escaped", "<u8"),
+                            ("residual", "<u8"), ("lost", "<u8"), ("by_status", "<u8", (5,)), ("edges", "<u8"),
+                            ("missing_edges", "<u8"), ("flags", "<u8"), ("reserved", "<u8", (2,))])
+assert DIST_INFO_DTYPE.itemsize == 8 * len(DIST_INFO_FIELDS)
+
+
+def dist_batch_opts(thresh=(0x8000,), max_rounds=0, max_edges=0, reserved=(0, 0)):
+    """A DistBatchOpts; thresholds past the first DIST_MAX_THRESH are dropped, n_thresh keeps their
+    number (so the call rejects them)."""
+    th = [int(t) for t in np.asarray(thresh, dtype=np.uint64).reshape(-1)]
+    o = DistBatchOpts()
+    for j, t in enumerate(th[:DIST_MAX_THRESH]):
+        o.thresh[j] = t & 0xFFFFFFFF
+    o.n_thresh, o.max_rounds, o.max_edges = len(th), max_rounds, max_edges
+    o.reserved[0], o.reserved[1] = reserved
+    return o
+
+
+def reach_batch_dist_slab_bytes(np_, thresh=(0x8000,), max_rounds=0, max_edges=0, inbox_limit=16, kind=CENSUS_DUMPS,
+                                max_states=1 << 16, max_depth=0, chunk=0):
+    """dsm_reach_batch_dist_slab_bytes: the device scratch one system in flight needs (0: bad options)."""
+    opts = ReachOpts(inbox_limit, CENSUS_KINDS.get(kind, kind), max_states, max_depth, chunk)
+    dopts = dist_batch_opts(thresh, max_rounds, max_edges)
+    return int(lib().dsm_reach_batch_dist_slab_bytes(np_, ctypes.byref(opts), ctypes.byref(dopts)))
+
+
+def _reach_dist_many_result(info, dinfo, terms, term_mass, term_cap, parents, masks, max_states, nth):
+    """The dict of reach_dist_many from the batch distribution's flat arrays."""
+    n = len(info)
+    out = _reach_many_result(info, terms, term_cap, parents, masks, max_states)
+    dinfo = dinfo[:n * nth].reshape(n, nth)
+    tm = term_mass[:n * nth * term_cap].reshape(n, nth, term_cap)
+    out.update({"dinfo": dinfo,
+                "term_mass": [tm[s, :, :min(term_cap, int(info["terminals"][s]))] for s in range(n)],
+                "p_status": dinfo["by_status"].astype(np.float64) / float(DIST_ONE),
+                "p_deadlock": dinfo["by_status"][:, :, 1].astype(np.float64) / float(DIST_ONE)})
+    first = [int(x) for x in dinfo["by_status"][:, 0, 1]] if n else []
+    out["ranking"] = np.array(sorted(range(n), key=lambda s: (-first[s], s)), dtype=np.int64)
+    return out
+
+
+def reach_dist_many(np_, traces, counts, thresh=(0x8000,), max_rounds=0, max_edges=0, inbox_limit=16, kind=CENSUS_DUMPS,
+                    max_states=1 << 16, max_depth=0, term_cap=None, witnesses=False):
+    """dsm_reach_batch_dist (the host reference; no GPU): pydsm.reach_dist over every system of traces
+    [n, np, stride] u16, counts [n, np] -> the dict of reach_many plus dinfo (DIST_INFO_DTYPE
+    [n, n_thresh]), term_mass (a list per system of uint64 [n_thresh, terminals]), p_status (float
+    [n, n_thresh, 5]: by_status / 2**63), p_deadlock (float [n, n_thresh]) and ranking (the system
+    indices by descending deadlock mass under the first threshold, ties by index)."""
+    traces = np.ascontiguousarray(traces, dtype=np.uint16)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    assert traces.ndim == 3 and traces.shape[1] == np_ and counts.shape == traces.shape[:2]
+    n = traces.shape[0]
+    opts = ReachOpts(inbox_limit, CENSUS_KINDS.get(kind, kind), max_states, max_depth, 0)
+    dopts = dist_batch_opts(thresh, max_rounds, max_edges)
+    nth = min(max(dopts.n_thresh, 1), DIST_MAX_THRESH)
+    ok = 0 < max_states <= REACH_BATCH_MAX_STATES
+    cap = max_states if ok else 1
+    term_cap = min(cap, 4096) if term_cap is None else term_cap
+    info = np.zeros(n, dtype=REACH_INFO_DTYPE)
+    dinfo = np.zeros(max(n * nth, 1), dtype=DIST_INFO_DTYPE)
+    terms = np.zeros(max(n * term_cap, 1), dtype=REACH_TERMINAL_DTYPE)
+    term_mass = np.zeros(max(n * nth * term_cap, 1), dtype=np.uint64)
+    parents = np.zeros(max(n * cap, 1), np.uint32) if witnesses else None
+    masks = np.zeros(max(n * cap, 1), np.uint8) if witnesses else None
+    _check(lib().dsm_reach_batch_dist(np_, _ptr(traces), _ptr(counts), traces.shape[2], n, ctypes.byref(opts),
+                                      ctypes.byref(dopts), _ptr(info), _ptr(dinfo), _ptr(terms), _ptr(term_mass), term_cap,
+                                      _ptr(parents), _ptr(masks)), "dsm_reach_batch_dist")
+    return _reach_dist_many_result(info, dinfo, terms[:n * term_cap], term_mass, term_cap, parents, masks, cap, nth)
+
+
+def end_incoherent_mass(terminals, term_words, term_mass):
+    """The exact mass, per threshold, on the terminals that completed and break an invariant:
+    terminals (REACH_TERMINAL_DTYPE), term_words (their audit words) and term_mass [n_thresh,
+    terminals] of ONE system, joined by terminal rank -> a list of Python ints."""
+    bad = ((terminals["status"] & 0xFF) == 0) & ((np.asarray(term_words) & 0x7F) != 0)
+    return [sum(int(v) for v in row[bad]) for row in np.asarray(term_mass)]
+
+
 # -- shrink (ABI 5 +shrink) --------------------------------------------------------------------
 SHRINK_DEADLOCK, SHRINK_OVERFLOW, SHRINK_ASSERT, SHRINK_END_INCOHERENT, SHRINK_QUIESCENT_INCOHERENT = range(5)
 SHRINK_PROPERTIES = {"deadlock": 0, "overflow": 1, "assert": 2, "end-incoherent": 3, "quiescent-incoherent": 4}
@@ -1495,6 +1587,93 @@ class Engine:
                                         d_words.cpu().numpy().view(np.uint32) if per_state else None,
                                         d_sets.cpu().numpy() if per_state else None,
                                         d_tw.cpu().numpy().view(np.uint32), cap)
+
+    def reach_batch_dist_device(self, d_traces, d_counts, n_sys, opts, dopts, d_info, d_dinfo, d_terminals, d_term_mass,
+                                term_cap, d_parents, d_masks, scratch_bytes=0, stream=0):
+        """dsm_reach_batch_dist_device: device pointers or tensors, each output may be None.
+        ASYNCHRONOUS on `stream`; returns the error code."""
+        return lib().dsm_reach_batch_dist_device(self.ctx, _dptr(d_traces), _dptr(d_counts), n_sys, ctypes.byref(opts),
+                                                 ctypes.byref(dopts), scratch_bytes, _dptr(d_info), _dptr(d_dinfo),
+                                                 _dptr(d_terminals), _dptr(d_term_mass), term_cap, _dptr(d_parents),
+                                                 _dptr(d_masks), ctypes.c_void_p(stream))
+
+    def debug_bdist_ptable(self, thresh):
+        """Test-only: the P tables a workgroup of the reach batch distribution computes -> uint64
+        [n_thresh, 64]."""
+        import torch
+        th = np.ascontiguousarray(thresh, dtype=np.uint32).reshape(-1)
+        dev = torch.device("cuda", self.device)
+        d_P = torch.zeros(max(len(th), 1) * 64, dtype=torch.int64, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _check(lib().dsm_debug_bdist_ptable_device(self.ctx, _ptr(th), len(th), _dptr(d_P), ctypes.c_void_p(st)),
+               "dsm_debug_bdist_ptable_device")
+        return d_P.cpu().numpy().view(np.uint64).reshape(-1, 64)
+
+    def reach_dist_many(self, traces, counts, thresh=(0x8000,), max_rounds=0, max_edges=0, inbox_limit=16,
+                        kind=CENSUS_DUMPS, max_states=1 << 16, max_depth=0, chunk=0, term_cap=None, witnesses=False,
+                        scratch_bytes=0, audit=False):
+        """The outcome probabilities of each of n systems (traces [n, np, max_instr] u16, counts
+        [n, np]) under every threshold, searched and distributed by one asynchronous launch on the
+        GPU -> the dict of pydsm.reach_dist_many.  With audit the reach batch audit runs behind it on
+        the same stream and the two are joined by terminal rank: term_words (a list per system),
+        mass_end_incoherent and p_end_incoherent (lists per system of n_thresh exact ints / floats:
+        the mass on terminals that completed and break an invariant; None for a system whose
+        terminals exceed term_cap or that carries DIST_F_EDGES)."""
+        import torch
+        tr, cn = np.ascontiguousarray(traces, dtype=np.uint16), np.ascontiguousarray(counts, dtype=np.uint32)
+        if tr.ndim != 3 or tr.shape[1:] != (self.np, self.max_instr) or cn.shape != tr.shape[:2]:
+            raise DsmError(E_INVAL, "reach_dist_many: systems of the engine's np and max_instr")
+        n = tr.shape[0]
+        dev = torch.device("cuda", self.device)
+        d_tr = torch.from_numpy(tr.view(np.int16).reshape(-1)).to(dev)
+        d_cn = torch.from_numpy(cn.view(np.int32).reshape(-1)).to(dev)
+        dopts = dist_batch_opts(thresh, max_rounds, max_edges)
+        nth = min(max(dopts.n_thresh, 1), DIST_MAX_THRESH)
+        ok = 0 < max_states <= REACH_BATCH_MAX_STATES
+        cap = max_states if ok else 1
+        term_cap = min(cap, 4096) if term_cap is None else term_cap
+        d_info = torch.zeros(max(n, 1) * len(REACH_INFO_FIELDS), dtype=torch.int64, device=dev)
+        d_dinfo = torch.zeros(max(n * nth, 1) * len(DIST_INFO_FIELDS), dtype=torch.int64, device=dev)
+        d_term = torch.zeros(5 * max(n * term_cap, 1), dtype=torch.int64, device=dev)
+        d_tm = torch.zeros(max(n * nth * term_cap, 1), dtype=torch.int64, device=dev)
+        d_par = torch.zeros(max(n * cap, 1), dtype=torch.int32, device=dev) if witnesses else None
+        d_msk = torch.zeros(max(n * cap, 1), dtype=torch.uint8, device=dev) if witnesses else None
+        opts = ReachOpts(inbox_limit, CENSUS_KINDS.get(kind, kind), max_states, max_depth, chunk)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _check(self.reach_batch_dist_device(d_tr, d_cn, n, opts, dopts, d_info, d_dinfo, d_term, d_tm, term_cap, d_par, d_msk,
+                                            scratch_bytes, st), "dsm_reach_batch_dist_device")
+        if audit:                             # behind the dist call on the stream: no host wait between them
+            d_ainfo2 = torch.zeros(max(n, 1) * (RAUDIT_INFO_DTYPE.itemsize // 8), dtype=torch.int64, device=dev)
+            d_info2 = torch.zeros_like(d_info)
+            d_term2 = torch.zeros_like(d_term)
+            d_tw = torch.zeros(max(n * term_cap, 1), dtype=torch.int32, device=dev)
+            _check(self.reach_batch_audit_device(d_tr, d_cn, n, opts, d_info2, d_ainfo2, d_term2, term_cap, None, None, None,
+                                                 None, d_tw, scratch_bytes, st), "dsm_reach_batch_audit_device")
+        info = d_info.cpu().numpy().view(REACH_INFO_DTYPE)[:n]          # .cpu() waits for the stream
+        dinfo = d_dinfo.cpu().numpy().view(DIST_INFO_DTYPE)
+        terms = d_term.cpu().numpy().view(REACH_TERMINAL_DTYPE)[:n * term_cap]
+        out = _reach_dist_many_result(info, dinfo, terms, d_tm.cpu().numpy().view(np.uint64), term_cap,
+                                      d_par.cpu().numpy().view(np.uint32) if witnesses else None,
+                                      d_msk.cpu().numpy() if witnesses else None, cap, nth)
+        if audit:
+            info2 = d_info2.cpu().numpy().view(REACH_INFO_DTYPE)[:n]
+            terms2 = d_term2.cpu().numpy().view(REACH_TERMINAL_DTYPE)[:n * term_cap].reshape(n, term_cap)
+            tw = d_tw.cpu().numpy().view(np.uint32)[:n * term_cap].reshape(n, term_cap)
+            assert info2.tobytes() == info.tobytes(), "reach_dist_many: the audit's search differs from the distribution's"
+            out["term_words"], out["mass_end_incoherent"], out["p_end_incoherent"] = [], [], []
+            for s in range(n):
+                nt = min(term_cap, int(info["terminals"][s]))
+                # both calls write the terminals in ascending state id: the join is by rank
+                assert terms2[s, :nt].tobytes() == out["terminals"][s].tobytes(), f"reach_dist_many: terminals of system {s}"
+                out["term_words"].append(tw[s, :nt])
+                if int(info["terminals"][s]) > term_cap or (int(out["dinfo"]["flags"][s, 0]) & DIST_F_EDGES):
+                    out["mass_end_incoherent"].append(None)
+                    out["p_end_incoherent"].append(None)
+                    continue
+                m = end_incoherent_mass(out["terminals"][s], tw[s, :nt], out["term_mass"][s])
+                out["mass_end_incoherent"].append(m)
+                out["p_end_incoherent"].append([v / DIST_ONE for v in m])
+        return out
 
     def shrink_many_device(self, d_traces, d_counts, n_sys, opts, sopts, d_out_traces, d_out_counts, d_orig, info, trail,
                            trail_cap, scratch_bytes=0, stream=0):

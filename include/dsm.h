@@ -66,7 +66,9 @@ extern "C" {
                              5 (+reach batch audit): additive -- that audit for a whole ensemble
                                 in one asynchronous launch (dsm_reach_batch_audit*) likewise;
                              5 (+profile): additive -- the access profile (dsm_profile_*) likewise;
-                             5 (+shrink): additive -- the test shrinker (dsm_shrink*) likewise */
+                             5 (+shrink): additive -- the test shrinker (dsm_shrink*) likewise;
+                             5 (+bdist): additive -- the reach batch distribution
+                                (dsm_reach_batch_dist*) likewise */
 
 #define DSM_MAX_NP 8             /* bitVector is one byte (README.md:51)                  */
 #define DSM_CACHE_SIZE 4         /* CACHE_SIZE      assignment.c:10                        */
@@ -1160,6 +1162,66 @@ int dsm_reach_batch_audit_device(dsm_ctx *ctx, const uint16_t *d_traces, const u
                                  dsm_reach_terminal *d_terminals, uint64_t term_cap,
                                  uint32_t *d_parents, uint8_t *d_masks, uint32_t *d_words,
                                  uint8_t *d_sets, uint32_t *d_term_words, void *stream);
+
+/* ---- reach batch distribution: the outcome probabilities of a whole ensemble ----------------- *
+ * The reach batch and the outcome distribution in one call: how LIKELY each system of an ensemble
+ * is to deadlock, overflow, fail an assertion or complete under the seeded schedules' thresholds.
+ * Inputs, options, limits and the rows of info, terminals, parents and masks are dsm_reach_batch's;
+ * the distribution adds, each may be NULL:
+ *   dinfo[s * n_thresh + j]: dsm_reach_dist's info of system s under thresh[j];
+ *   term_mass[(s * n_thresh + j) * term_cap + i] for i < min(term_cap, info[s].terminals): the mass
+ *     of terminal i (ascending state id; it does not need `terminals` itself).
+ * There is no round_mass; dinfo.rounds is written.  Entries of a system's own rows at and after
+ * those bounds are unspecified (the host call leaves them alone); nothing outside the rows is
+ * written.  For every s, every written value equals what dsm_reach_dist gives for that system alone
+ * under the same opts, thresholds and max_rounds -- but fp_collisions, as in dsm_reach_batch_device
+ * (DSM_DIST_F_INEXACT follows the side's own DSM_REACH_F_COLLISION).  edges counts the successors of
+ * the EXPANDED levels: a level dropped by DSM_REACH_F_STATES is in transitions and not in edges.
+ * A system with dinfo.edges > max_edges gets no distribution: each of its dinfo rows keeps thresh
+ * and edges, has flags = DSM_DIST_F_EDGES (| DSM_DIST_F_INEXACT after a collision) and every other
+ * field 0, and its written term_mass entries are 0; its search outputs are as ever.  Results never
+ * depend on chunk, on scratch_bytes, on how many systems are in flight or on the order of
+ * summation: every mass update is an integer addition. */
+#define DSM_DIST_F_EDGES 8u   /* the system has more edges than max_edges: no distribution */
+typedef struct dsm_dist_batch_opts {
+    uint32_t thresh[DSM_DIST_MAX_THRESH];
+    uint32_t n_thresh;        /* 1..DSM_DIST_MAX_THRESH, each thresh 1..65536 */
+    uint32_t max_rounds;      /* as dsm_reach_dist: 0 = 4096, at most DSM_DIST_MAX_ROUNDS */
+    uint64_t max_edges;       /* per system; 0 = 16 * max_states (np 4: never exceeded, a state has at
+                                 most 15 successors) or 64 * max_states (np 8) */
+    uint64_t reserved[2];     /* zero */
+} dsm_dist_batch_opts;
+/* host only: device scratch one system in flight needs under these options (0 for bad options);
+ * at least dsm_reach_batch_slab_bytes, and non-decreasing in max_states, chunk and max_edges
+ * (a max_edges above (2^np - 1) * max_states, which no system exceeds, adds nothing more) */
+uint64_t dsm_reach_batch_dist_slab_bytes(int np, const dsm_reach_opts *opts,
+                                         const dsm_dist_batch_opts *dopts);
+/* the host reference (no GPU): dsm_reach_dist over systems 0 .. n_sys-1, a plain loop, plus the
+ * max_edges rule (and dsm_reach where parents or masks are asked for).  A bad argument --
+ * dsm_reach_batch's, n_thresh 0 or above the cap, a threshold outside 1..65536, max_rounds above
+ * DSM_DIST_MAX_ROUNDS, a non-zero reserved word -- is DSM_E_INVAL with nothing written. */
+int dsm_reach_batch_dist(int np, const uint16_t *traces, const uint32_t *counts, uint32_t stride,
+                         uint64_t n_sys, const dsm_reach_opts *opts,
+                         const dsm_dist_batch_opts *dopts, dsm_reach_info *info, dsm_dist_info *dinfo,
+                         dsm_reach_terminal *terminals, uint64_t *term_mass, uint64_t term_cap,
+                         uint32_t *parents, uint8_t *masks);
+/* The same on the GPU, ASYNCHRONOUS on `stream` like dsm_reach_batch_device: one memset and one
+ * launch, no host wait.  The workgroup that searches a system keeps the search's own edges (a
+ * chunk's targets are in the visited table once the chunk has settled), runs the rounds of every
+ * threshold over them and then claims the next system.  The thresholds travel in the kernel's
+ * arguments, so calls with different thresholds may follow each other on the stream.  The slab is
+ * dsm_reach_batch_dist_slab_bytes'; the ctx's scratch, the claim counter, scratch_bytes and the
+ * "one run at a time, one stream" convention are dsm_reach_batch_device's: plain, audit and dist
+ * calls may follow each other on one ctx.  All pointers are device memory (d_info, d_dinfo,
+ * d_terminals and d_term_mass 8-byte aligned, d_parents 4-byte; a misaligned output is
+ * DSM_E_INVAL).  DSM_E_NOMEM, with nothing enqueued, when not one slab fits; n_sys == 0 is a
+ * no-op; every other error as in dsm_reach_batch_device and dsm_reach_batch_dist. */
+int dsm_reach_batch_dist_device(dsm_ctx *ctx, const uint16_t *d_traces, const uint32_t *d_counts,
+                                uint64_t n_sys, const dsm_reach_opts *opts,
+                                const dsm_dist_batch_opts *dopts, uint64_t scratch_bytes,
+                                dsm_reach_info *d_info, dsm_dist_info *d_dinfo,
+                                dsm_reach_terminal *d_terminals, uint64_t *d_term_mass,
+                                uint64_t term_cap, uint32_t *d_parents, uint8_t *d_masks, void *stream);
 
 /* ---- shrink: the minimal test that keeps a reachable defect ---------------------------------- *
  * The screens say THAT a test has a reachable defect; the shrinker says which of its instructions
